@@ -22,7 +22,15 @@ Other workloads (--workload): lidar (configs[1], 32 400 tokens), coop
 (configs[3] forward: vehicle 36 400 + infrastructure 44 400 tokens), stress4
 (configs[4]: 4 agents x 48 400 tokens, 1500 queries, fp16 policy).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the headline line
+(metric, value, unit, ms_per_step, dtype, config).  --dump-outputs DIR then
+writes what the last timed step returned (every tensor of the head's output,
+float32) as DIR/<name>.npy; the inputs and weights are seeded, so two builds
+can be compared output for output.  --full adds everything else to the line:
+the dominant kernel's roofline and PMC traffic, the weight-only-recomputed
+and bf16-policy frames, the voxel scatter-mean, the other configs' side keys
+and the CPU baseline (each with its own --no-* switch).
 With --gpus N > 1 and no torch.distributed environment, this process starts
 the N ranks itself (python -m torch.distributed.run, before any GPU call
 here) and exits with their status.  Frames are independent, so ranks share
@@ -198,13 +206,14 @@ def spawn_ranks(args):
     return dp.spawn(os.path.abspath(__file__), sys.argv[1:], args.gpus)
 
 
-def train_bench(workload, steps, warmup, env, dev):
+def train_bench(workload, steps, warmup, env, dev, last=None):
     """BASELINE configs[3]: CMTCoop head DDP training step on TUMTraf-shape
     synthetic frames (vehicle BEV 180x180 + 1 cam, infrastructure BEV 180x180
     + 3 cams, 900 queries + DN groups from 20 GT boxes, 6 layers), one frame
     per rank: training forward, Hungarian-matched losses, backward on the
     native kernels, bucketed RCCL gradient all-reduce, clip + AdamW.  Returns
-    (elapsed_max_s, steps_per_s_whole_job, last loss, memory lengths, params)."""
+    (elapsed_max_s, steps_per_s_whole_job, last loss, memory lengths, params);
+    ``last`` (a list) receives the latest step's predictions and loss."""
     from projects.mmdet3d_plugin.trainer import Trainer
     head, cfg, _, nks, _ = make_workload(workload, seed=dp.frame_seed(0, env), device=dev)
     w = WORKLOADS[workload]
@@ -229,14 +238,18 @@ def train_bench(workload, steps, warmup, env, dev):
         def step():
             preds = head.forward_train(agents, metas, gtb, gtl)
             loss[0] = tr.step(head.loss(gtb, gtl, [[p] for p in preds]))
+            if last is not None:
+                last[:] = [dict(preds=preds, loss=loss[0])]
         elapsed, value = dp.timed_frames(step, steps=steps, warmup=warmup, env=env,
                                          sync=torch.cuda.synchronize, device=dev)
         nparam = sum(p.numel() for p in tr.fp.params)
     return elapsed, value, float(loss[0].item()), nks, nparam
 
 
-def capture(step):
-    """Warm the step eagerly, then capture it as a HIP graph; returns replay."""
+def capture(step, last=None):
+    """Warm the step eagerly, then capture it as a HIP graph; returns the graph.
+    ``last`` (a list) receives what the captured step returned: the tensors every
+    replay writes, i.e. what a caller of the replayed frame reads."""
     for _ in range(2):
         step()
     torch.cuda.synchronize()
@@ -247,9 +260,58 @@ def capture(step):
         step()
         torch.cuda.synchronize()
         with torch.cuda.graph(graph):
-            step()
+            out = step()
     torch.cuda.current_stream().wait_stream(s)
+    if last is not None:
+        last[:] = [out]
     return graph
+
+
+def keep_last(step, last):
+    """``step`` as a callable that leaves its latest return value in ``last[0]``."""
+    def run():
+        last[:] = [step()]
+    return run
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def named_arrays(out, prefix="out"):
+    """Flatten nested tuples / lists / dicts of tensors into (name, tensor) pairs;
+    the name is the path of indices and keys."""
+    if torch.is_tensor(out):
+        return [(prefix, out)]
+    if isinstance(out, dict):
+        return [p for k in out for p in named_arrays(out[k], f"{prefix}_{k}")]
+    if isinstance(out, (list, tuple)):
+        return [p for i, v in enumerate(out) for p in named_arrays(v, f"{prefix}_{i}")]
+    return []
+
+
+def dump_outputs(out, path, limit=DUMP_LIMIT_BYTES):
+    """Write every tensor of ``out`` as ``path/<name>.npy``: float32 (float64 for
+    fp64 and integer tensors), at most ``limit`` bytes in all.  An array over its
+    equal share of the limit is cut to a fixed, seeded sample of its flattened
+    elements (ascending positions), the same from run to run."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = []
+    for name, t in named_arrays(out):
+        t = t.detach()
+        wide = t.dtype == torch.float64 or not (t.is_floating_point() or t.dtype == torch.bool)
+        arrays.append((name, t.to(torch.float64 if wide else torch.float32).cpu().numpy()))
+    if not arrays:
+        raise RuntimeError("--dump-outputs: the timed step returned no tensor")
+    share = limit // len(arrays)
+    written = {}
+    for name, a in arrays:
+        if a.nbytes > share:
+            keep = np.sort(np.random.default_rng(0).choice(a.size, size=share // a.itemsize, replace=False))
+            a = a.reshape(-1)[keep]
+        np.save(os.path.join(path, name + ".npy"), a)
+        written[name] = list(a.shape)
+    return written
 
 
 def with_metas(head, metas, replay, graph=True):
@@ -304,6 +366,12 @@ def main():
                          "[3] forward / [4]")
     ap.add_argument("--precision", default=None, choices=["bf16", "fp16", "ref", "exact"],
                     help="compute policy of the headline value (default: the workload's: ref, fp16 for stress4)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: roofline + PMC traffic of the dominant "
+                         "kernel, recomputed / bf16 frames, voxel scatter-mean, the other configs, the CPU "
+                         "baseline (each has its own --no-* switch below)")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-recompute", action="store_true",
                     help="skip the side key timing the frame with the weight-only encodings recomputed")
@@ -334,9 +402,12 @@ def main():
     w = WORKLOADS[args.workload]
     prec = args.precision or w["precision"]
     set_precision(prec)
+    last = [] if args.dump_outputs else None   # what the latest timed step returned
     if args.train:
-        elapsed, value, loss, nks, nparam = train_bench(args.workload, args.steps, args.warmup, env, dev)
+        elapsed, value, loss, nks, nparam = train_bench(args.workload, args.steps, args.warmup, env, dev, last)
         if rank == 0:
+            if last is not None:
+                dump_outputs(last[0], args.dump_outputs)
             print(json.dumps({
                 "metric": "head training steps/sec (DDP, one frame per GPU per step)", "value": round(value, 3),
                 "unit": "steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -357,25 +428,36 @@ def main():
     metas = step.metas
 
     with torch.no_grad():
-        run = capture(step).replay if not args.no_graph else step
+        if not args.no_graph:
+            run = capture(step, last).replay
+        else:
+            run = step if last is None else keep_last(step, last)
         elapsed, value = dp.timed_frames(with_metas(head, metas, run, not args.no_graph), steps=args.steps, warmup=args.warmup, env=env,
                                          sync=torch.cuda.synchronize, device=dev)
         value *= args.batch   # frames per forward
+        if last is not None:
+            if rank == 0:
+                dump_outputs(last[0], args.dump_outputs)
+            last.clear()
+
+        # --- everything below is beside the headline and runs under --full only ---
 
         # --- dominant kernel: the cross-attention core as the timed frame runs it (its 8 split
         # partials stay in the workspace for chain B1, which combines them in its prologue, ABI 19),
         # HIP events on its launch stream; PMC traffic from the same form
-        with region_timer() as rt:
-            for _ in range(3):
-                step()
-        attn_ms_all = rt.durations_ms("cross_attn")
-        attn_ms = sum(attn_ms_all) / len(attn_ms_all)
+        attn_ms = None
+        if args.full:
+            with region_timer() as rt:
+                for _ in range(3):
+                    step()
+            attn_ms_all = rt.durations_ms("cross_attn")
+            attn_ms = sum(attn_ms_all) / len(attn_ms_all)
 
         # --- the same frame with the weight-only encodings recomputed per frame (the reference
         # recomputes them on every forward, cmt_head.py:436, 489; the headline keeps them like weight
         # packs: WEIGHT_ONLY_KEPT)
         recompute = None
-        if not args.no_recompute and OPTIONS.bev_pos_cache:
+        if args.full and not args.no_recompute and OPTIONS.bev_pos_cache:
             with options(bev_pos_cache=False):
                 run_r = capture(step).replay if not args.no_graph else step
                 st_r = max(10, args.steps // 2)
@@ -390,7 +472,7 @@ def main():
         # --- the bf16 speed policy on the same frame (bf16 operands everywhere; NOT held to
         # north_star's 1e-3 -- reported beside the headline, never as it)
         side = None
-        if not args.no_ref and prec == "ref":
+        if args.full and not args.no_ref and prec == "ref":
             set_precision("bf16")
             run_b = capture(step).replay if not args.no_graph else step
             st_b = max(10, args.steps // 2)
@@ -402,27 +484,29 @@ def main():
             set_precision(prec)
 
         # --- voxel scatter-mean of ~30k points (timed separately)
-        vl = SPConvVoxelization(voxel_size=[0.075, 0.075, 0.2], point_cloud_range=[-54.0, -54.0, -5.0, 54.0, 54.0, 3.0],
-                                max_num_points=10, max_voxels=(120000, 160000), num_point_features=5).eval()
-        pts = S.synthetic_points(30000, [-54.0, -54.0, -5.0, 54.0, 54.0, 3.0], seed=rank, device=dev)
-        # three launches, voxel count kept on the device: captured as a graph like the frame
-        vstep = lambda: vl.forward_padded(pts, 5)  # noqa: E731
-        for _ in range(3):
-            vstep()
-        torch.cuda.synchronize()
-        vrun = capture(vstep).replay if not args.no_graph else vstep
-        nvox = 50
-        tv = time.perf_counter()
-        for _ in range(nvox):
-            vrun()
-        torch.cuda.synchronize()
-        vox_ms = (time.perf_counter() - tv) / nvox * 1e3
+        vox_ms = None
+        if args.full:
+            vl = SPConvVoxelization(voxel_size=[0.075, 0.075, 0.2], point_cloud_range=[-54.0, -54.0, -5.0, 54.0, 54.0, 3.0],
+                                    max_num_points=10, max_voxels=(120000, 160000), num_point_features=5).eval()
+            pts = S.synthetic_points(30000, [-54.0, -54.0, -5.0, 54.0, 54.0, 3.0], seed=rank, device=dev)
+            # three launches, voxel count kept on the device: captured as a graph like the frame
+            vstep = lambda: vl.forward_padded(pts, 5)  # noqa: E731
+            for _ in range(3):
+                vstep()
+            torch.cuda.synchronize()
+            vrun = capture(vstep).replay if not args.no_graph else vstep
+            nvox = 50
+            tv = time.perf_counter()
+            for _ in range(nvox):
+                vrun()
+            torch.cuda.synchronize()
+            vox_ms = (time.perf_counter() - tv) / nvox * 1e3
 
     # --- every other BASELINE config's number on the same line (GPU only): configs[1] lidar and
     # configs[4] stress4 forward frames/s, configs[3] coop training steps/s (tools/benchmark.py:110-138
     # timing pattern: warm-up, synchronize, timed loop)
     sides = {}
-    if not args.no_side and args.workload == "fusion" and args.batch == 1:
+    if args.full and not args.no_side and args.workload == "fusion" and args.batch == 1:
         del run
         torch.cuda.empty_cache()
         for key, fn in (("lidar", lambda: side_frames("lidar", args.side_steps, env, dev, not args.no_graph)),
@@ -435,12 +519,19 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     # mean algorithmic FLOPs of one cross-attention launch (agents may differ in Nk)
     nq = w["nq"]
-    flop_launch = args.batch * sum(cross_attn_flops(nq=nq, nk=nk) for nk in nks) / len(nks)
-    achieved = flop_launch / (attn_ms * 1e-3) / 1e12
-    peak = PEAK_TFLOPS.get(prec, PEAK_TFLOPS["bf16"])
-    traffic, traffic_src = (None, None)
-    if not args.no_traffic:
-        traffic, traffic_src = load_traffic(args.workload, sum(nks) // len(nks))
+    roofline = None
+    if args.full:
+        flop_launch = args.batch * sum(cross_attn_flops(nq=nq, nk=nk) for nk in nks) / len(nks)
+        achieved = flop_launch / (attn_ms * 1e-3) / 1e12
+        peak = PEAK_TFLOPS.get(prec, PEAK_TFLOPS["bf16"])
+        traffic, traffic_src = (None, None)
+        if not args.no_traffic:
+            traffic, traffic_src = load_traffic(args.workload, sum(nks) // len(nks))
+        roofline = {"kernel": "cmt_attn_fwd (cross-attention core attn_pb2_kernel; its split partials are "
+                              "combined by the next kernel, chain B1, as in the timed frame)", "bound": "mfma",
+                    "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
+                    "frac": round(achieved / peak, 4), "traffic": traffic, "traffic_source": traffic_src,
+                    "avg_launch_ms": round(attn_ms, 5), "flop_per_launch": flop_launch}
     result = {
         "metric": METRIC,
         "value": round(value, 3),
@@ -464,18 +555,17 @@ def main():
                    "weight_only_kept": WEIGHT_ONLY_KEPT if OPTIONS.bev_pos_cache else [],
                    "camera_metas_staged_per_step": bool(getattr(head, "_meta_plan", None)) and not args.no_graph,
                    "decoder_gflop_per_frame": round(sum(decoder_frame_flops(nq=nq, nk=nk) for nk in nks) / 1e9, 2)},
-        "roofline": {"kernel": "cmt_attn_fwd (cross-attention core attn_pb2_kernel; its split partials are "
-                               "combined by the next kernel, chain B1, as in the timed frame)", "bound": "mfma",
-                     "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
-                     "frac": round(achieved / peak, 4), "traffic": traffic, "traffic_source": traffic_src,
-                     "avg_launch_ms": round(attn_ms, 5), "flop_per_launch": flop_launch},
-        "bf16_policy": side,
-        "weight_only_recomputed": recompute,
-        "voxel_scatter_mean_ms": round(vox_ms, 4),
-        **sides,
-        "cpu_baseline": None,
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full:
+        result.update({
+            "roofline": roofline,
+            "bf16_policy": side,
+            "weight_only_recomputed": recompute,
+            "voxel_scatter_mean_ms": round(vox_ms, 4),
+            **sides,
+            "cpu_baseline": None,
+        })
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(args.workload, args.cpu_seconds, seed=dp.frame_seed(0, env))
     if rank == 0:
         print(json.dumps(result), flush=True)

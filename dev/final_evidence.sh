@@ -7,7 +7,7 @@
 #   3. FETCH_SIZE / WRITE_SIZE passes (separate) of the same frame, eager, the cross-attention core
 #      as the frame runs it (split partials for chain B1) -> profiles/<tag>_fusion_attn_pmc_summary.json;
 #   4. SQ / TCC counter passes (dev/pmc_passes.sh) of the pre-attention kernels on their probes;
-#   5. the default bench line (every config's side key, the CPU baseline);
+#   5. the full bench line (bench.py --full: every config's side key, the CPU baseline);
 #   6. the coop training step's kernel trace.
 #   gpurun --timeout 1200 -- bash dev/final_evidence.sh r6z [skip-tests]
 set -uo pipefail
@@ -42,7 +42,7 @@ for k in convh:conv_halo kv:kvproj_x3 mlp:mlp2_x3; do
     timeout -k 10 400 bash dev/pmc_passes.sh "$OUT/pmc_${k%%:*}" "${k##*:}" dev/kernel_probe.py "${k%%:*}" --iters 5 \
         > "$OUT/pmc_${k%%:*}.txt" 2>&1 || { echo "pmc ${k%%:*} failed"; tail "$OUT/pmc_${k%%:*}.txt"; exit 1; }
 done
-timeout -k 10 500 python3 -u bench.py > "$OUT/bench_fusion.json" 2> "$OUT/bench_fusion.log" \
+timeout -k 10 500 python3 -u bench.py --full > "$OUT/bench_fusion.json" 2> "$OUT/bench_fusion.log" \
     || { echo "bench failed"; tail "$OUT/bench_fusion.log"; exit 1; }
 cat "$OUT/bench_fusion.json"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/train_trace" -o run --output-format csv -- \

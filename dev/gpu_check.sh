@@ -2,7 +2,7 @@
 # One GPU-box pass (run from the repo root under gpurun): GPU parity tests,
 # smoke(), the rocprofv3 kernel-trace/stats pass and the FETCH_SIZE /
 # WRITE_SIZE PMC passes (separate runs, guide rule) of the bench workload,
-# the traffic summary bench.py reads, then the bench line itself.
+# the traffic summary bench.py --full reads, then the full bench line itself.
 # Every GPU step has its own time limit; the first failure ends the script.
 #   gpurun --timeout 1100 -- bash dev/gpu_check.sh r2a [tests|prof|bench|all] [workload]
 set -euo pipefail
@@ -42,7 +42,7 @@ if [[ $WHAT == all || $WHAT == prof ]]; then
     echo "profiles done"; cat "$P/traffic.txt"
 fi
 if [[ $WHAT == all || $WHAT == bench ]]; then
-    timeout -k 10 400 python -u bench.py --workload $WL > "$OUT/bench_$WL.json" 2> "$OUT/bench_$WL.log" \
+    timeout -k 10 400 python -u bench.py --full --workload $WL > "$OUT/bench_$WL.json" 2> "$OUT/bench_$WL.log" \
         || { echo "bench failed"; tail -20 "$OUT/bench_$WL.log"; exit 1; }
     cat "$OUT/bench_$WL.json"
 fi
