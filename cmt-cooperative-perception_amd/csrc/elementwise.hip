@@ -738,7 +738,9 @@ extern "C" int cmt_add_cast(const float* X, const float* P, int rows, int C, int
 
 extern "C" int cmt_pos2embed(const float* pos, int64_t pos_stride, int n, int F, int mode, int grid_h,
                              int grid_w, void* out, int odtype, int64_t ldo, void* stream) {
-    CMT_REQUIRE(out && n >= 0 && F > 0 && F % 4 == 0 && ldo % 8 == 0, "cmt_pos2embed: bad arguments");
+    CMT_REQUIRE(out && n >= 0 && ldo % 8 == 0, "cmt_pos2embed: bad arguments");
+    // a thread writes 8 consecutive outputs from one of the two halves [y(F) | x(F)]
+    CMT_REQUIRE(F > 0 && F % 8 == 0, "cmt_pos2embed: F (num_pos_feats) must be a positive multiple of 8");
     CMT_REQUIRE(pos != nullptr || (grid_h > 0 && grid_w > 0 && n == grid_h * grid_w),
                 "cmt_pos2embed: grid mode needs n == grid_h*grid_w");
     CMT_REQUIRE(odtype == CMT_F32 || odtype == CMT_F16 || odtype == CMT_BF16 || odtype == CMT_F16P,

@@ -401,8 +401,10 @@ int cmt_add_cast(const float* X, const float* P, int rows, int C, int lowp_dtype
 /* ------------------------------------------------------------------------
  * Coordinate encodings.
  * cmt_pos2embed: cmt_head.py:40-50.  pos [n, pos_stride] (x, y in the first two
- *   fp32 lanes), out [n, 2F] of odtype (F = num_pos_feats); mode 1 applies
- *   sigmoid(inverse_sigmoid(p)) first (query_embed, cmt_head.py:470).
+ *   fp32 lanes), out [n, 2F] of odtype (F = num_pos_feats, F % 8 == 0: the y and
+ *   the x half are each written in groups of 8 outputs; row stride ldo, ldo % 8
+ *   == 0); mode 1 applies sigmoid(inverse_sigmoid(p)) first (query_embed,
+ *   cmt_head.py:470).
  *   If pos == NULL the BEV grid centres (coords_bev, cmt_head.py:324-337) of a
  *   grid_h x grid_w map are generated in place of the input.
  * cmt_rv_pe_coords: _rv_pe geometry (cmt_head.py:417-432): out [BV*h*w, 3*D] (odtype)

@@ -97,6 +97,52 @@ def test_task_head_k1_equals_per_query_linear():
         assert torch.allclose(out["vel"][l, 0], ref, atol=1e-5)
 
 
+@pytest.mark.parametrize("final_kernel", [1, 3])
+def test_task_tail_reference_matches_oracle(final_kernel):
+    """The float64 reference the GPU test holds cmt_task_head_tail to
+    (tests/test_gpu_post_kernels.py::task_tail_ref64, fed the packed layouts of
+    SeparateTaskHead.packed) equals separate_task_head + box_epilogue run in float64
+    on a tiny head with randomised norm weights and biases."""
+    from test_gpu_post_kernels import CLAMP_ROWS, task_tail_ref64
+    L, B, Nq, C, hc = 2, 2, 7, 256, 64
+    cfg, sd = _tiny_head_sd(final_kernel=final_kernel, L=L, Nq=Nq)
+    g = torch.Generator().manual_seed(final_kernel)
+    sd = {k: v.double() for k, v in sd.items() if k.startswith("task_heads.0.")}
+    for k in sd:
+        if k.endswith(".1.weight"):
+            sd[k] = 1 + 0.1 * torch.randn(sd[k].shape, generator=g, dtype=torch.float64)
+        elif k.endswith(".bias"):
+            sd[k] = torch.randn(sd[k].shape, generator=g, dtype=torch.float64)
+    heads = dict(cfg["common_heads"], cls_logits=(10, 2))
+    names = list(heads)
+    head_out = [heads[n][0] for n in names]
+    x = torch.randn(L, B, Nq, C, generator=g, dtype=torch.float64)
+    ref_pts = torch.rand(B, Nq, 3, generator=g, dtype=torch.float64)
+    ref_pts[:, :3] = torch.tensor(CLAMP_ROWS, dtype=torch.float64)
+    pc = cfg["bbox_coder"]["pc_range"]
+    outs = O.box_epilogue(O.separate_task_head(x, sd, "task_heads.0", heads, final_kernel, L),
+                          O.inverse_sigmoid(ref_pts), pc)
+    want = torch.cat([outs[n] for n in names], -1)
+    # conv #1 of every head -> H1 [L, B*Nq, nheads*hc]; the other operands as packed() lays them out
+    xin = x.permute(1, 0, 3, 2).reshape(B, L * C, Nq)
+    pad = final_kernel // 2
+    H1, gw, gb, W2, B2 = [], [], [], [], []
+    for n, o in zip(names, head_out):
+        p = f"task_heads.0.{n}"
+        h = torch.nn.functional.conv1d(xin, sd[p + ".0.weight"], None, padding=pad, groups=L)
+        H1.append(h.view(B, L, hc, Nq).permute(1, 0, 3, 2))
+        gw.append(sd[p + ".1.weight"].view(L, hc))
+        gb.append(sd[p + ".1.bias"].view(L, hc))
+        W2.append(sd[p + ".3.weight"].view(L, o, hc, final_kernel).permute(0, 1, 3, 2))
+        B2.append(sd[p + ".3.bias"].view(L, o))
+    got = task_tail_ref64(torch.cat(H1, -1).reshape(L, B * Nq, -1), torch.cat(gw, 1), torch.cat(gb, 1),
+                          torch.cat(W2, 1), torch.cat(B2, 1), ref_pts, B=B, Nq=Nq, head_out=head_out,
+                          k=final_kernel, center_col=sum(head_out[:names.index("center")]),
+                          height_col=sum(head_out[:names.index("height")]), pc_range=pc)
+    assert got.shape == want.shape == (L, B, Nq, sum(head_out))
+    assert (got - want).abs().max().item() < 1e-9
+
+
 def test_coop_identical_agents_equals_single():
     from projects.mmdet3d_plugin import synthetic as S
     head, cfg, _ = S.build_synthetic_head("cmtcoop_lidar_tumtraf", num_query=16, num_layers=1,
