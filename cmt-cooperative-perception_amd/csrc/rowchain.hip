@@ -33,18 +33,13 @@
 // registers halve, and the workgroup keeps twice as many loads in flight --
 // each workgroup is bound by how fast one CU pulls its 128-384 KB of weights
 // and row data from L2, not by its MFMAs.
-#include "cmt_common.h"
+#include "rowchain_common.h"
 
 #include <cstdio>
 #include <cstdlib>
 
 namespace {
 
-constexpr int RB = 32;                         // query rows per workgroup
-constexpr int CE = 256;                        // embed dims
-constexpr int NWV = 8;                         // waves
-constexpr int NTC = 64 * NWV;                  // threads
-constexpr int VPL = CE / NWV / 2;              // values per lane of a row (its 32-column tile, lane pair)
 constexpr int KSTG = 32;                       // k per weight stage
 constexpr int NSTG = 6;                        // weight ring depth
 constexpr int STG_BYTES = CE * KSTG * 2;       // 16 KB
@@ -53,7 +48,6 @@ constexpr int ACT_BYTES = RB * CE * 2;         // 16 KB operand image [32][256] 
 constexpr int OFF_ACT_A = NSTG * STG_BYTES;    // 96 KB
 constexpr int OFF_ACT_B = OFF_ACT_A + ACT_BYTES;
 constexpr int OFF_PRM = OFF_ACT_B + ACT_BYTES; // fp32 parameter block
-constexpr int PRM_A = 1024, PRM_B = 3840;      // floats (cmt_hip.h cmt_chain_args.prm)
 constexpr int OFF_RED = OFF_PRM + PRM_B * 4;
 constexpr int LDS_TOTAL = OFF_RED + 2 * NWV * RB * 4;
 constexpr int DMA_PER_STAGE = STG_BYTES / 16 / NTC;   // 16-byte LDS-DMA pieces per thread per stage
@@ -69,10 +63,9 @@ __device__ __forceinline__ void rc_wait() {
 }
 
 template <typename T>
-struct Eng {
+struct Eng : RowCtx<OFF_PRM, OFF_RED> {
     typedef typename mfma_traits<T>::frag frag;
-    char* lds;
-    int tid, lane, wave, lr, lh;
+    int tid;
     int issued, consumed, nstages;
     const T *w0, *w1, *w2;   // weights of sub-GEMMs 0, 1, 2 ([256 rows][K], leading dims below)
     int ld0, ld1, ld2;
@@ -120,7 +113,7 @@ struct Eng {
         const int kc = consumed % SUB_STAGES;
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-            const frag af = *(const frag*)(A + lr * (CE * 2) + (((kc * 4 + 2 * ks + lh) ^ (lr & 15)) << 4));
+            const frag af = *(const frag*)act_at(A, lr, kc * 4 + 2 * ks + lh);
             const int n = wave * 32 + lr;
             const frag wf = *(const frag*)(Wt + n * (KSTG * 2) + (((2 * ks + lh) ^ ((n >> 2) & 3)) << 4));
             acc = mfma_traits<T>::mma(wf, af, acc);
@@ -165,49 +158,9 @@ struct Eng {
         for (int kc = 0; kc < SUB_STAGES; ++kc)
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
-                const frag af = *(const frag*)(A + lr * (CE * 2) + (((kc * 4 + 2 * ks + lh) ^ (lr & 15)) << 4));
+                const frag af = *(const frag*)act_at(A, lr, kc * 4 + 2 * ks + lh);
                 acc = mfma_traits<T>::mma(wr[kc][ks], af, acc);
             }
-    }
-
-    // column of this lane's value r (4 consecutive per group r >> 2) in its wave's 32-column tile
-    __device__ __forceinline__ int col(int r) const { return wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh; }
-
-    __device__ __forceinline__ const float* prm() const { return (const float*)(lds + OFF_PRM); }
-
-    // sum over the row's 256 columns (this lane's 16, the lane pair, the 8 waves); slots alternate
-    __device__ __forceinline__ float row_sum(float x, int slot) {
-        x = pair_sum(x);
-        float* red = (float*)(lds + OFF_RED);
-        if (lh == 0) red[(slot * NWV + wave) * RB + lr] = x;
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        barrier_mem();
-        float t = 0.f;
-#pragma unroll
-        for (int w = 0; w < NWV; ++w) t += red[(slot * NWV + w) * RB + lr];
-        return t;
-    }
-
-    // in-place LayerNorm (nn.LayerNorm: biased variance) with weight / bias at parameter offsets
-    __device__ __forceinline__ void layernorm(float (&v)[VPL], int w_off, int b_off, float eps) {
-        float s = 0.f;
-#pragma unroll
-        for (int i = 0; i < VPL; ++i) s += v[i];
-        const float mean = row_sum(s, 0) * (1.f / CE);
-        float q = 0.f;
-#pragma unroll
-        for (int i = 0; i < VPL; ++i) {
-            const float d = v[i] - mean;
-            q += d * d;
-        }
-        const float rstd = rsqrtf(row_sum(q, 1) * (1.f / CE) + eps);
-        const float* pw = prm() + w_off;
-        const float* pb = prm() + b_off;
-#pragma unroll
-        for (int r = 0; r < VPL; ++r) {
-            const int c = col(r);
-            v[r] = (v[r] - mean) * rstd * pw[c] + pb[c];
-        }
     }
 
     // this lane's values of its row into an operand image [32][256] (16-B chunks XOR row & 15)
@@ -217,53 +170,10 @@ struct Eng {
         for (int g = 0; g < 4; ++g) {
             const int c0 = col(4 * g);
             const t4 x = {(T)v[4 * g], (T)v[4 * g + 1], (T)v[4 * g + 2], (T)v[4 * g + 3]};
-            *(t4*)(act + lr * (CE * 2) + (((c0 >> 3) ^ (lr & 15)) << 4) + (c0 & 7) * 2) = x;
+            *(t4*)(act_at(act, lr, c0 >> 3) + (c0 & 7) * 2) = x;
         }
     }
 };
-
-// this lane's VPL fp32 values of `row` (columns of Eng::col) from a [rows][256] fp32 matrix
-__device__ __forceinline__ void load_row(const float* M, int row, int wave, int lh, float (&v)[VPL]) {
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        const f32x4 x = *(const f32x4*)(M + (int64_t)row * CE + wave * 32 + 8 * g + 4 * lh);
-        v[4 * g] = x[0];
-        v[4 * g + 1] = x[1];
-        v[4 * g + 2] = x[2];
-        v[4 * g + 3] = x[3];
-    }
-}
-
-__device__ __forceinline__ void store_row(float* M, int row, int wave, int lh, const float (&v)[VPL]) {
-#pragma unroll
-    for (int g = 0; g < 4; ++g)
-        *(f32x4*)(M + (int64_t)row * CE + wave * 32 + 8 * g + 4 * lh) =
-            f32x4{v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]};
-}
-
-// The B1 -> B2 partials workspace is private to the chains, so it is kept in
-// the lanes' own order: per (plane, row block, wave, 16-byte group j) one
-// contiguous 1 KB slab, lane-major.  Every wave instruction then moves 1 KB
-// of consecutive bytes (8 cache lines) instead of 32-byte pieces of 32 rows
-// (32 lines), which is what bounded chain B2 (~9 us for one workgroup).
-__device__ __forceinline__ void load_tile(const float* M, int rb, int wave, int lane, float (&v)[VPL]) {
-    const float* p = M + (int64_t)rb * RB * CE + wave * (VPL * 64) + lane * 4;
-#pragma unroll
-    for (int j = 0; j < VPL / 4; ++j) {
-        const f32x4 x = *(const f32x4*)(p + j * 256);
-        v[4 * j] = x[0];
-        v[4 * j + 1] = x[1];
-        v[4 * j + 2] = x[2];
-        v[4 * j + 3] = x[3];
-    }
-}
-
-__device__ __forceinline__ void store_tile(float* M, int rb, int wave, int lane, const float (&v)[VPL]) {
-    float* p = M + (int64_t)rb * RB * CE + wave * (VPL * 64) + lane * 4;
-#pragma unroll
-    for (int j = 0; j < VPL / 4; ++j)
-        *(f32x4*)(p + j * 256) = f32x4{v[4 * j], v[4 * j + 1], v[4 * j + 2], v[4 * j + 3]};
-}
 
 // KIND is compile-time: each chain kind gets its own register allocation (chain A's two
 // register-streamed weight sets would otherwise be live in every kind's code)
@@ -282,7 +192,7 @@ __global__ __launch_bounds__(NTC, 1) void chain_kernel(cmt_chain_args a) {
     constexpr int kind = KIND;
     const bool has_next = a.Wn != nullptr;
     // workgroup -> (row block, part g)
-    const int parts = kind == 0 ? 1 : kind == 1 ? 4 : (has_next ? 3 : 1);
+    const int parts = chain_parts(kind, has_next);
     const int rb = blockIdx.x / parts, g = blockIdx.x - rb * parts;
     const T* Wo = (const T*)a.Wo;
     const bool wo_regs = kind == 0 && a.wo_frag;   // chain A with fragment-major Wo: no LDS weight ring
@@ -381,11 +291,11 @@ __global__ __launch_bounds__(NTC, 1) void chain_kernel(cmt_chain_args a) {
             else e.sub_gemm(actA, acc, true);                          // out_proj (LDS weight ring)
         }
         {
-            const float* bo = e.prm();
+            const float* bo = e.prm() + prm_a::bo;
 #pragma unroll
             for (int r = 0; r < VPL; ++r) v[r] = acc[r] + bo[e.col(r)] + res[r];
         }
-        e.layernorm(v, 256, 512, eps);                                 // norms[0]
+        e.layernorm(v, prm_a::ln_w, prm_a::ln_b, eps);                 // norms[0]
         float y[VPL];
 #pragma unroll
         for (int i = 0; i < VPL; ++i) {
@@ -394,7 +304,7 @@ __global__ __launch_bounds__(NTC, 1) void chain_kernel(cmt_chain_args a) {
         }
         e.put_act(actB, v);                                            // lowp(y + query_pos)
         e.sub_gemm_regs(actB, wr, acc);                                // cross-attn Q projection
-        const float* bq = e.prm() + 768;
+        const float* bq = e.prm() + prm_a::bq;
         t4 qo[4];
 #pragma unroll
         for (int gg = 0; gg < 4; ++gg) {
@@ -418,22 +328,22 @@ __global__ __launch_bounds__(NTC, 1) void chain_kernel(cmt_chain_args a) {
         // ---------------- chain B1: out_proj + norms[1], then FFN quarter g
         e.sub_gemm(actA, acc, true);                                   // out_proj
         {
-            const float* bo = e.prm();
+            const float* bo = e.prm() + prm_b::bo;
 #pragma unroll
             for (int r = 0; r < VPL; ++r) v[r] = acc[r] + bo[e.col(r)] + res[r];
         }
-        e.layernorm(v, 256, 512, eps);                                 // norms[1] -> o (FFN residual)
+        e.layernorm(v, prm_b::ln1_w, prm_b::ln1_b, eps);               // norms[1] -> o (FFN residual)
         e.put_act(actB, v);                                            // lowp(o): fc1 operand
         e.sub_gemm(actB, acc, true);                                   // fc1 rows [256g, 256g + 256)
         {
-            const float* b1 = e.prm() + 768 + 256 * g;
+            const float* b1 = e.prm() + prm_b::b1 + CE * g;
             float h[VPL];
 #pragma unroll
             for (int r = 0; r < VPL; ++r) h[r] = fmaxf(acc[r] + b1[e.col(r)], 0.f);
             e.put_act(actA, h);                                        // hidden quarter g = fc2 K block g
         }
         e.sub_gemm_regs(actA, wr, acc);                                // fc2 partial over K block g
-        const float* b2 = e.prm() + 1792;
+        const float* b2 = e.prm() + prm_b::b2;
 #pragma unroll
         for (int r = 0; r < VPL; ++r) {
             float x = acc[r];
@@ -447,12 +357,12 @@ __global__ __launch_bounds__(NTC, 1) void chain_kernel(cmt_chain_args a) {
     // ---------------- chain B2: norms[2] (+ post_norm), next layer's in_proj block g
 #pragma unroll
     for (int i = 0; i < VPL; ++i) v[i] = res[i];
-    e.layernorm(v, 2048, 2304, eps);                                   // norms[2] -> next query
+    e.layernorm(v, prm_b::ln2_w, prm_b::ln2_b, eps);                   // norms[2] -> next query
     float y[VPL];
 #pragma unroll
     for (int i = 0; i < VPL; ++i) y[i] = v[i];
     if (g == 0) {
-        e.layernorm(v, 2560, 2816, eps);                               // post_norm -> layer output
+        e.layernorm(v, prm_b::post_w, prm_b::post_b, eps);             // post_norm -> layer output
 #pragma unroll
         for (int i = 0; i < VPL; ++i) {
             float x = v[i];
@@ -468,7 +378,7 @@ __global__ __launch_bounds__(NTC, 1) void chain_kernel(cmt_chain_args a) {
         for (int i = 0; i < VPL; ++i) u[i] = y[i] + qp[i];             // qp = 0 for the V block
         e.put_act(actA, u);                                            // lowp(y + pos) (Q|K) / lowp(y) (V)
         e.sub_gemm_regs(actA, wr, acc);
-        const float* bqkv = e.prm() + 3072 + g * CE;
+        const float* bqkv = e.prm() + prm_b::bn + g * CE;
 #pragma unroll
         for (int gg = 0; gg < 4; ++gg) {
             const int c0 = e.col(4 * gg);
@@ -527,8 +437,7 @@ extern "C" int cmt_chain(const cmt_chain_args* ap, void* stream) {
                 "cmt_chain: buffers must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     if (a.dtype == CMT_F16P) return cmt_chain_x3(a, s);   // rowchain_x3.hip
-    const int parts = a.kind == 0 ? 1 : a.kind == 1 ? 4 : (a.Wn ? 3 : 1);
-    const unsigned grid = (unsigned)(cdiv(a.rows, RB) * parts);
+    const unsigned grid = (unsigned)(cdiv(a.rows, RB) * chain_parts(a.kind, a.Wn != nullptr));
 #define CHAIN_LAUNCH(T)                                                    \
     do {                                                                   \
         if (a.kind == 0) chain_kernel<T, 0><<<grid, NTC, 0, s>>>(a);       \

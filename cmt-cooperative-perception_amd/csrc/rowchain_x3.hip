@@ -28,7 +28,7 @@
 // ordinary compiler-visible loads (its waitcnt pass counts them exactly).
 // MFMA 32x32x16 in the swapped form (lane = query row), so a row's LayerNorm
 // reduces over registers, the lane pair and the 8 waves.
-#include "cmt_common.h"
+#include "rowchain_common.h"
 
 #ifdef CMT_STAMPS
 // diagnostic build only (make OUT=../lib_stamps HIPFLAGS+=-DCMT_STAMPS): shader-clock stamps of
@@ -48,11 +48,6 @@ extern "C" int cmt_debug_chain_stamps(unsigned long long* host) {
 
 namespace {
 
-constexpr int RB = 32;                    // query rows per workgroup
-constexpr int CE = 256;                   // embed dims
-constexpr int NWV = 8;                    // waves
-constexpr int NTC = 64 * NWV;             // threads
-constexpr int VPL = CE / NWV / 2;         // values per lane of a row (16)
 constexpr int KS = CE / 16;               // MFMA k-steps per sub-GEMM
 constexpr int WRING_DEFAULT = 16;         // k-steps of weight fragments in flight per wave (a whole
                                           // sub-GEMM: one sub-GEMM ahead)
@@ -60,12 +55,8 @@ constexpr int PLANE = RB * CE * 2;        // one f16 image [32][256]: 16 KB
 constexpr int ACT = 2 * PLANE;            // a pair image: hi plane, lo plane
 constexpr int OFF_A = 0, OFF_B = ACT;
 constexpr int OFF_PRM = 2 * ACT;
-constexpr int PRM_A = 1024, PRM_B = 3840; // floats (cmt_hip.h cmt_chain_args.prm)
 constexpr int OFF_RED = OFF_PRM + PRM_B * 4;
 constexpr int LDS_TOTAL = OFF_RED + 2 * NWV * RB * 4;
-
-// column of lane value r in wave w's 32-column tile
-__device__ __forceinline__ int xcol(int wave, int lh, int r) { return wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh; }
 
 // Weight stream of one wave: up to 3 sub-GEMMs, each a fragment-major pair pack (the Wn layout,
 // cmt_hip.h: hi pack then lo pack, lo_off elements apart) of which this wave reads block g.
@@ -85,47 +76,7 @@ struct WStream {
     }
 };
 
-struct Ctx {
-    char* lds;
-    int lane, wave, lr, lh;
-
-    __device__ __forceinline__ int col(int r) const { return xcol(wave, lh, r); }
-    __device__ __forceinline__ const float* prm() const { return (const float*)(lds + OFF_PRM); }
-
-    // sum over the row's 256 columns (this lane's 16, the lane pair, the 8 waves); slots alternate
-    __device__ __forceinline__ float row_sum(float x, int slot) const {
-        x = pair_sum(x);
-        float* red = (float*)(lds + OFF_RED);
-        if (lh == 0) red[(slot * NWV + wave) * RB + lr] = x;
-        barrier_mem();
-        float t = 0.f;
-#pragma unroll
-        for (int w = 0; w < NWV; ++w) t += red[(slot * NWV + w) * RB + lr];
-        return t;
-    }
-
-    // nn.LayerNorm (biased variance), weight / bias at parameter offsets
-    __device__ __forceinline__ void layernorm(float (&v)[VPL], int w_off, int b_off, float eps) const {
-        float s = 0.f;
-#pragma unroll
-        for (int i = 0; i < VPL; ++i) s += v[i];
-        const float mean = row_sum(s, 0) * (1.f / CE);
-        float q = 0.f;
-#pragma unroll
-        for (int i = 0; i < VPL; ++i) {
-            const float d = v[i] - mean;
-            q += d * d;
-        }
-        const float rstd = rsqrtf(row_sum(q, 1) * (1.f / CE) + eps);
-        const float* pw = prm() + w_off;
-        const float* pb = prm() + b_off;
-#pragma unroll
-        for (int r = 0; r < VPL; ++r) {
-            const int c = col(r);
-            v[r] = (v[r] - mean) * rstd * pw[c] + pb[c];
-        }
-    }
-
+struct Ctx : RowCtx<OFF_PRM, OFF_RED> {
     // this lane's values of its row into a pair image (hi plane, lo plane)
     __device__ __forceinline__ void put_act(char* act, const float (&v)[VPL]) const {
         typedef pair_t p4 __attribute__((ext_vector_type(4)));
@@ -139,7 +90,7 @@ struct Ctx {
                 h[j] = (pair_t)x;
                 l[j] = (pair_t)(x - (float)h[j]);
             }
-            const int off = lr * (CE * 2) + (((c0 >> 3) ^ (lr & 15)) << 4) + (c0 & 7) * 2;
+            const int off = act_at(0, lr, c0 >> 3) + (c0 & 7) * 2;
             *(p4*)(act + off) = h;
             *(p4*)(act + PLANE + off) = l;
         }
@@ -154,7 +105,7 @@ struct Ctx {
 #pragma unroll
         for (int kk = 0; kk < KS; ++kk) {
             const int step = SUB * KS + kk;
-            const int off = lr * (CE * 2) + (((2 * kk + lh) ^ (lr & 15)) << 4);
+            const int off = act_at(0, lr, 2 * kk + lh);
             const pair8_t ah = *(const pair8_t*)(act + off);
             const pair8_t al = *(const pair8_t*)(act + PLANE + off);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ws.rh[step % WRING], al, acc, 0, 0, 0);
@@ -164,45 +115,6 @@ struct Ctx {
         }
     }
 };
-
-// this lane's VPL fp32 values of `row` (columns xcol) from a [rows][256] fp32 matrix
-__device__ __forceinline__ void load_row(const float* M, int row, int wave, int lh, float (&v)[VPL]) {
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        const f32x4 x = *(const f32x4*)(M + (int64_t)row * CE + wave * 32 + 8 * g + 4 * lh);
-        v[4 * g] = x[0];
-        v[4 * g + 1] = x[1];
-        v[4 * g + 2] = x[2];
-        v[4 * g + 3] = x[3];
-    }
-}
-
-__device__ __forceinline__ void store_row(float* M, int row, int wave, int lh, const float (&v)[VPL]) {
-#pragma unroll
-    for (int g = 0; g < 4; ++g)
-        *(f32x4*)(M + (int64_t)row * CE + wave * 32 + 8 * g + 4 * lh) =
-            f32x4{v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]};
-}
-
-// the B1 -> B2 partials in the lanes' own order (rowchain.hip's private layout)
-__device__ __forceinline__ void load_tile(const float* M, int rb, int wave, int lane, float (&v)[VPL]) {
-    const float* p = M + (int64_t)rb * RB * CE + wave * (VPL * 64) + lane * 4;
-#pragma unroll
-    for (int j = 0; j < VPL / 4; ++j) {
-        const f32x4 x = *(const f32x4*)(p + j * 256);
-        v[4 * j] = x[0];
-        v[4 * j + 1] = x[1];
-        v[4 * j + 2] = x[2];
-        v[4 * j + 3] = x[3];
-    }
-}
-
-__device__ __forceinline__ void store_tile(float* M, int rb, int wave, int lane, const float (&v)[VPL]) {
-    float* p = M + (int64_t)rb * RB * CE + wave * (VPL * 64) + lane * 4;
-#pragma unroll
-    for (int j = 0; j < VPL / 4; ++j)
-        *(f32x4*)(p + j * 256) = f32x4{v[4 * j], v[4 * j + 1], v[4 * j + 2], v[4 * j + 3]};
-}
 
 // this wave's first fragment (hi) in a fragment-major pack of a [256 G][256] matrix, block g
 __device__ __forceinline__ const pair_t* frag_base(const void* W, int g, int wave, int lane) {
@@ -229,7 +141,7 @@ __global__ __launch_bounds__(NTC, 1) void chain_x3_kernel(cmt_chain_args a) {
     e.lh = e.lane >> 5;
     const bool has_next = a.Wn != nullptr;
     constexpr int NSUB = KIND == 0 ? 2 : KIND == 1 ? 3 : 1;
-    const int parts = KIND == 0 ? 1 : KIND == 1 ? 4 : (has_next ? 3 : 1);
+    const int parts = chain_parts(KIND, has_next);
     const int rb = blockIdx.x / parts, g = blockIdx.x - rb * parts;
     const int m0 = rb * RB;
     const int row = min(m0 + e.lr, a.rows - 1);
@@ -361,7 +273,7 @@ __global__ __launch_bounds__(NTC, 1) void chain_x3_kernel(cmt_chain_args a) {
                 h[j] = (pair_t)x;
                 l[j] = (pair_t)(x - (float)h[j]);
             }
-            const int off = r * (CE * 2) + ((ch ^ (r & 15)) << 4);
+            const int off = act_at(0, r, ch);
             *(pair8_t*)(actA + off) = h;
             *(pair8_t*)(actA + PLANE + off) = l;
         }
@@ -372,7 +284,7 @@ __global__ __launch_bounds__(NTC, 1) void chain_x3_kernel(cmt_chain_args a) {
             const int piece = tid + NTC * i;
             const int pl = piece >> 10, pc = piece & 1023;
             const int r = pc >> 5, ch = pc & 31;
-            *(f32x4*)(actA + pl * PLANE + r * (CE * 2) + ((ch ^ (r & 15)) << 4)) = xv[i];
+            *(f32x4*)act_at(actA + pl * PLANE, r, ch) = xv[i];
         }
     }
 #pragma unroll
@@ -410,11 +322,11 @@ __global__ __launch_bounds__(NTC, 1) void chain_x3_kernel(cmt_chain_args a) {
         e.sub_gemm<0>(actA, wst, acc);                                  // self-attn out_proj
         STAMP(0, 3);
         {
-            const float* bo = e.prm();
+            const float* bo = e.prm() + prm_a::bo;
 #pragma unroll
             for (int r = 0; r < VPL; ++r) v[r] = acc[r] + bo[e.col(r)] + res[r];
         }
-        e.layernorm(v, 256, 512, eps);                                  // norms[0]
+        e.layernorm(v, prm_a::ln_w, prm_a::ln_b, eps);                  // norms[0]
         STAMP(0, 4);
         float u[VPL];
 #pragma unroll
@@ -424,7 +336,7 @@ __global__ __launch_bounds__(NTC, 1) void chain_x3_kernel(cmt_chain_args a) {
         STAMP(0, 5);
         e.sub_gemm<1>(actB, wst, acc);                                  // cross-attn Q projection
         STAMP(0, 6);
-        const float* bq = e.prm() + 768;
+        const float* bq = e.prm() + prm_a::bq;
         h4 qo[4];
 #pragma unroll
         for (int gg = 0; gg < 4; ++gg) {
@@ -449,11 +361,11 @@ __global__ __launch_bounds__(NTC, 1) void chain_x3_kernel(cmt_chain_args a) {
         e.sub_gemm<0>(actA, wst, acc);                                  // cross-attn out_proj
         STAMP(1, 3);
         {
-            const float* bo = e.prm();
+            const float* bo = e.prm() + prm_b::bo;
 #pragma unroll
             for (int r = 0; r < VPL; ++r) v[r] = acc[r] + bo[e.col(r)] + res[r];
         }
-        e.layernorm(v, 256, 512, eps);                                  // norms[1] -> o (FFN residual)
+        e.layernorm(v, prm_b::ln1_w, prm_b::ln1_b, eps);                // norms[1] -> o (FFN residual)
         STAMP(1, 4);
         e.put_act(actB, v);                                             // fc1 operand
         barrier_mem();
@@ -461,7 +373,7 @@ __global__ __launch_bounds__(NTC, 1) void chain_x3_kernel(cmt_chain_args a) {
         e.sub_gemm<1>(actB, wst, acc);                                  // fc1 rows [256g, 256g + 256)
         STAMP(1, 6);
         {
-            const float* b1 = e.prm() + 768 + 256 * g;
+            const float* b1 = e.prm() + prm_b::b1 + CE * g;
             float h[VPL];
 #pragma unroll
             for (int r = 0; r < VPL; ++r) h[r] = fmaxf(acc[r] + b1[e.col(r)], 0.f);
@@ -471,7 +383,7 @@ __global__ __launch_bounds__(NTC, 1) void chain_x3_kernel(cmt_chain_args a) {
         STAMP(1, 7);
         e.sub_gemm<2>(actA, wst, acc);                                  // fc2 partial over K block g
         STAMP(1, 8);
-        const float* b2 = e.prm() + 1792;
+        const float* b2 = e.prm() + prm_b::b2;
 #pragma unroll
         for (int r = 0; r < VPL; ++r) {
             float x = acc[r];
@@ -485,13 +397,13 @@ __global__ __launch_bounds__(NTC, 1) void chain_x3_kernel(cmt_chain_args a) {
     // ---------------- chain B2: norms[2] (+ post_norm), next layer's in_proj block g
 #pragma unroll
     for (int i = 0; i < VPL; ++i) v[i] = res[i];
-    e.layernorm(v, 2048, 2304, eps);                                    // norms[2] -> next query
+    e.layernorm(v, prm_b::ln2_w, prm_b::ln2_b, eps);                    // norms[2] -> next query
     STAMP(2, 3);
     float y[VPL];
 #pragma unroll
     for (int i = 0; i < VPL; ++i) y[i] = v[i];
     if (g == 0) {
-        e.layernorm(v, 2560, 2816, eps);                                // post_norm -> layer output
+        e.layernorm(v, prm_b::post_w, prm_b::post_b, eps);              // post_norm -> layer output
 #pragma unroll
         for (int i = 0; i < VPL; ++i) {
             float x = v[i];
@@ -524,7 +436,7 @@ __global__ __launch_bounds__(NTC, 1) void chain_x3_kernel(cmt_chain_args a) {
         }
         if (has_next) {
             // head-split pairs [B][24][Nq][64]: per (plane, row) the 32 hi values, then the 32 lo
-            const float* bqkv = e.prm() + 3072 + g * CE;
+            const float* bqkv = e.prm() + prm_b::bn + g * CE;
             const int b = row / a.Nq, rr = row - b * a.Nq;
 #pragma unroll
             for (int gg = 0; gg < 4; ++gg) {
@@ -553,8 +465,7 @@ int cmt_chain_x3(const cmt_chain_args& a, hipStream_t s) {
     CMT_REQUIRE(a.xpart == nullptr || (a.kind == 1 && a.xsplits == XS && a.Nq > 0 && a.rows % a.Nq == 0 &&
                                        (uintptr_t)a.xpart % 16 == 0),
                 "cmt_chain: xpart (split partials) feeds chain B1 with xsplits == 8, rows = B * Nq, 16-byte aligned");
-    const int parts = a.kind == 0 ? 1 : a.kind == 1 ? 4 : (a.Wn ? 3 : 1);
-    const unsigned grid = (unsigned)(cdiv(a.rows, RB) * parts);
+    const unsigned grid = (unsigned)(cdiv(a.rows, RB) * chain_parts(a.kind, a.Wn != nullptr));
     if (a.kind == 0) chain_x3_kernel<0, WRING_DEFAULT><<<grid, NTC, 0, s>>>(a);
     else if (a.kind == 1 && a.xpart) chain_x3_kernel<1, WRING_DEFAULT, true><<<grid, NTC, 0, s>>>(a);
     else if (a.kind == 1) chain_x3_kernel<1, WRING_DEFAULT><<<grid, NTC, 0, s>>>(a);

@@ -539,7 +539,7 @@ class PETRTransformerDecoder(nn.Module):
             def vec(t, n):
                 return t.detach().float().reshape(-1) if t is not None else torch.zeros(n, device=dev)
 
-            A, Bk = [], []
+            A, Bk = [], []   # in the order of the kernels' named offsets (rowchain_common.h prm_a / prm_b)
             for l, lay in enumerate(self.layers):
                 sa, ca, ffn, nm = lay.attentions[0].attn, lay.attentions[1].attn, lay.ffns[0], lay.norms
                 cbq = ca.in_proj_bias[:C] if ca.in_proj_bias is not None else None
@@ -751,26 +751,14 @@ class PETRTransformerDecoder(nn.Module):
 
     def lowp_layer0(self, st, qpos, *, B, Nq, prec, first_ops_ready=False):
         """Layer 0 up to the cross-attention core: the zero target's operands
-        (add_cast), the self-attention in_proj and core, out_proj + norms[0]
-        and the cross-attention Q projection (chain A on the chain path).  None
+        (add_cast) and layer 0's self block (_self_block) with no residual.  None
         of it reads the memory side, so the head runs it on a second stream
         beside shared_conv / the encodings / the K/V projection (the stream it
         runs on is recorded and joined before the first cross-attention)."""
         prec = get_precision(prec)
-        pk = self.packed(prec)
-        C, H, rows = self.embed_dims, self.embed_dims // 32, B * Nq
-        l0 = pk["layers"][0]
         if not first_ops_ready:   # else written by the query embedding's last kernel (masked_view_sum_ex)
-            native.add_cast(None, rows=rows, C=C, Yl=st["tl"], Yp=st["tp"], P=qpos)
-        native.gemm(st["tl"], l0["sa_w"], st["qkv"], M=rows, N=3 * C, K=C, lda=C, ldw=C, ldc=0, bias=l0["sa_b"],
-                    A2=st["tp"], lda2=C, a2_cols=2 * C, headsplit_rows=Nq)
-        self._self_attn(st, B=B, H=H, Nq=Nq, C=C)
-        if st["chain"]:
-            ch = self._chain_pack(prec)
-            native.chain(0, st["ob"], qpos, ch["A"][0], _wo(l0), l0["ca_wqp"], st["t1n"], rows=rows, Nq=Nq,
-                         eps=self.post_norm.eps, R=None, Q=st["qc"])
-        else:
-            self._self_out_q(st, l0, qpos, None, rows=rows, Nq=Nq, C=C)   # layer 0: zero residual
+            native.add_cast(None, rows=B * Nq, C=self.embed_dims, Yl=st["tl"], Yp=st["tp"], P=qpos)
+        self._self_block(st, 0, qpos, None, B=B, Nq=Nq, prec=prec)   # layer 0: zero residual
         st["layer0_done"] = True
         st["stream"] = torch.cuda.current_stream()
 
@@ -845,22 +833,19 @@ class PETRTransformerDecoder(nn.Module):
         (zero target, tgt0 None): buffers from lowp_state whose layer 0 up to
         the cross-attention core may already be queued (lowp_layer0)."""
         pk = self.packed(prec)
-        L, C, H = self.num_layers, self.embed_dims, self.embed_dims // 32
-        lp = prec.gemm
+        L, C = self.num_layers, self.embed_dims
         dev = qpos.device
-        f32 = torch.float32
         rows = B * Nq
         if out is None:
-            out = torch.empty((L, rows, C), dtype=f32, device=dev)
+            out = torch.empty((L, rows, C), dtype=torch.float32, device=dev)
         if kv_operands is None:
-            memb = op_empty(B * Nk, C, lp, dev)
+            memb = op_empty(B * Nk, C, prec.gemm, dev)
             mposb = torch.empty_like(memb)
             native.add_cast(mem, rows=B * Nk, C=C, Yl=memb, Yp=mposb, P=pos)
         else:
             memb, mposb = kv_operands
         # K columns read lowp(mem + pos), V columns lowp(mem)
         kv, kvl = self._project_kv(pk, memb, mposb, B=B, Nk=Nk, prec=prec)
-        use_chain = self._use_chain(prec)
         if tgt0 is None:
             # target = zeros_like(query_embed) in every CMT transformer (cmt_transformer.py:114):
             # layer 0's residual is None and its first operands come from add_cast's zeros
@@ -869,82 +854,90 @@ class PETRTransformerDecoder(nn.Module):
                 self.lowp_layer0(st, qpos, B=B, Nq=Nq, prec=prec)
             elif st["stream"] is not None and st["stream"] != torch.cuda.current_stream():
                 torch.cuda.current_stream().wait_stream(st["stream"])   # join the layer-0 side stream
-            if use_chain:
-                return self._chain_layers(st, qpos, kv, kvl, B=B, Nk=Nk, Nq=Nq, out=out, post_flags=post_flags,
-                                          prec=prec, out16=out16)
-            return self._sep_layers(st, qpos, kv, kvl, B=B, Nk=Nk, Nq=Nq, out=out, post_flags=post_flags,
-                                    prec=prec, out16=out16, l0_done=True)
-        if state is not None:
-            raise ValueError("run_rows: a lowp_state applies to a zero target only")
-        st = self.lowp_state(B=B, Nk=Nk, Nq=Nq, prec=prec, device=dev)
-        tgt = st["tgt"]
-        tgt.copy_(tgt0)
-        native.add_cast(tgt, rows=rows, C=C, Yl=st["tl"], Yp=st["tp"], P=qpos)
-        if use_chain:
-            # per layer: self-attn core, chain A (out_proj + norms[0] + cross Q proj),
-            # cross-attn core, chain B1 (out_proj + norms[1] + FFN quarter -> fp32 partials),
-            # chain B2 (partials -> norms[2] + post_norm + next layer's in_proj) -- see rowchain.hip
-            ch = self._chain_pack(prec)
-            eps = self.post_norm.eps
-            l0 = pk["layers"][0]
-            native.gemm(st["tl"], l0["sa_w"], st["qkv"], M=rows, N=3 * C, K=C, lda=C, ldw=C, ldc=0,
-                        bias=l0["sa_b"], A2=st["tp"], lda2=C, a2_cols=2 * C, headsplit_rows=Nq)
-            for l, lw in enumerate(pk["layers"]):
-                self._self_attn(st, B=B, H=H, Nq=Nq, C=C)
-                native.chain(0, st["ob"], qpos, ch["A"][l], lw["sa_ow"], lw["ca_wqp"], st["t1n"], rows=rows, Nq=Nq,
-                             eps=eps, R=tgt, Q=st["qc"])
-                xs = self._cross_attn(st["qc"], kv, kvl[l], st["ob"], B=B, Nq=Nq, Nk=Nk, ws=st["ws"], prec=prec,
-                                      keep=self._keep_partials(prec))
-                nxt = pk["layers"][l + 1]["sa_wp"] if l + 1 < L else None
-                native.chain(1, st["ob"], None, ch["B"][l], *_b1w(lw), tgt, rows=rows, Nq=Nq, eps=eps,
-                             R=st["t1n"], W2=lw["f2_wp"], WS=st["cws"], **self._xpart(st["ws"], xs, prec))
-                native.chain(2, None, qpos if nxt is not None else None, ch["B"][l], None, None, tgt, rows=rows,
-                             Nq=Nq, eps=eps, Wn=nxt, OUT=out, out_offset=l * rows * C, out_flags=post_flags,
-                             Q=st["qkv"] if nxt is not None else None, WS=st["cws"], OUT16=out16)
-            return out
-        return self._sep_layers(st, qpos, kv, kvl, B=B, Nk=Nk, Nq=Nq, out=out, post_flags=post_flags, prec=prec,
-                                out16=out16, l0_done=False)
+            r0 = None
+        else:
+            if state is not None:
+                raise ValueError("run_rows: a lowp_state applies to a zero target only")
+            st = self.lowp_state(B=B, Nk=Nk, Nq=Nq, prec=prec, device=dev)
+            r0 = st["tgt"]
+            r0.copy_(tgt0)
+            native.add_cast(r0, rows=rows, C=C, Yl=st["tl"], Yp=st["tp"], P=qpos)
+        return self._layers(st, qpos, kv, kvl, r0, B=B, Nk=Nk, Nq=Nq, out=out, post_flags=post_flags, prec=prec,
+                            out16=out16)
 
-    def _sep_layers(self, st, qpos, kv, kvl, *, B, Nk, Nq, out, post_flags, prec, out16, l0_done):
-        """Separate-launch decoder layers (the split policy, or CMT_CHAIN=0).
-        ``l0_done``: layer 0 up to its cross-attention core already queued
-        (lowp_layer0, zero target)."""
-        pk = self.packed(prec)
-        L, C, H = self.num_layers, self.embed_dims, self.embed_dims // 32
-        rows = B * Nq
-        lp = prec.gemm
-        tgt, tl, tp, qkv, ob, t1n, hf, t1, o, ws, ksp = (st[k] for k in ("tgt", "tl", "tp", "qkv", "ob", "t1n", "hf",
-                                                                         "t1", "o", "ws", "ksp"))
-        FF = hf.shape[-1]
-        pw, pb, _pe = pk["post"]
-        for l, lw in enumerate(pk["layers"]):
-            if l > 0 or not l0_done:
-                # --- self attention: Q|K columns read lowp(tgt + qpos), V columns lowp(tgt)
-                native.gemm(tl, lw["sa_w"], qkv, M=rows, N=3 * C, K=C, lda=C, ldw=C, ldc=0, bias=lw["sa_b"],
-                            A2=tp, lda2=C, a2_cols=2 * C, headsplit_rows=Nq)
-                self._self_attn(st, B=B, H=H, Nq=Nq, C=C)
-                self._self_out_q(st, lw, qpos, tgt, rows=rows, Nq=Nq, C=C)
-            # --- cross attention: q = lowp(x + qpos); K/V from _project_kv
-            self._cross_attn(st["qc"], kv, kvl[l], ob, B=B, Nq=Nq, Nk=Nk, ws=ws, prec=prec)
-            w1, b1, e1 = lw["norms"][1]
-            native.gemm(ob, lw["ca_ow"], t1, M=rows, N=C, K=C, lda=C, ldw=C, ldc=C, bias=lw["ca_ob"], R=t1n,
-                        ldr=C, k_splits=ksp)
-            native.layernorm_ex(t1, w1, b1, rows=rows, C=C, ldx=C, eps=e1, Y=o, ldy=C, Yl=tl, nparts=ksp)
-            # --- FFN (fc1 activation written in the compute dtype)
-            native.gemm(tl, lw["f1_w"], hf, M=rows, N=FF, K=C, lda=C, ldw=C, ldc=FF, bias=lw["f1_b"], relu=True)
-            # --- fc2 + residual + norms.2 -> next query (fp32 + both lowp operands), + post_norm -> out[l]
-            w2, b2, e2 = lw["norms"][2]
-            native.gemm(hf, lw["f2_w"], t1, M=rows, N=C, K=FF, lda=FF, ldw=FF, ldc=C, bias=lw["f2_b"], R=o,
-                        ldr=C, k_splits=ksp)
-            native.layernorm_ex(t1, w2, b2, rows=rows, C=C, ldx=C, eps=e2, Y=tgt, ldy=C, Yl=tl, Yp=tp, P=qpos,
-                                W2=pw, B2=pb, Y2=out, ldy2=C, flags2=post_flags, y2_offset=l * rows * C,
-                                nparts=ksp)
-        if out16 is not None:
-            if lp == SPLIT:
-                native.split_rows(out.view(-1, C), out16.view(-1, 2, C))
+    def _layers(self, st, qpos, kv, kvl, r0, *, B, Nk, Nq, out, post_flags, prec, out16):
+        """The layer walk of both lowp paths (row-block chains, or separate
+        launches: CMT_CHAIN=0 / shapes the chains do not take): per layer the
+        self block, then the cross block.  ``r0``: layer 0's residual (None: the
+        zero target, whose self block lowp_layer0 may already have queued)."""
+        for l in range(self.num_layers):
+            if l > 0 or not st["layer0_done"]:
+                self._self_block(st, l, qpos, r0 if l == 0 else st["tgt"], B=B, Nq=Nq, prec=prec)
+            self._cross_block(st, l, qpos, kv, kvl[l], B=B, Nk=Nk, Nq=Nq, out=out, post_flags=post_flags, prec=prec,
+                              out16=out16)
+        if out16 is not None and not st["chain"]:   # chain B2 writes out16 itself
+            if prec.gemm == SPLIT:
+                native.split_rows(out.view(-1, self.embed_dims), out16.view(-1, 2, self.embed_dims))
             else:
                 native.cast(out, out16)
         return out
+
+    def _self_block(self, st, l, qpos, R, *, B, Nq, prec):
+        """Self block of layer l: in_proj (Q|K columns read lowp(tgt + qpos), V
+        columns lowp(tgt)), the self-attention core, then out_proj + residual R
+        (None = zero target) + norms[0] -> t1n and the cross-attention Q
+        projection of lowp(t1n + qpos) -> qc: chain A, or _self_out_q."""
+        lw = self.packed(prec)["layers"][l]
+        C, H, rows = self.embed_dims, self.embed_dims // 32, B * Nq
+        if l == 0 or not st["chain"]:   # chain B2 writes the later layers' qkv
+            native.gemm(st["tl"], lw["sa_w"], st["qkv"], M=rows, N=3 * C, K=C, lda=C, ldw=C, ldc=0, bias=lw["sa_b"],
+                        A2=st["tp"], lda2=C, a2_cols=2 * C, headsplit_rows=Nq)
+        self._self_attn(st, B=B, H=H, Nq=Nq, C=C)
+        if st["chain"]:
+            native.chain(0, st["ob"], qpos, self._chain_pack(prec)["A"][l], _wo(lw), lw["ca_wqp"], st["t1n"],
+                         rows=rows, Nq=Nq, eps=self.post_norm.eps, R=R, Q=st["qc"])
+        else:
+            self._self_out_q(st, lw, qpos, R, rows=rows, Nq=Nq, C=C)
+
+    def _cross_block(self, st, l, qpos, kv, ent, *, B, Nk, Nq, out, post_flags, prec, out16):
+        """Cross block of layer l: the cross-attention core (q = qc; K/V from
+        _project_kv), out_proj + t1n + norms[1], the FFN + norms[2] -> tgt (the
+        next query) and post_norm -> out[l].  Chain path: chain B1 (out_proj +
+        norms[1] + one FFN quarter per workgroup -> fp32 partials), chain B2
+        (partials -> norms[2] + post_norm + the next layer's in_proj) -- see
+        rowchain.hip; else the separate GEMM / layernorm_ex launches."""
+        pk = self.packed(prec)
+        lw = pk["layers"][l]
+        L, C, rows = self.num_layers, self.embed_dims, B * Nq
+        tgt, ob, t1n, ws = st["tgt"], st["ob"], st["t1n"], st["ws"]
+        if st["chain"]:
+            xs = self._cross_attn(st["qc"], kv, ent, ob, B=B, Nq=Nq, Nk=Nk, ws=ws, prec=prec,
+                                  keep=self._keep_partials(prec))
+            prm, eps = self._chain_pack(prec)["B"][l], self.post_norm.eps
+            nxt = pk["layers"][l + 1]["sa_wp"] if l + 1 < L else None
+            native.chain(1, ob, None, prm, *_b1w(lw), tgt, rows=rows, Nq=Nq, eps=eps,
+                         R=t1n, W2=lw["f2_wp"], WS=st["cws"], **self._xpart(ws, xs, prec))
+            native.chain(2, None, qpos if nxt is not None else None, prm, None, None, tgt, rows=rows,
+                         Nq=Nq, eps=eps, Wn=nxt, OUT=out, out_offset=l * rows * C, out_flags=post_flags,
+                         Q=st["qkv"] if nxt is not None else None, WS=st["cws"], OUT16=out16)
+            return
+        tl, tp, hf, t1, o, ksp = (st[k] for k in ("tl", "tp", "hf", "t1", "o", "ksp"))
+        FF = hf.shape[-1]
+        self._cross_attn(st["qc"], kv, ent, ob, B=B, Nq=Nq, Nk=Nk, ws=ws, prec=prec)
+        w1, b1, e1 = lw["norms"][1]
+        native.gemm(ob, lw["ca_ow"], t1, M=rows, N=C, K=C, lda=C, ldw=C, ldc=C, bias=lw["ca_ob"], R=t1n,
+                    ldr=C, k_splits=ksp)
+        native.layernorm_ex(t1, w1, b1, rows=rows, C=C, ldx=C, eps=e1, Y=o, ldy=C, Yl=tl, nparts=ksp)
+        # --- FFN (fc1 activation written in the compute dtype)
+        native.gemm(tl, lw["f1_w"], hf, M=rows, N=FF, K=C, lda=C, ldw=C, ldc=FF, bias=lw["f1_b"], relu=True)
+        # --- fc2 + residual + norms.2 -> next query (fp32 + both lowp operands), + post_norm -> out[l]
+        w2, b2, e2 = lw["norms"][2]
+        pw, pb, _pe = pk["post"]
+        native.gemm(hf, lw["f2_w"], t1, M=rows, N=C, K=FF, lda=FF, ldw=FF, ldc=C, bias=lw["f2_b"], R=o,
+                    ldr=C, k_splits=ksp)
+        native.layernorm_ex(t1, w2, b2, rows=rows, C=C, ldx=C, eps=e2, Y=tgt, ldy=C, Yl=tl, Yp=tp, P=qpos,
+                            W2=pw, B2=pb, Y2=out, ldy2=C, flags2=post_flags, y2_offset=l * rows * C,
+                            nparts=ksp)
 
     @staticmethod
     def _keep_partials(prec):
@@ -957,29 +950,3 @@ class PETRTransformerDecoder(nn.Module):
         if not kept:
             return {}
         return dict(xpart=ws.view(torch.float32), xsplits=kept, xround=prec.round_cross_out)
-
-    def _chain_layers(self, st, qpos, kv, kvl, *, B, Nk, Nq, out, post_flags, prec, out16):
-        """Chain path from layer 0's cross-attention core on (layer 0's self
-        block already queued by lowp_layer0): per layer the cross-attention
-        core, chain B1, chain B2 (which also runs the next layer's in_proj),
-        then the next layer's self-attention core and chain A."""
-        pk = self.packed(prec)
-        ch = self._chain_pack(prec)
-        L, C, H = self.num_layers, self.embed_dims, self.embed_dims // 32
-        rows = B * Nq
-        eps = self.post_norm.eps
-        tgt, qkv, qc, ob, t1n, ws, cws = (st[k] for k in ("tgt", "qkv", "qc", "ob", "t1n", "ws", "cws"))
-        for l, lw in enumerate(pk["layers"]):
-            if l > 0:
-                self._self_attn(st, B=B, H=H, Nq=Nq, C=C)
-                native.chain(0, ob, qpos, ch["A"][l], _wo(lw), lw["ca_wqp"], t1n, rows=rows, Nq=Nq, eps=eps,
-                             R=tgt, Q=qc)
-            xs = self._cross_attn(qc, kv, kvl[l], ob, B=B, Nq=Nq, Nk=Nk, ws=ws, prec=prec,
-                                  keep=self._keep_partials(prec))
-            nxt = pk["layers"][l + 1]["sa_wp"] if l + 1 < L else None
-            native.chain(1, ob, None, ch["B"][l], *_b1w(lw), tgt, rows=rows, Nq=Nq, eps=eps,
-                         R=t1n, W2=lw["f2_wp"], WS=cws, **self._xpart(ws, xs, prec))
-            native.chain(2, None, qpos if nxt is not None else None, ch["B"][l], None, None, tgt, rows=rows,
-                         Nq=Nq, eps=eps, Wn=nxt, OUT=out, out_offset=l * rows * C, out_flags=post_flags,
-                         Q=qkv if nxt is not None else None, WS=cws, OUT16=out16)
-        return out

@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 import torch
 
+from test_gpu_split import SPLIT, _pair, _same, _unpair
+
 pytestmark = pytest.mark.gpu
 
 
@@ -622,33 +624,55 @@ def _ln64(x, w, b, eps=1e-5):
     return (x - m) / torch.sqrt(v + eps) * w + b
 
 
-@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
+def _chain_fmt(dt):
+    """A chain operand format: (op, val) -- op(x) is the tensor handed to the kernel for the
+    values x (f16 / bf16 rows, or the 'ref' policy's f16 pair rows), val(o) the float64 values
+    that operand holds."""
+    if dt == SPLIT:
+        return _pair, _unpair
+    return (lambda x: x.to(dt)), (lambda o: o.double())
+
+
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16, SPLIT])
 @pytest.mark.parametrize("B,Nq,with_r", [(1, 900, True), (2, 37, False)])
 def test_chain_a(N, dev, dt, B, Nq, with_r):
     """Row-block chain A (out_proj + bias + residual -> norms[0] -> lowp(y + pos)
     -> cross-attn Q projection, head split) vs fp64 math on the same rounded
-    operands; ragged last row block, no-residual (layer 0) form."""
+    operands; ragged last row block, no-residual (layer 0) form.  SPLIT: the
+    split chains (rowchain_x3.hip) on f16 pairs -- Y to cmt_gemm_ln's pair bound
+    (test_gemm_ln_split), the f16 Q to one f16 ulp of its scale."""
+    split = dt == SPLIT
+    op, val = _chain_fmt(dt)
     g = torch.Generator().manual_seed(B * 100 + Nq)
     C, rows = 256, B * Nq
-    X = torch.randn(rows, C, generator=g).to(dt)
+    X = op(torch.randn(rows, C, generator=g))
     R = torch.randn(rows, C, generator=g) if with_r else None
     P = torch.randn(rows, C, generator=g)
-    Wo = (torch.randn(C, C, generator=g) / 16).to(dt)
-    Wq = (torch.randn(C, C, generator=g) / 16).to(dt)
+    Wo = op(torch.randn(C, C, generator=g) / 16)
+    Wq = op(torch.randn(C, C, generator=g) / 16)
     bo, lb, bq = (torch.randn(C, generator=g) * 0.1 for _ in range(3))
     lw = 1 + 0.1 * torch.randn(C, generator=g)
     prm = torch.cat([bo, lw, lb, bq])
     Y = torch.empty(rows, C, device=dev)
-    Q = torch.empty(B * 8 * Nq * 32, dtype=dt, device=dev)
-    N.chain(0, X.to(dev), P.to(dev), prm.to(dev), Wo.to(dev), N.pack_chain_wn(Wq.to(dev)), Y, rows=rows, Nq=Nq, eps=1e-5,
-            R=R.to(dev) if R is not None else None, Q=Q)
+    Q = torch.empty(B * 8 * Nq * 32, dtype=torch.float16 if split else dt, device=dev)
+    pack = N.pack_chain_pair if split else N.pack_chain_wn
+    N.chain(0, X.to(dev), P.to(dev), prm.to(dev), pack(Wo.to(dev)) if split else Wo.to(dev), pack(Wq.to(dev)), Y,
+            rows=rows, Nq=Nq, eps=1e-5, R=R.to(dev) if R is not None else None, Q=Q)
     d = lambda t: t.double()
-    t = d(X) @ d(Wo).T + d(bo) + (d(R) if R is not None else 0)
+    t = val(X) @ val(Wo).T + d(bo) + (d(R) if R is not None else 0)
     y = _ln64(t, d(lw), d(lb))
-    q = d((y + d(P)).to(dt)) @ d(Wq).T + d(bq)
+    q = val(op(y + d(P))) @ val(Wq).T + d(bq)
     qref = q.view(B, Nq, 8, 32).permute(0, 2, 1, 3).reshape(-1)
-    assert (Y.cpu().double() - y).abs().max().item() < 2e-3
-    rel = (Q.cpu().double() - qref).abs().max().item() / qref.abs().max().item()
+    ey = (Y.cpu().double() - y).abs().max().item()
+    eq = (Q.cpu().double() - qref).abs().max().item()
+    if split:
+        print(f"split chain A ({B} x {Nq}): Y err {ey:.2e} (bound {2e-5 * y.abs().max().item():.2e}), "
+              f"Q err {eq:.2e} (bound {2 ** -10 * qref.abs().max().item():.2e})")
+        assert ey <= 2e-5 * y.abs().max().item(), ey
+        assert eq <= 2 ** -10 * qref.abs().max().item(), eq
+        return   # the split chains have the fragment-major (register) form only
+    assert ey < 2e-3
+    rel = eq / qref.abs().max().item()
     assert rel < 1.5e-2, rel
     # fragment-major Wo (wo_frag: register-streamed out_proj, no LDS weight ring): the same
     # MFMA k-order, so bit-identical outputs
@@ -659,22 +683,28 @@ def test_chain_a(N, dev, dt, B, Nq, with_r):
     assert torch.equal(Y, Y2) and torch.equal(Q, Q2)
 
 
-@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16, SPLIT])
 @pytest.mark.parametrize("B,Nq,last,flags", [(1, 900, False, 1), (2, 37, True, 3)])
 def test_chain_b(N, dev, dt, B, Nq, last, flags):
     """Row-block chains B1 (out_proj + residual -> norms[1] -> one FFN quarter per
     workgroup -> fp32 partials) and B2 (partials -> norms[2] and post_norm
     (nan_to_num / coop max-into) -> next in_proj, head split) vs fp64 math on the
-    same rounded operands."""
+    same rounded operands.  SPLIT: the split chains (rowchain_x3.hip) on f16
+    pairs.  No other test bounds three pair GEMMs and three LayerNorms in a row,
+    so the bound is measured: the same formula in float32 torch on the CPU (the
+    reference's arithmetic) against float64, times 4 for another summation order,
+    and never below cmt_gemm_ln's 2e-5 of the scale; both errors are printed."""
+    split = dt == SPLIT
+    op, val = _chain_fmt(dt)
     g = torch.Generator().manual_seed(B * 1000 + Nq)
     C, F, rows = 256, 1024, B * Nq
-    X = torch.randn(rows, C, generator=g).to(dt)
+    X = op(torch.randn(rows, C, generator=g))
     R = torch.randn(rows, C, generator=g)
     P = torch.randn(rows, C, generator=g)
-    Wo = (torch.randn(C, C, generator=g) / 16).to(dt)
-    W1 = (torch.randn(F, C, generator=g) / 16).to(dt)
-    W2 = (torch.randn(C, F, generator=g) / 32).to(dt)
-    Wn = (torch.randn(3 * C, C, generator=g) / 16).to(dt)
+    Wo = op(torch.randn(C, C, generator=g) / 16)
+    W1 = op(torch.randn(F, C, generator=g) / 16)
+    W2 = op(torch.randn(C, F, generator=g) / 32)
+    Wn = op(torch.randn(3 * C, C, generator=g) / 16)
     v = lambda n, s=0.1: torch.randn(n, generator=g) * s
     bo, b1, b2, bn = v(C), v(F), v(C), v(3 * C)
     l1w, l2w, pw = (1 + v(C) for _ in range(3))
@@ -683,30 +713,58 @@ def test_chain_b(N, dev, dt, B, Nq, last, flags):
     Y = torch.empty(rows, C, device=dev)
     old = torch.randn(rows, C, generator=g)
     OUT = old.clone().to(dev)
-    OUT16 = torch.full(OUT.shape, float("nan"), dtype=dt, device=dev)
-    QKV = torch.empty(B * 24 * Nq * 32, dtype=dt, device=dev)
+    sps = 2 if split else 1   # 16-bit words per value
+    OUT16 = torch.full((rows, sps, C), float("nan"), dtype=torch.float16 if split else dt, device=dev).view(dt)
+    QKV = torch.empty(B * 24 * Nq * 32 * sps, dtype=dt, device=dev)
     WS = torch.full((N.chain_ws_numel(rows),), float("nan"), device=dev)
     prm_d = prm.to(dev)
-    N.chain(1, X.to(dev), None, prm_d, Wo.to(dev), W1.to(dev), Y, rows=rows, Nq=Nq, eps=1e-5,
-            R=R.to(dev), W2=N.pack_chain_fc2(W2.to(dev)), WS=WS)
+    wn, fc2 = (N.pack_chain_pair, N.pack_chain_fc2_pair) if split else (N.pack_chain_wn, N.pack_chain_fc2)
+    N.chain(1, X.to(dev), None, prm_d, wn(Wo.to(dev)) if split else Wo.to(dev),
+            wn(W1.to(dev)) if split else W1.to(dev), Y, rows=rows, Nq=Nq, eps=1e-5,
+            R=R.to(dev), W2=fc2(W2.to(dev)), WS=WS)
     N.chain(2, None, None if last else P.to(dev), prm_d, None, None, Y, rows=rows, Nq=Nq, eps=1e-5,
-            Wn=None if last else N.pack_chain_wn(Wn.to(dev)), OUT=OUT, out_flags=flags, Q=None if last else QKV, WS=WS,
+            Wn=None if last else wn(Wn.to(dev)), OUT=OUT, out_flags=flags, Q=None if last else QKV, WS=WS,
             OUT16=OUT16)
-    d = lambda t: t.double()
-    o = _ln64(d(X) @ d(Wo).T + d(bo) + d(R), d(l1w), d(l1b))
-    h = torch.relu(d(o.to(dt)) @ d(W1).T + d(b1)).to(dt)
-    y = _ln64(d(h) @ d(W2).T + d(b2) + o, d(l2w), d(l2b))
-    out = _ln64(y, d(pw), d(pb))
-    if flags & 2:
-        out = torch.maximum(out, d(old))
-    assert (Y.cpu().double() - y).abs().max().item() < 2e-2
-    assert (OUT.cpu().double() - out).abs().max().item() < 2e-2
-    assert torch.equal(OUT16, OUT.to(dt))      # the 16-bit copy is the rounded fp32 output
+
+    def ref(fdt):
+        """The chains' formula in fdt arithmetic on the values the operands hold -> y, out, qkv."""
+        d = lambda t: t.to(fdt)
+        hv = lambda x: d(val(op(x)))   # a GEMM operand produced inside the chain
+        o = _ln64(d(val(X)) @ d(val(Wo)).T + d(bo) + d(R), d(l1w), d(l1b))
+        h = torch.relu(hv(o) @ d(val(W1)).T + d(b1))
+        y = _ln64(hv(h) @ d(val(W2)).T + d(b2) + o, d(l2w), d(l2b))
+        out = _ln64(y, d(pw), d(pb))
+        if flags & 2:
+            out = torch.maximum(out, d(old))
+        if last:
+            return y, out, None
+        wnv = d(val(Wn))
+        qk = hv(y + d(P)) @ wnv[:2 * C].T + d(bn[:2 * C])
+        vv = hv(y) @ wnv[2 * C:].T + d(bn[2 * C:])
+        return y, out, torch.cat([qk, vv], 1).view(B, Nq, 24, 32).permute(0, 2, 1, 3).reshape(-1)
+
+    y, out, qkv = ref(torch.float64)
+    err = lambda a, b: (a.double() - b).abs().max().item()
+    if split:
+        y32, out32, qkv32 = ref(torch.float32)
+        got = QKV.cpu().view(torch.float16).view(-1, 2, 32).double().sum(1).reshape(-1) if not last else None
+        for name, a, r, r32, extra in (("Y", Y.cpu(), y, y32, 0.0), ("OUT", OUT.cpu(), out, out32, 0.0),
+                                       ("QKV", got, qkv, qkv32, 2 ** -21)):   # + the pair output's own precision
+            if r is None:
+                continue
+            scale = r.abs().max().item()
+            e, e32 = err(a, r), err(r32, r)
+            bound = max(4 * e32, 2e-5 * scale) + extra * scale
+            print(f"split chain B ({B} x {Nq}) {name}: kernel err {e:.2e}, float32 torch err {e32:.2e}, "
+                  f"bound {bound:.2e}")
+            assert e <= bound, (name, e, e32, bound)
+        assert _same(OUT16, _pair(OUT.cpu()))   # the pair copy is the split of the fp32 output
+        return
+    assert err(Y.cpu(), y) < 2e-2
+    assert err(OUT.cpu(), out) < 2e-2
+    assert torch.equal(OUT16.view(rows, C), OUT.to(dt))      # the 16-bit copy is the rounded fp32 output
     if not last:
-        qk = d((y + d(P)).to(dt)) @ d(Wn[:2 * C]).T + d(bn[:2 * C])
-        vv = d(y.to(dt)) @ d(Wn[2 * C:]).T + d(bn[2 * C:])
-        ref = torch.cat([qk, vv], 1).view(B, Nq, 24, 32).permute(0, 2, 1, 3).reshape(-1)
-        rel = (QKV.cpu().double() - ref).abs().max().item() / ref.abs().max().item()
+        rel = err(QKV.cpu(), qkv) / qkv.abs().max().item()
         assert rel < 2e-2, rel
 
 
