@@ -17,7 +17,9 @@ backward); the glue here is index/reshape work on [B, Nq]-sized tensors,
 residual adds, ReLU, dropout masks and the sin/cos / camera geometry of the
 query embedding (a few thousand elements), all on the device.  The Hungarian
 assignment copies the [Nq, n_gt] cost matrix to the host and runs scipy's
-linear_sum_assignment, exactly as the reference does.
+linear_sum_assignment, exactly as the reference does; with
+runtime.OPTIONS.device_assign (off by default) it is solved on the device by
+cmt_lsap instead and the loss needs nothing from the host.
 """
 import math
 
@@ -41,6 +43,15 @@ def _to_dev_async(t, dev):
     if t.device.type != "cpu" or torch.device(dev).type == "cpu":
         return t.to(dev)
     return t.pin_memory().to(dev, non_blocking=True)
+
+
+class _DeviceMatches:
+    """What _assign_all_device hands to _targets_all_device: match_g [P + 1, max Nq] (cmt_lsap's
+    gather form; row P all -1), per task the match row and the GT offset of every (layer, sample)
+    [tasks, L * B] on the device, and the host-known number of matches per job."""
+
+    def __init__(self, match_g, sel, goff, count):
+        self.match_g, self.sel, self.goff, self.count = match_g, sel, goff, count
 
 
 class _DecoderStep(torch.nn.Module):
@@ -428,15 +439,10 @@ class HeadTrainMixin:
             flag += ncls
         return out
 
-    def _assign_all(self, preds, gts, cfg, code_w, between=None):
-        """HungarianAssigner3D (hungarian_assigner_3d.py:68-156) for every
-        (layer, task, sample): the [Nq, n_gt] cost matrices are built on the
-        device (cmt_match_cost, each sample's normalised GT built once for all
-        layers), copied to the host in ONE non-blocking transfer and solved by
-        scipy's linear_sum_assignment as the reference does; ``between()`` (host
-        work that does not need the matches) runs while that copy waits for the
-        forward's kernels.  Returns {(l, t, b): (rows, cols) host int64 arrays}
-        (absent: no GT)."""
+    def _match_costs(self, preds, gts, cfg, code_w):
+        """The [Nq, n_gt] cost matrix of every (layer, task, sample) with GT, built on the device
+        (cmt_match_cost, each sample's normalised GT built once for all layers): (jobs = [((l, t,
+        b), shape)], the flattened matrices in job order)."""
         L, B = preds[0]["center"].shape[:2]
         jobs, costs = [], []
         gnorm = {key: (_normalize_bbox(g).contiguous(), gl.int().contiguous())
@@ -455,6 +461,23 @@ class HeadTrainMixin:
                                         reg_weight=cfg["match_reg_weight"])
                     jobs.append(((l, t, b), cost.shape))
                     costs.append(cost.reshape(-1))
+        return jobs, costs
+
+    def _assign_all(self, preds, gts, cfg, code_w, between=None):
+        """HungarianAssigner3D (hungarian_assigner_3d.py:68-156) for every
+        (layer, task, sample): the [Nq, n_gt] cost matrices are built on the
+        device (_match_costs), copied to the host in ONE non-blocking transfer
+        and solved by scipy's linear_sum_assignment as the reference does;
+        ``between()`` (host work that does not need the matches) runs while that
+        copy waits for the forward's kernels.  Returns {(l, t, b): (rows, cols)
+        host int64 arrays} (absent: no GT).  With OPTIONS.device_assign the
+        matrices stay on the device (_assign_all_device)."""
+        jobs, costs = self._match_costs(preds, gts, cfg, code_w)
+        if OPTIONS.device_assign:
+            self.assign_status = None                          # nothing assigned on the device (yet)
+        if OPTIONS.device_assign and jobs and costs[0].is_cuda:
+            L, B = preds[0]["center"].shape[:2]
+            return self._assign_all_device(jobs, costs, gts, L, B, len(preds), between)
         out = {}
         if not jobs:
             if between is not None:
@@ -517,6 +540,68 @@ class HeadTrainMixin:
             bw.index_fill_(0, idx[0], 1.0)   # (an index_put of a Python scalar copies it to the device: a sync)
         return labels, tgt, bw, npos
 
+    def _assign_all_device(self, jobs, costs, gts, L, B, ntask, between=None):
+        """_assign_all with OPTIONS.device_assign: every job's matrix solved by ONE cmt_lsap call
+        (native_train.lsap) on the device.  What the host knows -- the jobs' shapes and offsets,
+        which match row belongs to which (layer, sample) of a task, each sample's offset into its
+        task's GT -- goes up as one pinned non-blocking block; the host waits for nothing and no
+        match comes back.  status, OR-reduced to one device int, is kept as ``assign_status``
+        (Trainer.step reads it).  Returns _DeviceMatches for _targets_all_device."""
+        dev = costs[0].device
+        P = len(jobs)
+        desc = np.empty((P, 4), dtype=np.int64)
+        sel = np.full((ntask, L * B), P, dtype=np.int64)      # P: the all -1 row appended below (no GT)
+        goff = np.zeros((ntask, L * B), dtype=np.int64)
+        count, off = {}, 0
+        for p, ((l, t, b), shape) in enumerate(jobs):
+            desc[p] = (off, shape[0], shape[1], shape[1])
+            off += shape[0] * shape[1]
+            sel[t, l * B + b] = p
+            goff[t, l * B + b] = sum(gts[(t, bb)][0].shape[0] for bb in range(b))
+            count[(l, t, b)] = min(shape)                     # finite costs: the smaller side is fully matched
+        max_nq, max_ngt = max(s[0] for _, s in jobs), max(s[1] for _, s in jobs)
+        block = _to_dev_async(torch.from_numpy(np.concatenate([desc.reshape(-1), sel.reshape(-1), goff.reshape(-1)])),
+                              dev)
+        n = ntask * L * B
+        _, match_g, status = T.lsap(torch.cat(costs), block[:4 * P].view(P, 4), max_nq=max_nq, max_ngt=max_ngt)
+        if between is not None:
+            between()
+        self.assign_status = (status != 0).any().to(torch.int32)
+        if not torch.cuda.is_current_stream_capturing():
+            # its host copy starts now (pinned, non-blocking, with an event): Trainer.step waits for
+            # that event only -- the forward's kernels, not the backward it has queued by then
+            host = torch.empty(1, dtype=torch.int32, pin_memory=True)
+            host.copy_(self.assign_status.reshape(1), non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            self.__dict__["_assign_status_host"] = (self.assign_status, host, ev)
+        mg = torch.cat([match_g, torch.full((1, max_nq), -1, dtype=torch.int32, device=dev)])
+        return _DeviceMatches(mg, block[4 * P:4 * P + n].view(ntask, L * B), block[4 * P + n:].view(ntask, L * B), count)
+
+    def _targets_all_device(self, L, B, Nq, ncls, t, gts, dm, dev):
+        """_targets_all from the device matches: each query's GT index (match_g, -1 = background)
+        selects its label and box by a gather; a -1 is masked, never used as an index.  #pos per
+        layer is the host-known count of matched GT (no device read)."""
+        R = L * B * Nq
+        npos = [sum(dm.count.get((l, t, b), 0) for b in range(B)) for l in range(L)]
+        gb_l = [gts[(t, b)][0] for b in range(B)]
+        gl_l = [gts[(t, b)][1] for b in range(B)]
+        if sum(npos) == 0:
+            return (torch.full((R,), ncls, dtype=torch.int32, device=dev),
+                    torch.zeros((R, 9), dtype=torch.float32, device=dev),
+                    torch.zeros((R, 10), dtype=torch.float32, device=dev), npos)
+        gb_t = gb_l[0] if B == 1 else torch.cat(gb_l)
+        gl_t = gl_l[0] if B == 1 else torch.cat(gl_l)
+        m = dm.match_g.index_select(0, dm.sel[t])[:, :Nq]                   # [L * B, Nq]
+        valid = (m >= 0).reshape(-1)
+        gi = (m.clamp(min=0).long() + dm.goff[t][:, None]).reshape(-1)     # masked rows read GT 0 of their sample
+        lab = gl_t.index_select(0, gi).int()
+        box = gb_t.index_select(0, gi).float()
+        labels = torch.where(valid, lab, torch.full_like(lab, ncls))
+        tgt = torch.where(valid[:, None], box, torch.zeros_like(box))
+        bw = valid[:, None].float().expand(R, 10).contiguous()
+        return labels, tgt, bw, npos
+
     def _box_terms(self, tgt, bw, code_w):
         """normalize the targets, drop non-finite rows (isnotnan), code weights."""
         nt = _normalize_bbox(tgt)
@@ -575,7 +660,8 @@ class HeadTrainMixin:
             ncls = self.num_classes[t]
             Nq = d["cls_logits"].shape[2]
             pbs, pls, dn = pre[t]
-            labels, tgt, bw, npos = self._targets_all(L, B, Nq, ncls, t, gts, matches, dev)
+            targets = self._targets_all_device if isinstance(matches, _DeviceMatches) else self._targets_all
+            labels, tgt, bw, npos = targets(L, B, Nq, ncls, t, gts, matches, dev)
             nt, w = self._box_terms(tgt, bw, code_w)
             lw = torch.ones(B * Nq, dtype=torch.float32, device=dev)
             R = B * Nq

@@ -130,6 +130,13 @@ class MatchCostArgs(ctypes.Structure):
                 ("cls_weight", _flt), ("reg_weight", _flt), ("cost", _vp)]
 
 
+class LsapArgs(ctypes.Structure):
+    _fields_ = [("P", _int), ("max_nq", _int), ("max_ngt", _int), ("reserved", _int),
+                ("cost", _vp), ("cost_elems", _i64), ("desc", _vp),
+                ("match_q", _vp), ("ld_q", _i64), ("match_g", _vp), ("ld_g", _i64),
+                ("status", _vp), ("workspace", _vp), ("workspace_bytes", _i64)]
+
+
 class AdamwArgs(ctypes.Structure):
     _fields_ = [("n", _i64), ("step", _int), ("lr", _flt), ("beta1", _flt), ("beta2", _flt), ("eps", _flt),
                 ("weight_decay", _flt), ("max_norm", _flt), ("param", _vp), ("grad", _vp), ("exp_avg", _vp),
@@ -149,7 +156,7 @@ class Mlp2Args(ctypes.Structure):
 
 STRUCTS = {"gemm": GemmArgs, "attn": AttnArgs, "ln": LnArgs, "chain": ChainArgs, "gemm_ex": GemmExArgs,
            "attn_train": AttnTrainArgs, "ln_train": LnTrainArgs, "bn": BnArgs, "det_loss": DetLossArgs,
-           "match_cost": MatchCostArgs, "adamw": AdamwArgs, "mlp2": Mlp2Args}
+           "match_cost": MatchCostArgs, "adamw": AdamwArgs, "mlp2": Mlp2Args, "lsap": LsapArgs}
 
 _LIB = None
 
@@ -210,6 +217,7 @@ def _load():
         "cmt_det_loss_args_size": ([], _i64),
         "cmt_match_cost_args_size": ([], _i64),
         "cmt_adamw_args_size": ([], _i64),
+        "cmt_lsap_args_size": ([], _i64),
         "cmt_gemm_f32_ex": ([P(GemmExArgs), _vp], _int),
         "cmt_gemm_bf16x3_ex": ([P(GemmExArgs), _vp], _int),
         "cmt_linear_bwd_bf16x3": ([_vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _i64, _int, _vp], _int),
@@ -226,6 +234,8 @@ def _load():
         "cmt_conv3x3_wgrad_bf16x3": ([_vp, _vp, _vp, _int, _int, _int, _int, _int, _int, _vp], _int),
         "cmt_det_loss": ([P(DetLossArgs), _vp], _int),
         "cmt_match_cost": ([P(MatchCostArgs), _vp], _int),
+        "cmt_lsap_workspace_bytes": ([_int, _int, _int], _i64),
+        "cmt_lsap": ([P(LsapArgs), _vp], _int),
         "cmt_sumsq": ([_vp, _i64, _vp, _vp], _int),
         "cmt_adamw_step": ([P(AdamwArgs), _vp], _int),
     }

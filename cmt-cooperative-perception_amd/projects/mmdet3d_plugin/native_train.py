@@ -9,7 +9,7 @@ import torch
 from . import native as N
 
 __all__ = ["gemm_ex", "set_train_gemm", "linear_fwd", "linear_bwd", "attn_train_fwd", "attn_train_bwd", "ln_train_fwd", "ln_train_bwd",
-           "bn_relu_train_fwd", "bn_relu_train_bwd", "im2col3x3", "conv3x3_wgrad", "det_loss", "match_cost", "sumsq", "adamw_step"]
+           "bn_relu_train_fwd", "bn_relu_train_bwd", "im2col3x3", "conv3x3_wgrad", "det_loss", "match_cost", "lsap", "sumsq", "adamw_step"]
 
 
 def _ptr(t):
@@ -376,6 +376,41 @@ def match_cost(logits, boxes, gt, gt_labels, code_w, *, gamma, alpha, cls_weight
     a.gamma, a.alpha, a.cls_weight, a.reg_weight, a.cost = gamma, alpha, cls_weight, reg_weight, cost.data_ptr()
     N._check(N.lib().cmt_match_cost(ctypes.byref(a), N._stream()), "cmt_match_cost")
     return cost
+
+
+LSAP_MAX_COLS, LSAP_MAX_ROWS = 2048, 512   # cmt_hip.h cmt_lsap limits: max(Nq, ngt), min(Nq, ngt)
+
+
+def lsap(costs, descriptors, *, max_nq, max_ngt, want_match_g=True):
+    """cmt_lsap: the linear sum assignment of P cost matrices held in ONE fp32 device buffer.
+    descriptors: [P, 4] int64 DEVICE tensor (element offset into ``costs``, Nq, ngt, row stride);
+    max_nq / max_ngt: host-known upper bounds of the descriptors' shapes (they size the grid, the
+    workspace and the outputs -- the descriptors themselves are not read on the host).
+    Returns (match_q [P, max_ngt] int32: the query of GT j or -1 in the first ngt entries,
+    match_g [P, max_nq] int32 or None: the GT of query q or -1 in the first Nq entries,
+    status [P] int32: 0 solved, 1 non-finite cost, 2 descriptor outside the bounds); entries past a
+    problem's own ngt / Nq are left unwritten."""
+    _f32(costs)
+    N._dev(descriptors)
+    if descriptors.dtype != torch.int64 or descriptors.dim() != 2 or descriptors.shape[1] != 4 \
+            or not descriptors.is_contiguous() or not costs.is_contiguous():
+        raise RuntimeError("lsap: descriptors must be a contiguous [P, 4] int64 tensor, costs contiguous")
+    P = descriptors.shape[0]
+    dev = costs.device
+    L = N.lib()
+    match_q = torch.empty((P, max_ngt), dtype=torch.int32, device=dev)
+    match_g = torch.empty((P, max_nq), dtype=torch.int32, device=dev) if want_match_g else None
+    status = torch.empty((P,), dtype=torch.int32, device=dev)
+    ws_bytes = L.cmt_lsap_workspace_bytes(P, max_nq, max_ngt)
+    ws = torch.empty((max(ws_bytes, 4) // 4,), dtype=torch.float32, device=dev)
+    a = N.LsapArgs()
+    a.P, a.max_nq, a.max_ngt = P, max_nq, max_ngt
+    a.cost, a.cost_elems, a.desc = costs.data_ptr(), costs.numel(), descriptors.data_ptr()
+    a.match_q, a.ld_q = match_q.data_ptr(), max_ngt
+    a.match_g, a.ld_g = _ptr(match_g), max_nq
+    a.status, a.workspace, a.workspace_bytes = status.data_ptr(), ws.data_ptr(), ws_bytes
+    N._check(L.cmt_lsap(ctypes.byref(a), N._stream()), "cmt_lsap")
+    return match_q, match_g, status
 
 
 def sumsq(x, out):

@@ -133,6 +133,13 @@ class Options:
                            # host issue 39.2 -> 34.9 ms/step, step rate 27.7 vs 28.8 steps/s (r5ai).
                            # Limits: one capture per DN padding (it follows the GT count; 8 kept), and
                            # a second forward before the first one's backward runs eagerly
+    device_assign: bool = False   # CMT_DEVICE_ASSIGN=1 (off by default): the Hungarian assignment of the training
+                           # loss solved on the device (cmt_lsap, float64 shortest augmenting paths) and the
+                           # targets gathered from its matches there, instead of the cost matrices going to
+                           # the host for scipy's linear_sum_assignment: loss() then waits for nothing and
+                           # copies no match back.  A non-finite cost matrix is reported through
+                           # head.assign_status, which Trainer.step reads (scipy's ValueError).  Limits:
+                           # max(Nq, n_gt) <= 2048 and min(Nq, n_gt) <= 512 per sample and task
 
 
 def _env_on(name):
@@ -142,7 +149,8 @@ def _env_on(name):
 OPTIONS = Options(side_stream=_env_on("CMT_SIDE_STREAM"), chain=_env_on("CMT_CHAIN"),
                   bev_pos_cache=_env_on("CMT_BEV_POS_CACHE"), conv_halo=_env_on("CMT_CONV_HALO"),
                   mlp_fused=_env_on("CMT_MLP_FUSED"), chain_combine=_env_on("CMT_CHAIN_COMBINE"),
-                  rv_geo=_env_on("CMT_RV_GEO"), train_graph=os.environ.get("CMT_TRAIN_GRAPH", "0") == "1")
+                  rv_geo=_env_on("CMT_RV_GEO"), train_graph=os.environ.get("CMT_TRAIN_GRAPH", "0") == "1",
+                  device_assign=os.environ.get("CMT_DEVICE_ASSIGN", "0") == "1")
 
 
 @contextlib.contextmanager

@@ -208,6 +208,7 @@ class Trainer:
         self.freeze_gc = freeze_gc
         self._gc_frozen = False
         self._broken = None
+        self._submodules = None   # the module tree, listed once (_check_assign_status)
         multi = dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
         self.fp = FlatParams(module, status_words=64 if multi else 0)
         self.lr, self.wd, self.betas, self.eps, self.max_norm = lr, weight_decay, betas, eps, max_norm
@@ -288,11 +289,42 @@ class Trainer:
             raise
         return total
 
+    def _check_assign_status(self):
+        """OPTIONS.device_assign: the step's one host read of the device assignment's status
+        (the head's ``assign_status``, train_engine._assign_all_device), taken once the backward
+        is queued and before the optimiser touches the weights.  A cost matrix with a NaN or an
+        infinity raises the ValueError scipy's linear_sum_assignment raises for it on the default
+        path; with several ranks the flag is all-reduced first, so every rank raises together."""
+        if not OPTIONS.device_assign:
+            return
+        if self._submodules is None:
+            self._submodules = list(self.module.modules())
+        heads = [m for m in self._submodules if m.__dict__.get("assign_status") is not None]
+        if self.buckets is None:
+            # one rank: the status' pinned host copy the loss started (it waits for the forward's
+            # kernels only); a status set some other way is read from the device
+            bad = 0
+            for m in heads:
+                st, stash = m.__dict__["assign_status"], m.__dict__.get("_assign_status_host")
+                if stash is not None and stash[0] is st:
+                    stash[2].synchronize()
+                    bad |= int(stash[1][0])
+                else:
+                    bad |= int(st.item())
+        else:
+            sts = [m.__dict__["assign_status"] for m in heads]
+            st = torch.stack(sts).amax() if sts else torch.zeros((), dtype=torch.int32, device=self.fp.flat.device)
+            dist.all_reduce(st, op=dist.ReduceOp.MAX, group=self.group)
+            bad = int(st.item())
+        if bad != 0:
+            raise ValueError("cost matrix contains invalid numeric entries")
+
     def step(self, losses):
         self._check_usable()
         total = self.backward(losses)
         if self.buckets is not None:
             self.buckets.finish()
+        self._check_assign_status()
         self.step_count += 1
         self.sumsq.zero_()
         if self.max_norm and self.max_norm > 0:

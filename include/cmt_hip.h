@@ -75,6 +75,7 @@ int64_t cmt_bn_args_size(void);
 int64_t cmt_det_loss_args_size(void);
 int64_t cmt_match_cost_args_size(void);
 int64_t cmt_adamw_args_size(void);
+int64_t cmt_lsap_args_size(void);
 
 /* ------------------------------------------------------------------------
  * GEMM with fused prologue/epilogue (MFMA, gfx950).
@@ -692,6 +693,48 @@ typedef struct cmt_match_cost_args {
     float* cost;
 } cmt_match_cost_args;
 int cmt_match_cost(const cmt_match_cost_args* args, void* stream);
+
+/* Batched rectangular linear sum assignment on the device: the
+ * scipy.optimize.linear_sum_assignment call of HungarianAssigner3D
+ * (hungarian_assigner_3d.py:139-147) for P independent cost matrices in one
+ * call (a memset of status and two launches; additive to ABI 25).
+ *   cost      one fp32 device buffer of cost_elems elements holding every
+ *             matrix, [Nq][ngt] row-major as cmt_match_cost writes them.
+ *   desc      [P][4] int64 in DEVICE memory: element offset into cost, Nq, ngt,
+ *             row stride.  The host reads none of it: it only states P and the
+ *             maxima max_nq / max_ngt that size the grid and the workspace.
+ *   match_q   [P][ld_q] int32: match_q[p][j] = the query matched to GT j or -1
+ *             (entries 0 .. ngt-1 are written, nothing else).
+ *   match_g   [P][ld_g] int32, optional: match_g[p][q] = the GT matched to
+ *             query q or -1 (entries 0 .. Nq-1): the gather form of the matching.
+ *   status    [P] int32: 0 solved; 1 the matrix holds a NaN or an infinity (the
+ *             ValueError of scipy); 2 a descriptor outside max_nq / max_ngt, the
+ *             limits below or the cost buffer.  A problem with a non-zero status
+ *             is not solved: all its matches are -1.
+ * The smaller side is fully assigned (both ngt <= Nq and ngt > Nq work).
+ * Method: the shortest augmenting path algorithm scipy uses (rectangular_lsap,
+ * Crouse's Jonker-Volgenant variant), one wave per problem, dual variables and
+ * path costs in float64 (fp32 costs are exact in it, scipy computes in it): on
+ * a matrix whose optimum is unique the assignment equals scipy's.  An argmin
+ * tie goes to the lowest column index, so a run is bitwise repeatable; on a
+ * matrix with several optima the total cost equals scipy's, the assignment
+ * need not.  Every loop is bounded by the shape (min(Nq, ngt) augmentations of
+ * at most max(Nq, ngt) steps), and the finiteness check runs first.
+ * Limits: max(max_nq, max_ngt) <= 2048, min(max_nq, max_ngt) <= 512, P <=
+ * 65535 (CMT_ENOTSUP beyond); null pointers or P <= 0 give CMT_EINVAL before
+ * any launch.  workspace: cmt_lsap_workspace_bytes(P, max_nq, max_ngt) bytes
+ * (each matrix with its smaller side as rows). */
+typedef struct cmt_lsap_args {
+    int P, max_nq, max_ngt, reserved;
+    const float* cost; int64_t cost_elems;
+    const int64_t* desc;                         /* [P][4] device */
+    int* match_q; int64_t ld_q;                  /* ld_q >= max_ngt */
+    int* match_g; int64_t ld_g;                  /* optional; ld_g >= max_nq */
+    int* status;                                 /* [P] */
+    void* workspace; int64_t workspace_bytes;
+} cmt_lsap_args;
+int64_t cmt_lsap_workspace_bytes(int P, int max_nq, int max_ngt);
+int cmt_lsap(const cmt_lsap_args* args, void* stream);
 
 /* cmt_sumsq: *out += sum x^2 (zero *out first).  cmt_adamw_step:
  * torch.optim.AdamW over a flat buffer; if max_norm > 0 the gradient is scaled
