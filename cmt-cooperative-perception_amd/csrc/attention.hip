@@ -1,10 +1,29 @@
 // Multi-head attention forward, head_dim = 32, for gfx950 (flash-style).
 //
-// One workgroup = 4 waves = 128 query rows of one (batch, head) and one slice
-// of the key range ("kv split").  Each wave owns 32 queries.  Keys are
-// consumed in 64-key tiles staged through a double-buffered LDS image (K and
-// V, 4 KB each); the next tile's global loads are in flight while the current
-// tile is computed.
+// Five kernel families, chosen by attn_fwd_impl (see 'Path choice'):
+//   attn_pb2_kernel      f16 / bf16, long key ranges: 8 waves, ping-pong schedule
+//   attn_kw_kernel       f16 / bf16, <= 64 key tiles: KW waves split the keys of 32 queries
+//   attn_kw_pair_kernel  split-f16 (CMT_F16P), the same workgroup structure
+//   attn_fwd_kernel      f16 / bf16, anything else: 4 waves, split partials
+//   attn_fwd_f32_kernel  exact f32
+// and attn_combine_kernel for the split partials.  The pieces they share are
+// defined once, below AttnKParams: head_ctx (workgroup prologue), load_qf
+// (Q^T fragments), acc_key / mask_keys (accumulator register -> key, ragged
+// tile), vt_frag (V^T fragment), write_row (a finished query row).  Code
+// generation here is sensitive to where a helper is called from: a helper
+// called from another __forceinline__ function leaves the caller's code as it
+// was, one called from a kernel body does not.  attn_pb2_kernel and
+// attn_kw_pair_kernel are held to their former instruction streams, so their
+// bodies keep the prologue and the write written out (the pair kernel also its
+// mask loop), and the two KW kernels keep their ring loop and merge for the
+// same reason.  attn_fwd_f32_kernel writes its mask loop out as well: through
+// mask_keys it needs 160 VGPRs instead of 152.
+//
+// attn_fwd_kernel: one workgroup = 4 waves = 128 query rows of one (batch,
+// head) and one slice of the key range ("kv split").  Each wave owns 32
+// queries.  Keys are consumed in 64-key tiles staged through an LDS ring (K and
+// V, 4 KB each); the next tiles' LDS-DMA is in flight while the current tile
+// is computed.
 //
 // Per 64-key tile and wave (swapped-QK^T form, MI355X guide T12 / 'An
 // accumulator tile as the next MFMA's operand'):
@@ -35,7 +54,7 @@ constexpr int KT = 64;     // keys per tile
 // precision).
 constexpr float kDeferMax = 8.f;
 constexpr int QW = 32;     // queries per wave
-constexpr int NW = 4;      // waves per workgroup (f32 kernel; the f16/bf16 kernel takes it as a template arg)
+constexpr int NW = 4;      // waves per workgroup (attn_fwd_kernel, attn_fwd_f32_kernel)
 constexpr int QB = QW * NW;
 constexpr int D = 32;
 
@@ -80,6 +99,104 @@ __device__ __forceinline__ void store_o4(const AttnKParams& p, int b, int q, int
     }
 }
 
+// ---- pieces every kernel family shares --------------------------------------
+// A workgroup's (batch, head), its Q / K / V planes, and this lane's query row
+// clamped into [0, Nq) (padding lanes of the last query block compute a copy of
+// the last row and write nothing).
+template <typename T>
+struct HeadCtx {
+    int b, h;
+    const T *Q, *K, *V;
+    int qc;
+};
+template <typename T>
+__device__ __forceinline__ HeadCtx<T> head_ctx(const AttnKParams& p, int bh, int q) {
+    HeadCtx<T> x;
+    x.b = bh / p.H;
+    x.h = bh - x.b * p.H;
+    x.Q = (const T*)p.Q + (int64_t)x.b * p.q_bs + (int64_t)x.h * p.q_hs;
+    x.K = (const T*)p.K + (int64_t)x.b * p.k_bs + (int64_t)x.h * p.k_hs;
+    x.V = (const T*)p.V + (int64_t)x.b * p.v_bs + (int64_t)x.h * p.v_hs;
+    x.qc = q < p.Nq ? q : p.Nq - 1;
+    return x;
+}
+
+// The two Q^T fragments of one query row (B operand of S^T = K Q^T):
+// B[k = 8*lh + j][col = q] = Q[q][16*ks + 8*lh + j].  FOLD: times c, rounded to T.
+template <typename T, bool FOLD>
+__device__ __forceinline__ void load_qf(const T* qrow, int lh, float c, typename mfma_traits<T>::frag (&qf)[2]) {
+    typedef typename mfma_traits<T>::frag frag;
+    qf[0] = *(const frag*)(qrow + 8 * lh);
+    qf[1] = *(const frag*)(qrow + 16 + 8 * lh);
+    if (FOLD) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) qf[i][j] = (T)((float)qf[i][j] * c);
+    }
+}
+
+// Register r of a 32x32 accumulator tile in lane half lh holds row (here: key)
+// key0 + acc_key: 4 consecutive rows per 8, the halves 4 apart.
+__device__ __forceinline__ int acc_key(int key0, int r, int lh) { return key0 + (r & 3) + 8 * (r >> 2) + 4 * lh; }
+
+// Ragged last tile: the scores of keys >= Nk become -inf (key0 = key of s's row 0).
+__device__ __forceinline__ f32x16 mask_keys(f32x16 s, int key0, int Nk, int lh) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+        if (acc_key(key0, r, lh) >= Nk) s[r] = -__builtin_inff();
+    return s;
+}
+
+// A V^T fragment (A operand of O^T += V^T P^T) by two transposed LDS reads
+// (ds_read_b64_tr_b16) 8 key rows apart: lane 4q+p of each 16-lane group
+// addresses row (r0 + q), columns dgrp + 4p .. +3; a = that byte address.
+template <typename F>
+__device__ __forceinline__ F vt_frag(const char* a, int rows8) {
+    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((CMT_LDS s16v4_lds*)a);
+    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((CMT_LDS s16v4_lds*)(a + rows8));
+    s16x8 vv;
+    vv[0] = lo[0]; vv[1] = lo[1]; vv[2] = lo[2]; vv[3] = lo[3];
+    vv[4] = hi[0]; vv[5] = hi[1]; vv[6] = hi[2]; vv[7] = hi[3];
+    return __builtin_bit_cast(F, vv);
+}
+
+// A finished query row (lane = query, half lh: head dims 8g + 4lh .. +3 in
+// o[4g .. 4g+3]): splits == 1 writes O / l_tot, rounded to R first when
+// round_out is set (flash-attn returns the input dtype; R = float: never);
+// otherwise the split's unnormalised partial with its row sum and the offset
+// m2 (exp2 units) its P was taken against, for attn_combine_kernel.
+template <typename R>
+__device__ __forceinline__ void write_row(const AttnKParams& p, int b, int h, int split, int q, int lh,
+                                          const f32x16& o, float l_tot, float m2) {
+    if (p.splits == 1) {
+        const float inv = 1.f / l_tot;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            f32x4 v = {o[4 * g] * inv, o[4 * g + 1] * inv, o[4 * g + 2] * inv, o[4 * g + 3] * inv};
+            if constexpr (!std::is_same<R, float>::value) {
+                if (p.round_out) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) v[j] = (float)(R)v[j];
+                }
+            }
+            store_o4(p, b, q, h * D + 8 * g + 4 * lh, v);
+        }
+    } else {
+        const int64_t row = (((int64_t)split * p.B + b) * p.H + h) * p.Nq + q;
+        float* dst = p.Op + row * D;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            f32x4 v = {o[4 * g], o[4 * g + 1], o[4 * g + 2], o[4 * g + 3]};
+            *(f32x4*)(dst + 8 * g + 4 * lh) = v;
+        }
+        if (lh == 0) {
+            p.Mp[row] = m2;
+            p.Lp[row] = l_tot;
+        }
+    }
+}
+
 // One 64-key tile for one wave: S^T = K Q^T, online softmax, O^T += V^T P^T.
 // MASK = keys >= Nk in this tile are set to -inf (only the ragged last tile).
 // The running maximum enters the QK^T chain as its accumulator input (negm =
@@ -112,12 +229,7 @@ __device__ __forceinline__ void attn_tile_lowp(const T* __restrict__ Kt, const T
     }
     if (MASK) {
 #pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int key = key0 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                if (key >= Nk) s[kb][r] = -__builtin_inff();
-            }
+        for (int kb = 0; kb < 2; ++kb) s[kb] = mask_keys(s[kb], key0 + kb * 32, Nk, lh);
     }
     // tile max (two v_max3 chains), then across the lane pair holding the same query
     float m0 = vmax(s[0][0], s[0][1]), m1 = vmax(s[1][0], s[1][1]);
@@ -153,8 +265,6 @@ __device__ __forceinline__ void attn_tile_lowp(const T* __restrict__ Kt, const T
         pf[1][r >> 3][r & 7] = (T)e1;
     }
     lsum[0] += ps;
-    // V^T fragments by transposed LDS reads: lane 4q+p of each 16-lane group
-    // addresses row (r0 + q), columns dgrp + 4p .. +3
     const int dgrp = 16 * ((lane >> 4) & 1);
     const int tq = (lane & 15) >> 2;
     const int tp = lane & 3;
@@ -163,105 +273,8 @@ __device__ __forceinline__ void attn_tile_lowp(const T* __restrict__ Kt, const T
 #pragma unroll
         for (int ss = 0; ss < 2; ++ss) {
             const int r0 = kb * 32 + 16 * ss + 4 * lh + tq;
-            const T* base0 = &Vt[r0 * D + dgrp + 4 * tp];
-            const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((CMT_LDS s16v4_lds*)base0);
-            const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((CMT_LDS s16v4_lds*)(base0 + 8 * D));
-            s16x8 vv;
-            vv[0] = lo[0]; vv[1] = lo[1]; vv[2] = lo[2]; vv[3] = lo[3];
-            vv[4] = hi[0]; vv[5] = hi[1]; vv[6] = hi[2]; vv[7] = hi[3];
-            o = mfma_traits<T>::mma(__builtin_bit_cast(frag, vv), pf[kb][ss], o);
-        }
-}
-
-// Two independent 32-query sub-blocks per wave (64 queries): the K and V
-// fragments read from LDS serve both, and the two dependency chains
-// (QK^T MFMA -> max -> exp -> PV MFMA) interleave in one instruction stream, so
-// one sub-block's softmax VALU work overlaps the other's MFMAs.
-template <typename T, bool MASK, bool FOLD>
-__device__ __forceinline__ void attn_tile2_lowp(const T* __restrict__ Kt, const T* __restrict__ Vt,
-                                                const typename mfma_traits<T>::frag (&qf)[2][2], f32x16 (&o)[2],
-                                                f32x16 (&lsum)[2], f32x16 (&negm)[2], float (&m_run)[2], bool first,
-                                                float c, int key0, int Nk, int lane) {
-    typedef typename mfma_traits<T>::frag frag;
-    const float u = FOLD ? 1.f : c;   // s' units -> exp2 units
-    const int lr = lane & 31;
-    const int lh = lane >> 5;
-    f32x16 s[2][2];
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb) {
-        const int row = kb * 32 + lr;
-        const frag k0 = *(const frag*)(&Kt[row * D + 8 * ((lh) ^ ((row >> 2) & 3))]);
-        const frag k1 = *(const frag*)(&Kt[row * D + 8 * ((2 + lh) ^ ((row >> 2) & 3))]);
-#pragma unroll
-        for (int sb = 0; sb < 2; ++sb) {
-            s[sb][kb] = mfma_traits<T>::mma(k0, qf[sb][0], negm[sb]);
-            s[sb][kb] = mfma_traits<T>::mma(k1, qf[sb][1], s[sb][kb]);
-        }
-    }
-    if (MASK) {
-#pragma unroll
-        for (int sb = 0; sb < 2; ++sb)
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int key = key0 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    if (key >= Nk) s[sb][kb][r] = -__builtin_inff();
-                }
-    }
-    frag pf[2][2][2];
-#pragma unroll
-    for (int sb = 0; sb < 2; ++sb) {
-        float m0 = vmax(s[sb][0][0], s[sb][0][1]), m1 = vmax(s[sb][1][0], s[sb][1][1]);
-#pragma unroll
-        for (int r = 2; r < 16; r += 2) {
-            m0 = vmax3(m0, s[sb][0][r], s[sb][0][r + 1]);
-            m1 = vmax3(m1, s[sb][1][r], s[sb][1][r + 1]);
-        }
-        const float mt = pair_max(vmax(m0, m1));
-        if (first || __any(mt > (FOLD ? kDeferMax : kDeferMax / c))) {
-            const float d = first ? mt : vmax(mt, 0.f);
-            // first tile: O and the sums are still 0 and -d may be huge (exp2 overflow -> 0*inf)
-        const float alpha = first ? 1.f : __builtin_amdgcn_exp2f(-d * u);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                o[sb][r] *= alpha;
-                lsum[sb][r] *= alpha;
-                s[sb][0][r] -= d;
-                s[sb][1][r] -= d;
-            }
-            m_run[sb] += d;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) negm[sb][r] = -m_run[sb];
-        }
-        float ps = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const float e0 = __builtin_amdgcn_exp2f(FOLD ? s[sb][0][r] : s[sb][0][r] * u);
-            const float e1 = __builtin_amdgcn_exp2f(FOLD ? s[sb][1][r] : s[sb][1][r] * u);
-            ps += e0 + e1;
-            pf[sb][0][r >> 3][r & 7] = (T)e0;
-            pf[sb][1][r >> 3][r & 7] = (T)e1;
-        }
-        lsum[sb][0] += ps;
-    }
-    const int dgrp = 16 * ((lane >> 4) & 1);
-    const int tq = (lane & 15) >> 2;
-    const int tp = lane & 3;
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-        for (int ss = 0; ss < 2; ++ss) {
-            const int r0 = kb * 32 + 16 * ss + 4 * lh + tq;
-            const T* base0 = &Vt[r0 * D + dgrp + 4 * tp];
-            const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((CMT_LDS s16v4_lds*)base0);
-            const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((CMT_LDS s16v4_lds*)(base0 + 8 * D));
-            s16x8 vv;
-            vv[0] = lo[0]; vv[1] = lo[1]; vv[2] = lo[2]; vv[3] = lo[3];
-            vv[4] = hi[0]; vv[5] = hi[1]; vv[6] = hi[2]; vv[7] = hi[3];
-            const frag vf = __builtin_bit_cast(frag, vv);
-#pragma unroll
-            for (int sb = 0; sb < 2; ++sb) o[sb] = mfma_traits<T>::mma(vf, pf[sb][kb][ss], o[sb]);
+            const frag vf = vt_frag<frag>((const char*)&Vt[r0 * D + dgrp + 4 * tp], 8 * D * (int)sizeof(T));
+            o = mfma_traits<T>::mma(vf, pf[kb][ss], o);
         }
 }
 
@@ -286,16 +299,10 @@ __device__ __forceinline__ void dma16(const void* g, const void* lds_base) {
     asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "s"(m) : "memory", "m0");
 }
 
-template <int N>
-__device__ __forceinline__ void wait_vm_lgkm() {
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
-}
-
-template <typename T, int NWAVES, bool FOLD, int SUB>
-__global__ __launch_bounds__(NWAVES * 64, SUB == 2 ? 1 : (NWAVES == 8 ? 2 : 2)) void attn_fwd_kernel(AttnKParams p) {
+template <typename T, bool FOLD>
+__global__ __launch_bounds__(NW * 64, 2) void attn_fwd_kernel(AttnKParams p) {
     typedef typename mfma_traits<T>::frag frag;
-    static_assert(SUB == 1 || SUB == 2, "1 or 2 query sub-blocks per wave");
-    constexpr int PERT = 8 / NWAVES;               // glds per thread per tile (8 KB / (NWAVES KB))
+    constexpr int PERT = 8 / NW;                   // glds per thread per tile (8 KB / (NW KB))
     constexpr int STAGE = 2 * KT * D;              // elements: K tile then V tile
     __shared__ __attribute__((aligned(16))) T ring[RING * STAGE];
 
@@ -304,32 +311,12 @@ __global__ __launch_bounds__(NWAVES * 64, SUB == 2 ? 1 : (NWAVES == 8 ? 2 : 2)) 
     const int wave = tid >> 6;
     const int lr = lane & 31;
     const int lh = lane >> 5;
-    const int bh = blockIdx.y;
-    const int b = bh / p.H;
-    const int h = bh - b * p.H;
     const int split = blockIdx.z;
-
-    const T* Qb = (const T*)p.Q + (int64_t)b * p.q_bs + (int64_t)h * p.q_hs;
-    const T* Kb = (const T*)p.K + (int64_t)b * p.k_bs + (int64_t)h * p.k_hs;
-    const T* Vb = (const T*)p.V + (int64_t)b * p.v_bs + (int64_t)h * p.v_hs;
-
-    int qs[SUB];
+    const int q = blockIdx.x * QB + wave * QW + lr;
+    const HeadCtx<T> hc = head_ctx<T>(p, blockIdx.y, q);
     const float c = p.c;
-    // Q^T fragments (B operand): B[k = 8*lh + j][col = q] = Q[q][16*ks + 8*lh + j]
-    frag qf[SUB][2];
-#pragma unroll
-    for (int sb = 0; sb < SUB; ++sb) {
-        qs[sb] = blockIdx.x * (NWAVES * QW * SUB) + (wave * SUB + sb) * QW + lr;
-        const int qc = qs[sb] < p.Nq ? qs[sb] : p.Nq - 1;
-        qf[sb][0] = *(const frag*)(Qb + (int64_t)qc * p.q_rs + 8 * lh);
-        qf[sb][1] = *(const frag*)(Qb + (int64_t)qc * p.q_rs + 16 + 8 * lh);
-        if (FOLD) {
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 8; ++j) qf[sb][i][j] = (T)((float)qf[sb][i][j] * c);
-        }
-    }
+    frag qf[2];
+    load_qf<T, FOLD>(hc.Q + (int64_t)hc.qc * p.q_rs, lh, c, qf);
 
     const int ntiles = (p.Nk + KT - 1) / KT;
     const int t_begin = split * p.tiles_per_split;
@@ -337,34 +324,30 @@ __global__ __launch_bounds__(NWAVES * 64, SUB == 2 ? 1 : (NWAVES == 8 ? 2 : 2)) 
     const int nt = t_end - t_begin;
     const bool ragged = (p.Nk % KT) != 0;
 
-    // this thread's copies: id = i*NWAVES + wave -> (K|V, 16-row block); lane -> (row, chunk)
+    // this thread's copies: id = i*NW + wave -> (K|V, 16-row block); lane -> (row, chunk)
     const int crow = lane >> 2, cch = lane & 3;
     auto issue = [&](int slot, int t) {
         T* st = ring + slot * STAGE;
 #pragma unroll
         for (int i = 0; i < PERT; ++i) {
-            const int id = i * NWAVES + wave;
+            const int id = i * NW + wave;
             const int kv = id >> 2;
             const int row = (id & 3) * 16 + crow;
             const int key = min(t * KT + row, p.Nk - 1);       // ragged tail: clamped, masked in compute
-            const T* src = kv == 0 ? Kb + (int64_t)key * p.k_rs + 8 * (cch ^ ((row >> 2) & 3))
-                                   : Vb + (int64_t)key * p.v_rs + 8 * cch;
+            const T* src = kv == 0 ? hc.K + (int64_t)key * p.k_rs + 8 * (cch ^ ((row >> 2) & 3))
+                                   : hc.V + (int64_t)key * p.v_rs + 8 * cch;
             __builtin_amdgcn_global_load_lds((gaddr_t)src, (laddr_t)(st + kv * KT * D + (id & 3) * 16 * D), 16, 0, 0);
         }
     };
 
-    f32x16 o[SUB], lsum[SUB], negm[SUB];
-    float m_run[SUB];
+    f32x16 o, lsum, negm;
 #pragma unroll
-    for (int sb = 0; sb < SUB; ++sb) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            o[sb][r] = 0.f;
-            lsum[sb][r] = 0.f;
-            negm[sb][r] = 0.f;
-        }
-        m_run[sb] = 0.f;   // placeholder until the first tile sets it
+    for (int r = 0; r < 16; ++r) {
+        o[r] = 0.f;
+        lsum[r] = 0.f;
+        negm[r] = 0.f;
     }
+    float m_run = 0.f;   // placeholder until the first tile sets it
 
 #pragma unroll
     for (int i = 0; i < RING - 1; ++i)
@@ -382,53 +365,15 @@ __global__ __launch_bounds__(NWAVES * 64, SUB == 2 ? 1 : (NWAVES == 8 ? 2 : 2)) 
         const T* Vt = Kt + KT * D;
         const int t = t_begin + i;
         const bool last_ragged = ragged && t == ntiles - 1;
-        if constexpr (SUB == 2) {
-            if (last_ragged)
-                attn_tile2_lowp<T, true, FOLD>(Kt, Vt, qf, o, lsum, negm, m_run, i == 0, c, t * KT, p.Nk, lane);
-            else
-                attn_tile2_lowp<T, false, FOLD>(Kt, Vt, qf, o, lsum, negm, m_run, i == 0, c, t * KT, p.Nk, lane);
-        } else {
-            if (last_ragged)
-                attn_tile_lowp<T, true, FOLD>(Kt, Vt, qf[0], o[0], lsum[0], negm[0], m_run[0], i == 0, c, t * KT,
-                                              p.Nk, lane);
-            else
-                attn_tile_lowp<T, false, FOLD>(Kt, Vt, qf[0], o[0], lsum[0], negm[0], m_run[0], i == 0, c, t * KT,
-                                               p.Nk, lane);
-        }
+        if (last_ragged)
+            attn_tile_lowp<T, true, FOLD>(Kt, Vt, qf, o, lsum, negm, m_run, i == 0, c, t * KT, p.Nk, lane);
+        else
+            attn_tile_lowp<T, false, FOLD>(Kt, Vt, qf, o, lsum, negm, m_run, i == 0, c, t * KT, p.Nk, lane);
     }
 
-    // ---- write ---------------------------------------------------------------
-#pragma unroll
-    for (int sb = 0; sb < SUB; ++sb) {
-        const int q = qs[sb];
-        const float l_tot = pair_sum(lsum[sb][0]);
-        if (q >= p.Nq) continue;
-        if (p.splits == 1) {
-            const float inv = 1.f / l_tot;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                f32x4 v = {o[sb][4 * g] * inv, o[sb][4 * g + 1] * inv, o[sb][4 * g + 2] * inv,
-                           o[sb][4 * g + 3] * inv};
-                if (p.round_out) {   // flash-attn returns the input dtype (attention.py:46 out_fp32 cast after)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) v[j] = (float)(T)v[j];
-                }
-                store_o4(p, b, q, h * D + 8 * g + 4 * lh, v);
-            }
-        } else {
-            const int64_t row = (((int64_t)split * p.B + b) * p.H + h) * p.Nq + q;
-            float* dst = p.Op + row * D;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                f32x4 v = {o[sb][4 * g], o[sb][4 * g + 1], o[sb][4 * g + 2], o[sb][4 * g + 3]};
-                *(f32x4*)(dst + 8 * g + 4 * lh) = v;
-            }
-            if (lh == 0) {
-                p.Mp[row] = FOLD ? m_run[sb] : m_run[sb] * c;   // exp2 units for the combine
-                p.Lp[row] = l_tot;
-            }
-        }
-    }
+    const float l_tot = pair_sum(lsum[0]);
+    if (q >= p.Nq) return;
+    write_row<T>(p, hc.b, hc.h, split, q, lh, o, l_tot, FOLD ? m_run : m_run * c);
 }
 
 // ---------------------------------------------------------------------------
@@ -466,14 +411,9 @@ __global__ __launch_bounds__(KW * 64) void attn_kw_kernel(AttnKParams p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lr = lane & 31;
     const int lh = lane >> 5;
-    const int bh = blockIdx.y;
-    const int b = bh / p.H;
-    const int h = bh - b * p.H;
+    const int q = blockIdx.x * QW + lr;
+    const HeadCtx<T> hc = head_ctx<T>(p, blockIdx.y, q);
     const float c = p.c;
-
-    const T* Qb = (const T*)p.Q + (int64_t)b * p.q_bs + (int64_t)h * p.q_hs;
-    const T* Kb = (const T*)p.K + (int64_t)b * p.k_bs + (int64_t)h * p.k_hs;
-    const T* Vb = (const T*)p.V + (int64_t)b * p.v_bs + (int64_t)h * p.v_hs;
 
     const int ntiles = (p.Nk + KT - 1) / KT;
     const int my_n = wave < ntiles ? (ntiles - 1 - wave) / KW + 1 : 0;   // tiles wave, wave + KW, ...
@@ -487,24 +427,15 @@ __global__ __launch_bounds__(KW * 64) void attn_kw_kernel(AttnKParams p) {
         for (int i = 0; i < 4; ++i) {
             const int row = i * 16 + crow;
             const int key = min(t * KT + row, p.Nk - 1);   // ragged tail: clamped, masked in compute
-            dma16(Kb + (int64_t)key * p.k_rs + 8 * (cch ^ ((row >> 2) & 3)), st + i * 16 * D);
-            dma16(Vb + (int64_t)key * p.v_rs + 8 * cch, st + KT * D + i * 16 * D);
+            dma16(hc.K + (int64_t)key * p.k_rs + 8 * (cch ^ ((row >> 2) & 3)), st + i * 16 * D);
+            dma16(hc.V + (int64_t)key * p.v_rs + 8 * cch, st + KT * D + i * 16 * D);
         }
     };
     if (my_n > 0) issue(0, wave);
     if (my_n > 1) issue(1, wave + KW);
 
-    const int q = blockIdx.x * QW + lr;
-    const int qc = q < p.Nq ? q : p.Nq - 1;
     frag qf[2];
-    qf[0] = *(const frag*)(Qb + (int64_t)qc * p.q_rs + 8 * lh);
-    qf[1] = *(const frag*)(Qb + (int64_t)qc * p.q_rs + 16 + 8 * lh);
-    if (FOLD) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) qf[i][j] = (T)((float)qf[i][j] * c);
-    }
+    load_qf<T, FOLD>(hc.Q + (int64_t)hc.qc * p.q_rs, lh, c, qf);
 
     f32x16 o, lsum, negm;
 #pragma unroll
@@ -525,8 +456,8 @@ __global__ __launch_bounds__(KW * 64) void attn_kw_kernel(AttnKParams p) {
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb) {
                 const int key = min(t * KT + kb * 32 + lr, p.Nk - 1);
-                const frag k0 = *(const frag*)(Kb + (int64_t)key * p.k_rs + 8 * lh);
-                const frag k1 = *(const frag*)(Kb + (int64_t)key * p.k_rs + 16 + 8 * lh);
+                const frag k0 = *(const frag*)(hc.K + (int64_t)key * p.k_rs + 8 * lh);
+                const frag k1 = *(const frag*)(hc.K + (int64_t)key * p.k_rs + 16 + 8 * lh);
                 f32x16 z;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) z[r] = 0.f;
@@ -535,12 +466,7 @@ __global__ __launch_bounds__(KW * 64) void attn_kw_kernel(AttnKParams p) {
             }
             if (ragged && t == ntiles - 1) {
 #pragma unroll
-                for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int key = t * KT + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                        if (key >= p.Nk) s[kb][r] = -__builtin_inff();
-                    }
+                for (int kb = 0; kb < 2; ++kb) s[kb] = mask_keys(s[kb], t * KT + kb * 32, p.Nk, lh);
             }
 #pragma unroll
             for (int r = 0; r < 16; ++r) mw = vmax3(mw, s[0][r], s[1][r]);
@@ -609,7 +535,7 @@ __global__ __launch_bounds__(KW * 64) void attn_kw_kernel(AttnKParams p) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) v[j] = (float)(T)v[j];
             }
-            store_o4(p, b, qo, h * D + d0, v);
+            store_o4(p, hc.b, qo, hc.h * D + d0, v);
         }
     }
 }
@@ -661,12 +587,10 @@ __device__ __forceinline__ void attn_tile_pair(const f16_t* __restrict__ Kt, con
     s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh1, ql[1], s, 0, 0, 0);
     s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh0, qh[0], s, 0, 0, 0);
     s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh1, qh[1], s, 0, 0, 0);
-    if (MASK) {
+    if (MASK) {   // mask_keys written out: through the helper this kernel's code changes
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int key = key0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-            if (key >= Nk) s[r] = -__builtin_inff();
-        }
+        for (int r = 0; r < 16; ++r)
+            if (acc_key(key0, r, lh) >= Nk) s[r] = -__builtin_inff();
     }
     float mt = vmax(s[0], s[1]);
 #pragma unroll
@@ -694,7 +618,7 @@ __device__ __forceinline__ void attn_tile_pair(const f16_t* __restrict__ Kt, con
         ph[r >> 3][r & 7] = h;
         pl[r >> 3][r & 7] = (f16_t)(pv - (float)h);
     }
-    // V^T fragments by transposed LDS reads (attn_tile_lowp's key order), both halves
+    // V^T fragments (vt_frag, attn_tile_lowp's key order), both halves
     const int dgrp = 16 * ((lane >> 4) & 1);
     const int tq = (lane & 15) >> 2;
     const int tp = lane & 3;
@@ -704,13 +628,7 @@ __device__ __forceinline__ void attn_tile_pair(const f16_t* __restrict__ Kt, con
         f16x8 vf[2];
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
-            const f16_t* base0 = &Vt[r0 * PRW + 32 * half + dgrp + 4 * tp];
-            const s16x4 a0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((CMT_LDS s16v4_lds*)base0);
-            const s16x4 a1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((CMT_LDS s16v4_lds*)(base0 + 8 * PRW));
-            s16x8 vv;
-            vv[0] = a0[0]; vv[1] = a0[1]; vv[2] = a0[2]; vv[3] = a0[3];
-            vv[4] = a1[0]; vv[5] = a1[1]; vv[6] = a1[2]; vv[7] = a1[3];
-            vf[half] = __builtin_bit_cast(f16x8, vv);
+            vf[half] = vt_frag<f16x8>((const char*)&Vt[r0 * PRW + 32 * half + dgrp + 4 * tp], 8 * PRW * 2);
         }
         o = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf[1], ph[ss], o, 0, 0, 0);
         o = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf[0], pl[ss], o, 0, 0, 0);
@@ -758,7 +676,7 @@ __global__ __launch_bounds__(KW * 64) void attn_kw_pair_kernel(AttnKParams p) {
     if (my_n > 0) issue(0, wave);
     if (my_n > 1) issue(1, wave + KW);
 
-    // Q^T fragments (B operand), q * c re-split: B[k = 8 lh + j][col = q] = Q[q][16 ks + 8 lh + j]
+    // Q^T fragments (load_qf's layout) of both halves, q * c re-split
     const int q = blockIdx.x * QW + lr;
     const int qc = q < p.Nq ? q : p.Nq - 1;
     f16x8 qh[2], ql[2];
@@ -796,7 +714,7 @@ __global__ __launch_bounds__(KW * 64) void attn_kw_pair_kernel(AttnKParams p) {
     }
     l_run = pair_sum(l_run);
 
-    // ---- merge the KW partials through LDS (each wave's own ring region holds its O^T image)
+    // ---- merge: attn_kw_kernel's, without the rounding (a change to one goes into the other)
     wait_vm_lgkm<0>();
     float* xo = (float*)myring;
 #pragma unroll
@@ -859,11 +777,6 @@ __device__ __forceinline__ float kmax_reduce(const AttnKParams& p, int b, int h,
     return km;
 }
 
-template <int N>
-__device__ __forceinline__ void pp_wait_n() {
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
-}
-
 // ---------------------------------------------------------------------------
 // Long-key kernel (the cross-attention shape: Nk >= 4096, Nq > 128), f16/bf16,
 // 8 waves, two 64-key tiles per ping-pong window.
@@ -921,7 +834,7 @@ __device__ __forceinline__ void pp_barrier() {
 }
 
 // LDS -> register fragments of one tile: K rows (A operand of S^T = K Q^T,
-// XOR-swizzled image) and V^T (A operand of O^T += V^T P^T, transposed reads).
+// XOR-swizzled image) and V^T (vt_frag).
 // The lane-dependent parts of the addresses are byte offsets (PpLane) that the
 // caller re-launders per use (empty asm), so every read is lane base +
 // compile-time immediate -- no per-slot address registers kept live.
@@ -964,13 +877,7 @@ __device__ __forceinline__ void pp_load_v(const char* Vt, const PpLane& l, typen
     for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
         for (int ss = 0; ss < 2; ++ss) {
-            const char* base0 = Vt + l.v + (kb * 32 + 16 * ss) * D * (int)sizeof(T);
-            const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((CMT_LDS s16v4_lds*)base0);
-            const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((CMT_LDS s16v4_lds*)(base0 + 8 * D * sizeof(T)));
-            s16x8 vv;
-            vv[0] = lo[0]; vv[1] = lo[1]; vv[2] = lo[2]; vv[3] = lo[3];
-            vv[4] = hi[0]; vv[5] = hi[1]; vv[6] = hi[2]; vv[7] = hi[3];
-            vf[kb][ss] = __builtin_bit_cast(frag, vv);
+            vf[kb][ss] = vt_frag<frag>(Vt + l.v + (kb * 32 + 16 * ss) * D * (int)sizeof(T), 8 * D * (int)sizeof(T));
         }
 }
 
@@ -1104,11 +1011,11 @@ __device__ __forceinline__ void pb2_vseg(f32x16 (&s0)[2], f32x16 (&s1)[2], typen
 
 // tiles (two LDS-DMA pieces each) still allowed in flight behind the ones needed now, 0..4
 __device__ __forceinline__ void pb2_wait(int tiles) {
-    if (tiles >= 4) pp_wait_n<8>();
-    else if (tiles == 3) pp_wait_n<6>();
-    else if (tiles == 2) pp_wait_n<4>();
-    else if (tiles == 1) pp_wait_n<2>();
-    else pp_wait_n<0>();
+    if (tiles >= 4) wait_vm_lgkm<8>();
+    else if (tiles == 3) wait_vm_lgkm<6>();
+    else if (tiles == 2) wait_vm_lgkm<4>();
+    else if (tiles == 1) wait_vm_lgkm<2>();
+    else wait_vm_lgkm<0>();
 }
 
 // US (f16, bounded offsets or not): Q enters the QK^T MFMAs unscaled, exactly the f16 q the
@@ -1305,7 +1212,7 @@ __global__ __launch_bounds__(512, 2) void attn_pb2_kernel(AttnKParams p) {
             // leftover full tile (odd count): every wave at once
             if (!hb) {
                 issue_upto(nt);
-                pp_wait_n<0>();
+                wait_vm_lgkm<0>();
             }
             pp_barrier();
             const PpLane l = pp_launder(lane_ofs);
@@ -1326,7 +1233,7 @@ __global__ __launch_bounds__(512, 2) void attn_pb2_kernel(AttnKParams p) {
                 const T* vs = Vb + (int64_t)key * p.v_rs + 8 * cch;
                 dma16(ks, my_k);
                 dma16(vs, my_k + KT * D);
-                pp_wait_n<0>();
+                wait_vm_lgkm<0>();
             }
             pp_barrier();
             const PpLane l = pp_launder(lane_ofs);
@@ -1335,10 +1242,7 @@ __global__ __launch_bounds__(512, 2) void attn_pb2_kernel(AttnKParams p) {
             if (livew) pb_mseg<T, true, false, QS>(kf0, vf0, qf, ql, sinit, pf0, s0, o, lsum);
             const int key0 = (ntiles - 1) * KT;
 #pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    if (key0 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh >= p.Nk) s0[kb][r] = -__builtin_inff();
+            for (int kb = 0; kb < 2; ++kb) s0[kb] = mask_keys(s0[kb], key0 + kb * 32, p.Nk, lh);
             if (livew) us_scale(s0, fastw);
             if (livew) pb_vseg<T>(s0, pf0, o, lsum, m_run, fastw, nt == 0);
             if (livew) pb_mseg<T, false, true, QS>(kf0, vf0, qf, ql, sinit, pf0, s0, o, lsum);
@@ -1416,20 +1320,12 @@ __global__ __launch_bounds__(256) void attn_fwd_f32_kernel(AttnKParams p) {
     const int wave = tid >> 6;
     const int lr = lane & 31;
     const int lh = lane >> 5;
-    const int bh = blockIdx.y;
-    const int b = bh / p.H;
-    const int h = bh - b * p.H;
     const int split = blockIdx.z;
-
-    const float* Qb = (const float*)p.Q + (int64_t)b * p.q_bs + (int64_t)h * p.q_hs;
-    const float* Kb = (const float*)p.K + (int64_t)b * p.k_bs + (int64_t)h * p.k_hs;
-    const float* Vb = (const float*)p.V + (int64_t)b * p.v_bs + (int64_t)h * p.v_hs;
-
     const int q = blockIdx.x * QB + wave * QW + lr;
-    const int qc = q < p.Nq ? q : p.Nq - 1;
+    const HeadCtx<float> hc = head_ctx<float>(p, blockIdx.y, q);
     f32x4 qf[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) qf[i] = *(const f32x4*)(Qb + (int64_t)qc * p.q_rs + 16 * lh + 4 * i);
+    for (int i = 0; i < 4; ++i) qf[i] = *(const f32x4*)(hc.Q + (int64_t)hc.qc * p.q_rs + 16 * lh + 4 * i);
 
     const int ntiles = (p.Nk + KT - 1) / KT;
     const int t_begin = split * p.tiles_per_split;
@@ -1443,8 +1339,8 @@ __global__ __launch_bounds__(256) void attn_fwd_f32_kernel(AttnKParams p) {
             const int row = idx >> 3, c4 = idx & 7;
             const int key = t * KT + row;
             if (key < p.Nk) {
-                kreg[i] = *(const f32x4*)(Kb + (int64_t)key * p.k_rs + 4 * c4);
-                vreg[i] = *(const f32x4*)(Vb + (int64_t)key * p.v_rs + 4 * c4);
+                kreg[i] = *(const f32x4*)(hc.K + (int64_t)key * p.k_rs + 4 * c4);
+                vreg[i] = *(const f32x4*)(hc.V + (int64_t)key * p.v_rs + 4 * c4);
             } else {
                 kreg[i] = f32x4{0.f, 0.f, 0.f, 0.f};
                 vreg[i] = kreg[i];
@@ -1490,14 +1386,12 @@ __global__ __launch_bounds__(256) void attn_fwd_f32_kernel(AttnKParams p) {
                     s[kb] = __builtin_amdgcn_mfma_f32_32x32x2f32(kv[j], qf[i][j], s[kb], 0, 0, 0);
             }
         }
-        if ((t + 1) * KT > p.Nk) {
+        if ((t + 1) * KT > p.Nk) {   // mask_keys written out (VGPRs, see the file header)
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    int key = t * KT + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    if (key >= p.Nk) s[kb][r] = -__builtin_inff();
-                }
+                for (int r = 0; r < 16; ++r)
+                    if (acc_key(t * KT + kb * 32, r, lh) >= p.Nk) s[kb][r] = -__builtin_inff();
         }
         float mt = s[0][0];
 #pragma unroll
@@ -1525,8 +1419,7 @@ __global__ __launch_bounds__(256) void attn_fwd_f32_kernel(AttnKParams p) {
         for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int key = kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                const float v = Vs[cur][key * D + lr];
+                const float v = Vs[cur][acc_key(kb * 32, r, lh) * D + lr];
                 o = __builtin_amdgcn_mfma_f32_32x32x2f32(v, s[kb][r], o, 0, 0, 0);
             }
         if (t + 1 < t_end) store_tile(cur ^ 1);
@@ -1534,26 +1427,7 @@ __global__ __launch_bounds__(256) void attn_fwd_f32_kernel(AttnKParams p) {
     }
     const float l_tot = l_run + __shfl_xor(l_run, 32);
     if (q >= p.Nq) return;
-    if (p.splits == 1) {
-        const float inv = 1.f / l_tot;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            f32x4 v = {o[4 * g] * inv, o[4 * g + 1] * inv, o[4 * g + 2] * inv, o[4 * g + 3] * inv};
-            store_o4(p, b, q, h * D + 8 * g + 4 * lh, v);
-        }
-    } else {
-        const int64_t row = (((int64_t)split * p.B + b) * p.H + h) * p.Nq + q;
-        float* dst = p.Op + row * D;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            f32x4 v = {o[4 * g], o[4 * g + 1], o[4 * g + 2], o[4 * g + 3]};
-            *(f32x4*)(dst + 8 * g + 4 * lh) = v;
-        }
-        if (lh == 0) {
-            p.Mp[row] = m_run * c;   // exp2 units for the combine
-            p.Lp[row] = l_tot;
-        }
-    }
+    write_row<float>(p, hc.b, hc.h, split, q, lh, o, l_tot, m_run * c);
 }
 
 // Merge the kv-split partials: 8 threads per (b, h, q), each owning 4 of the
@@ -1623,18 +1497,17 @@ bool use_kw(const cmt_attn_args& a) {
     return (a.Nk + KT - 1) / KT <= 64;
 }
 
-// CUs of the current device (the round size of a one-workgroup-per-CU grid), read once
-int device_cus() {
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) == hipSuccess &&
-            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
-            cus = n;
-        else
-            cus = 256;
+// The (dtype, fold) of a 16-bit call as types: f(T{}, std::bool_constant<FOLD>{}) picks a
+// kernel family's instantiation once.
+template <typename F>
+void lowp_case(int dtype, bool fold, F&& f) {
+    if (dtype == CMT_F16) {
+        if (fold) f(f16_t{}, std::true_type{});
+        else f(f16_t{}, std::false_type{});
+    } else {
+        if (fold) f(bf16_t{}, std::true_type{});
+        else f(bf16_t{}, std::false_type{});
     }
-    return cus;
 }
 
 int choose_splits(const cmt_attn_args& a) {
@@ -1650,7 +1523,7 @@ int choose_splits(const cmt_attn_args& a) {
         // 900 queries over 56 400 / 32 400 keys: 8 splits (one round of 256); 1 500 queries over
         // 48 400 keys (configs[4]): 5 splits, 120 vs 142 us for the former power of two 8 -- 384
         // workgroups in 1.5 rounds (profiles/r6_experiments.txt r6v)
-        const int cus = device_cus();
+        const int cus = cmt_cu_count();
         int best = 1;
         int64_t best_cost = INT64_MAX;
         for (int s = 1; s <= 16; ++s) {
@@ -1760,33 +1633,26 @@ int attn_fwd_impl(const cmt_attn_args& a, float* lse, void* stream) {
         attn_fwd_f32_kernel<<<dim3(cdiv(a.Nq, QB), a.B * a.H, splits), 256, 0, s>>>(p);
     } else if (use_kw(a)) {
         const dim3 g2(cdiv(a.Nq, QW), a.B * a.H);
-        if (a.dtype == CMT_F16) {
-            if (fold) attn_kw_kernel<f16_t, true, 8><<<g2, 512, 0, s>>>(p);
-            else attn_kw_kernel<f16_t, false, 8><<<g2, 512, 0, s>>>(p);
-        } else {
-            if (fold) attn_kw_kernel<bf16_t, true, 8><<<g2, 512, 0, s>>>(p);
-            else attn_kw_kernel<bf16_t, false, 8><<<g2, 512, 0, s>>>(p);
-        }
+        lowp_case(a.dtype, fold, [&](auto t, auto f) {
+            attn_kw_kernel<decltype(t), decltype(f)::value, 8><<<g2, 512, 0, s>>>(p);
+        });
     } else if (use_long(a)) {
         // the scale is folded into Q either way; without the FOLD permission q * c is kept as hi + lo
+        // (QS), or, f16 with CMT_ATTN_UNSCALED_Q, Q enters unscaled (US)
         const unsigned nwg = (unsigned)p.nqb * a.B * a.H * splits;
-        if (a.dtype == CMT_F16) {
-            if (fold) attn_pb2_kernel<f16_t, false><<<nwg, 512, 0, s>>>(p);
-            else if (us_mode(a.flags)) attn_pb2_kernel<f16_t, false, true><<<nwg, 512, 0, s>>>(p);
-            else attn_pb2_kernel<f16_t, true><<<nwg, 512, 0, s>>>(p);
-        } else {
-            if (fold) attn_pb2_kernel<bf16_t, false><<<nwg, 512, 0, s>>>(p);
-            else attn_pb2_kernel<bf16_t, true><<<nwg, 512, 0, s>>>(p);
-        }
+        lowp_case(a.dtype, fold, [&](auto t, auto f) {
+            typedef decltype(t) T;
+            constexpr bool FOLD = decltype(f)::value;
+            if (std::is_same<T, f16_t>::value && !FOLD && us_mode(a.flags))
+                attn_pb2_kernel<f16_t, false, true><<<nwg, 512, 0, s>>>(p);
+            else
+                attn_pb2_kernel<T, !FOLD><<<nwg, 512, 0, s>>>(p);
+        });
     } else {
-        const dim3 grid(cdiv(a.Nq, 4 * QW), a.B * a.H, splits);
-        if (a.dtype == CMT_F16) {
-            if (fold) attn_fwd_kernel<f16_t, 4, true, 1><<<grid, 256, 0, s>>>(p);
-            else attn_fwd_kernel<f16_t, 4, false, 1><<<grid, 256, 0, s>>>(p);
-        } else {
-            if (fold) attn_fwd_kernel<bf16_t, 4, true, 1><<<grid, 256, 0, s>>>(p);
-            else attn_fwd_kernel<bf16_t, 4, false, 1><<<grid, 256, 0, s>>>(p);
-        }
+        const dim3 grid(cdiv(a.Nq, QB), a.B * a.H, splits);
+        lowp_case(a.dtype, fold, [&](auto t, auto f) {
+            attn_fwd_kernel<decltype(t), decltype(f)::value><<<grid, NW * 64, 0, s>>>(p);
+        });
     }
     int rc = cmt_check_launch("cmt_attn_fwd");
     if (rc || splits == 1 || (a.flags & CMT_ATTN_KEEP_PARTIALS)) return rc;   // KEEP: partials for chain B1

@@ -81,6 +81,14 @@ __device__ __forceinline__ float pair_sum(float x) {
 // landed -- a 4 x 8 block of wrong outputs in ~1 of 10^6 GEMM tiles).
 __device__ __forceinline__ void barrier_mem() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
+// Counted wait for LDS-DMA (global_load_lds) pieces: at most N of this wave's
+// vector-memory operations stay in flight, and every LDS access it issued has
+// completed (the barrier that follows hands its LDS writes to the other waves).
+template <int N>
+__device__ __forceinline__ void wait_vm_lgkm() {
+    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
+}
+
 // Non-finite sanitiser with torch.nan_to_num defaults.
 __device__ __forceinline__ float nan_to_num(float x) {
     if (x != x) return 0.f;

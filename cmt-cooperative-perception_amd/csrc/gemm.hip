@@ -424,11 +424,6 @@ __device__ __forceinline__ void glds16(const void* src, void* lds) {
     __builtin_amdgcn_global_load_lds((gaddr_t)src, (laddr_t)lds, 16, 0, 0);
 }
 
-template <int N>
-__device__ __forceinline__ void wait_vm_lgkm() {
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
-}
-
 template <int PER, int S>
 __device__ __forceinline__ void wait_tiles(int inflight) {
     if (S > 3 && inflight >= 3) wait_vm_lgkm<(S > 3 ? 3 * PER : 0)>();

@@ -55,13 +55,6 @@ constexpr int DMA_PER_STAGE = STG_BYTES / 16 / NTC;   // 16-byte LDS-DMA pieces 
 typedef const __attribute__((address_space(1))) void* rc_gaddr_t;
 typedef __attribute__((address_space(3))) void* rc_laddr_t;
 
-// counted LDS-DMA wait + every outstanding LDS access of this wave (the
-// barrier that follows hands LDS writes to the other waves)
-template <int N>
-__device__ __forceinline__ void rc_wait() {
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
-}
-
 template <typename T>
 struct Eng : RowCtx<OFF_PRM, OFF_RED> {
     typedef typename mfma_traits<T>::frag frag;
@@ -98,11 +91,11 @@ struct Eng : RowCtx<OFF_PRM, OFF_RED> {
     __device__ __forceinline__ void acquire() {
         const int ahead = issued - consumed - 1;   // stages issued after the one needed now
         static_assert(NSTG - 2 == 4, "wait ladder covers 0..4 stages");
-        if (ahead >= 4) rc_wait<4 * DMA_PER_STAGE>();
-        else if (ahead == 3) rc_wait<3 * DMA_PER_STAGE>();
-        else if (ahead == 2) rc_wait<2 * DMA_PER_STAGE>();
-        else if (ahead == 1) rc_wait<DMA_PER_STAGE>();
-        else rc_wait<0>();
+        if (ahead >= 4) wait_vm_lgkm<4 * DMA_PER_STAGE>();
+        else if (ahead == 3) wait_vm_lgkm<3 * DMA_PER_STAGE>();
+        else if (ahead == 2) wait_vm_lgkm<2 * DMA_PER_STAGE>();
+        else if (ahead == 1) wait_vm_lgkm<DMA_PER_STAGE>();
+        else wait_vm_lgkm<0>();
         barrier_mem();
         issue();
     }
@@ -278,7 +271,7 @@ __global__ __launch_bounds__(NTC, 1) void chain_kernel(cmt_chain_args a) {
     // first use of the ordinary loads: everything issued so far has landed after this
     asm volatile("" ::"v"(res[0]), "v"(res[VPL - 1]), "v"(qp[0]), "v"(qp[VPL - 1]), "v"(oold[0]),
                  "v"(oold[VPL - 1]));
-    rc_wait<0>();
+    wait_vm_lgkm<0>();
     barrier_mem();
 
     f32x16 acc;
