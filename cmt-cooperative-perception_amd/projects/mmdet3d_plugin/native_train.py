@@ -340,6 +340,19 @@ def conv3x3_wgrad(X, dY, nimg, H, W, Cin, ksplit):
     return dW
 
 
+def _grad_like_rows(x):
+    """A gradient buffer for the 2-D ``x`` that the kernel addresses with x's OWN row stride
+    (cmt_det_loss_args has one ld_* for an input and its gradient): dense x -> an unfilled dense
+    tensor (the kernel writes every element); otherwise the [:, :width] view of a zeroed
+    [R, x.stride(0)] parent (zeros_like of a column slice would be dense, R * width elements, while
+    the kernel writes rows R * ld apart)."""
+    if x.dim() != 2 or (x.shape[1] > 1 and x.stride(1) != 1) or x.stride(0) < x.shape[1]:
+        raise RuntimeError("det_loss: inputs must be 2-D with unit column stride and non-overlapping rows")
+    if x.stride(0) == x.shape[1]:
+        return torch.empty(x.shape, dtype=x.dtype, device=x.device)
+    return torch.zeros((x.shape[0], x.stride(0)), dtype=x.dtype, device=x.device)[:, :x.shape[1]]
+
+
 def det_loss(logits, labels, label_w, boxes, targets, box_w, *, gamma, alpha, cls_weight, box_weight, cls_avg,
              box_avg, need_grad=True, out=None):
     """(loss [2] device tensor, dlogits, dboxes) of FocalLoss + L1Loss; out: a caller's [2] slot."""
@@ -349,9 +362,9 @@ def det_loss(logits, labels, label_w, boxes, targets, box_w, *, gamma, alpha, cl
         out = torch.empty(2, dtype=torch.float32, device=logits.device)
     elif out.dtype != torch.float32 or out.numel() != 2 or not out.is_contiguous():
         raise RuntimeError("det_loss: out must be a contiguous fp32 [2] tensor")
-    # the kernel writes every gradient element (rows x ncls, rows x 10): no fill for dense operands
-    dl = (torch.empty_like if logits.is_contiguous() else torch.zeros_like)(logits) if need_grad else None
-    db = (torch.empty_like if boxes.is_contiguous() else torch.zeros_like)(boxes) if need_grad else None
+    # the kernel writes every gradient element (rows x ncls, rows x 10) at the input's row stride
+    dl = _grad_like_rows(logits) if need_grad else None
+    db = _grad_like_rows(boxes) if need_grad else None
     a = N.DetLossArgs()
     a.R, a.ncls = logits.shape
     a.logits, a.ld_logits, a.labels, a.label_w = logits.data_ptr(), logits.stride(0), labels.data_ptr(), _ptr(label_w)
