@@ -283,8 +283,6 @@ __device__ __forceinline__ void attn_tile_lowp(const T* __restrict__ Kt, const T
 // one barrier per tile: a wave-instruction copies 16 key rows (1 KB) of K or V;
 // the K image's 16-byte chunk swizzle is applied to the source address.
 constexpr int RING = 4;
-typedef const __attribute__((address_space(1))) void* gaddr_t;
-typedef __attribute__((address_space(3))) void* laddr_t;
 
 // One 16-byte-per-lane LDS-DMA piece (global_load_lds_dwordx4, 1 KB per wave)
 // issued from inline asm.  Issued through the builtin, the compiler's waitcnt
@@ -336,7 +334,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_kernel(AttnKParams p) {
             const int key = min(t * KT + row, p.Nk - 1);       // ragged tail: clamped, masked in compute
             const T* src = kv == 0 ? hc.K + (int64_t)key * p.k_rs + 8 * (cch ^ ((row >> 2) & 3))
                                    : hc.V + (int64_t)key * p.v_rs + 8 * cch;
-            __builtin_amdgcn_global_load_lds((gaddr_t)src, (laddr_t)(st + kv * KT * D + (id & 3) * 16 * D), 16, 0, 0);
+            glds16(src, st + kv * KT * D + (id & 3) * 16 * D);
         }
     };
 

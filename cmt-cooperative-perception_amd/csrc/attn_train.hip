@@ -975,9 +975,8 @@ __global__ __launch_bounds__(64 * (8 / QB)) void train16_dq2_kernel(AP p, const 
             for (int i = 0; i < QB; ++i) {
                 const int pc = wave + NWV * i, piece = pc & 3;
                 const int key = min(issued * KT + 16 * piece + prow_l, a.Nk - 1);
-                __builtin_amdgcn_global_load_lds(
-                    (const __attribute__((address_space(1))) void*)(src0[i] + (int64_t)key * D),
-                    (__attribute__((address_space(3))) void*)(dst0[i] + (issued % DQ_RING) * 2 * KT * 64), 16, 0, 0);
+                glds16(src0[i] + (int64_t)key * D,
+                       dst0[i] + (issued % DQ_RING) * 2 * KT * 64);
             }
             ++issued;
         }

@@ -89,6 +89,14 @@ __device__ __forceinline__ void wait_vm_lgkm() {
     asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
 }
 
+// One LDS-DMA piece (global_load_lds_dwordx4): every lane copies 16 bytes from its own global
+// address; the wave's 1 KB lands lane-linear at the (wave-uniform) LDS address.
+typedef const __attribute__((address_space(1))) void* gaddr_t;
+typedef __attribute__((address_space(3))) void* laddr_t;
+__device__ __forceinline__ void glds16(const void* src, void* lds) {
+    __builtin_amdgcn_global_load_lds((gaddr_t)src, (laddr_t)lds, 16, 0, 0);
+}
+
 // Non-finite sanitiser with torch.nan_to_num defaults.
 __device__ __forceinline__ float nan_to_num(float x) {
     if (x != x) return 0.f;

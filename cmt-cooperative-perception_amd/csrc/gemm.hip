@@ -15,15 +15,19 @@
 // Exact-f32 path: v_mfma_f32_32x32x2_f32 with the k index permuted as
 // k = 16*(lane>>5) + t so each lane reads 16 contiguous floats; LDS rows are
 // padded to 36 floats (conflict-free ds_read_b128).
+//
+// Which calls reach which kernel (cmt_gemm's dispatch, bottom of the file):
+//   CMT_A_CONV3X3_NCHW                        conv_halo_x3_kernel
+//   A, W both CMT_F16P, rows / 3x3, >= 160
+//     256 x 128 tiles, row-mode C             gemm_x3_kernel
+//   A in the compute dtype (f16 / bf16 /
+//     pair), every a_mode                     gemm_dma_kernel (cmt_gemm_ln: gemm_ln_kernel)
+//   fp32 A, f16 / bf16 W, rows or CONV1D3     gemm_lowp_kernel (A cast in registers; a 3x3
+//                                             gather with fp32 A is rejected)
+//   fp32 A, fp32 W, every a_mode              gemm_f32_kernel
 #include "cmt_common.h"
 
 #include <cstdlib>
-
-// conv_halo_x3_kernel's variant bits for dev experiments (dev/build_exp.sh -DCMT_CONV_VAR=n); the
-// product build compiles variant 0 only
-#ifndef CMT_CONV_VAR
-#define CMT_CONV_VAR 0
-#endif
 
 namespace {
 
@@ -77,15 +81,18 @@ __device__ __forceinline__ int64_t a_offset(const cmt_gemm_args& a, const RowInf
     }
 }
 
+// columns of A one tap of the implicit conv covers (rows: all of K)
+__host__ __device__ __forceinline__ int tap_width(const cmt_gemm_args& a, int a_mode) {
+    return a_mode == CMT_A_CONV3X3 ? a.conv_c : (a_mode == CMT_A_CONV1D3 ? a.K / 3 : a.K);
+}
+
 __device__ __forceinline__ float load_elem(const void* p, int64_t idx, int dt) {
     if (dt == CMT_F32) return ((const float*)p)[idx];
     if (dt == CMT_F16) return (float)((const f16_t*)p)[idx];
     return (float)((const bf16_t*)p)[idx];
 }
 
-template <typename T>
 __device__ __forceinline__ void store_out(void* C, int64_t idx, int dt, float v) {
-    (void)sizeof(T);
     if (dt == CMT_F32) ((float*)C)[idx] = v;
     else if (dt == CMT_F16) ((f16_t*)C)[idx] = (f16_t)v;
     else ((bf16_t*)C)[idx] = (bf16_t)v;
@@ -153,14 +160,15 @@ __device__ __forceinline__ void epilogue(const cmt_gemm_args& a, f32x16 (&acc)[B
                     }
                     idx = (((int64_t)b * (a.N >> 5) + (col >> 5)) * rpb + rr) * 32 + (col & 31);
                 }
-                store_out<float>(Cz, idx, a.c_dtype, acc[tm][tn][r]);
+                store_out(Cz, idx, a.c_dtype, acc[tm][tn][r]);
             }
         }
     }
 }
 
 // ---------------------------------------------------------------------------
-// f16 / bf16 compute
+// f16 / bf16 compute with fp32 A (cast in registers on the way to LDS); a call
+// whose A is already in the compute dtype takes the LDS-DMA path below
 // ---------------------------------------------------------------------------
 template <int CPR>
 __device__ __forceinline__ int swz(int row, int c) {
@@ -170,7 +178,7 @@ __device__ __forceinline__ int swz(int row, int c) {
     return c ^ ((row / (16 / CPR)) & (CPR - 1));
 }
 
-template <typename CT, int BM, int BN, int LBK, int AMODE, bool A_F32>
+template <typename CT, int BM, int BN, int LBK, int AMODE>
 __global__ __launch_bounds__(NT) void gemm_lowp_kernel(cmt_gemm_args a) {
     typedef typename mfma_traits<CT>::frag frag;
     constexpr int CPR = LBK / 8;               // 16-byte chunks per LDS row
@@ -188,7 +196,7 @@ __global__ __launch_bounds__(NT) void gemm_lowp_kernel(cmt_gemm_args a) {
     const int m0 = blockIdx.y * BM;
     const int z = blockIdx.z;
 
-    const char* Ab = (const char*)a.A + (int64_t)z * a.a_bstride * (A_F32 ? 4 : 2);
+    const char* Ab = (const char*)a.A + (int64_t)z * a.a_bstride * 4;
     const CT* Wb = (const CT*)a.W + (int64_t)z * a.w_bstride;
     const bool use_a2 = (AMODE == CMT_A_ROWS) && a.A2 != nullptr && n0 < a.a2_cols;
 
@@ -209,7 +217,7 @@ __global__ __launch_bounds__(NT) void gemm_lowp_kernel(cmt_gemm_args a) {
             if (off < 0) {
 #pragma unroll
                 for (int j = 0; j < 8; ++j) areg[i][j] = (CT)0.f;
-            } else if (A_F32) {
+            } else {
                 const float* p = (const float*)Ab + off;
                 f32x4 v0 = *(const f32x4*)p;
                 f32x4 v1 = *(const f32x4*)(p + 4);
@@ -223,8 +231,6 @@ __global__ __launch_bounds__(NT) void gemm_lowp_kernel(cmt_gemm_args a) {
                     areg[i][j] = (CT)v0[j];
                     areg[i][j + 4] = (CT)v1[j];
                 }
-            } else {
-                areg[i] = *(const frag*)((const CT*)Ab + off);
             }
         }
 #pragma unroll
@@ -417,13 +423,6 @@ __global__ __launch_bounds__(NT) void gemm_f32_kernel(cmt_gemm_args a) {
 // ---------------------------------------------------------------------------
 __device__ __attribute__((aligned(64))) char g_zero_page[256];
 
-typedef const __attribute__((address_space(1))) void* gaddr_t;
-typedef __attribute__((address_space(3))) void* laddr_t;
-
-__device__ __forceinline__ void glds16(const void* src, void* lds) {
-    __builtin_amdgcn_global_load_lds((gaddr_t)src, (laddr_t)lds, 16, 0, 0);
-}
-
 template <int PER, int S>
 __device__ __forceinline__ void wait_tiles(int inflight) {
     if (S > 3 && inflight >= 3) wait_vm_lgkm<(S > 3 ? 3 * PER : 0)>();
@@ -432,7 +431,6 @@ __device__ __forceinline__ void wait_tiles(int inflight) {
     else wait_vm_lgkm<0>();
 }
 
-template <typename CT>
 __device__ __forceinline__ void store4(void* C, int64_t idx, int dt, f32x4 v) {
     if (dt == CMT_F32) {
         *(f32x4*)((float*)C + idx) = v;
@@ -467,13 +465,65 @@ __device__ __forceinline__ f32x4 load4(const void* p, int64_t idx, int dt, int l
     return f32x4{(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
 }
 
+// acc[tm][tn] += b[tn] . a[tm] for every 32 x 32 tile of a wave (W rows on the MFMA's A operand)
+template <typename CT, int TM, int TN>
+__device__ __forceinline__ void mma_tiles(f32x16 (&acc)[TM][TN], const typename mfma_traits<CT>::frag (&b)[TN],
+                                          const typename mfma_traits<CT>::frag (&a)[TM]) {
+#pragma unroll
+    for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+        for (int tn = 0; tn < TN; ++tn) acc[tm][tn] = mfma_traits<CT>::mma(b[tn], a[tm], acc[tm][tn]);
+}
+
+// 16-byte fragment of row r, logical chunk c, of an LDS-DMA tile with ROWB-byte rows (64 | 128):
+// undoes the chunk permutation the copy applied to its source address
+template <int ROWB, typename F>
+__device__ __forceinline__ F ld_frag(const char* tile, int r, int c) {
+    return *(const F*)(tile + r * ROWB + ((c ^ ((r >> (ROWB == 128 ? 1 : 2)) & (ROWB / 16 - 1))) << 4));
+}
+
+// The implicit convs' walk over the taps (3x3, 1D k = 3): the stages arrive in increasing k order
+// and a tap spans (tap width) / KS stages, so each row's gathered offset is recomputed once per
+// tap (9 or 3 times per tile), not per stage (no integer division in the k loop).
+template <int AMODE, int KS, int APER>
+struct TapCursor {
+    int tap = -1, cin = 0;   // current tap; first column of the current stage inside it
+    int64_t off[APER];       // element offset of copy i's gathered row at this tap, -1: padding
+    // moves to stage kt; row(i) = tile row of this thread's copy i
+    template <typename Row>
+    __device__ __forceinline__ void next(const cmt_gemm_args& a, const RowInfo (&ri)[APER], int m0, Row row, int tapw,
+                                         int kt) {
+        if (tap < 0) {
+            const int k0 = kt * KS;
+            tap = k0 / tapw;
+            cin = k0 - tap * tapw;
+        } else if ((cin += KS) == tapw) {
+            cin = 0;
+            ++tap;
+        } else {
+            return;
+        }
+#pragma unroll
+        for (int i = 0; i < APER; ++i) off[i] = a_offset<AMODE>(a, ri[i], m0 + row(i), tap * tapw);
+    }
+};
+
+// One 1 KB wave copy of a stage and, X3, its lo plane's (lo elements further in the source, plane
+// bytes further in LDS); PAD: a null src (a padding row of the gather) reads the zero page.
+template <bool X3, bool PAD, typename CT>
+__device__ __forceinline__ void issue_planes(const CT* src, int lo, char* dst, int plane) {
+    const bool pad = PAD && src == nullptr;
+    glds16(pad ? (const void*)g_zero_page : (const void*)src, dst);
+    if constexpr (X3) glds16(pad ? (const void*)g_zero_page : (const void*)(src + lo), dst + plane);
+}
+
 // Main loop of the LDS-DMA GEMM for one BM x BN output tile (4 waves in a
 // WM x (4/WM) grid; each wave owns (BM/WM) x (BN*WM/4) as TM x TN 32x32 MFMA
 // tiles).  Accumulators are in the swapped C^T layout: lane = output row.
 //
 // X3 (A and W both CMT_F16P, cmt_hip.h): every stage carries four tiles --
 // A_hi, A_lo, W_hi, W_lo of the same 64 k -- and each k step runs the three
-// products A_hi W_hi + A_lo W_hi + A_hi W_lo on them, so one staged byte feeds
+// products W_hi A_lo + W_lo A_hi + W_hi A_hi on them, so one staged byte feeds
 // 3/2 MFMAs instead of one (a stage per product re-streams A_hi and W_hi) and
 // the k loop is K / 64 steps long, not 3K / 64.  The A row's lo half starts at
 // its logical width (K for rows, the channel count for the implicit convs),
@@ -524,36 +574,16 @@ struct DmaTile {
             bsrc[i] = Wb + (int64_t)(n0 + row) * a.ldw + (ch ^ ((row >> 1) & 7)) * 8;
         }
 
-        // implicit convs (3x3, 1D k = 3): the stages arrive in increasing k order and a tap spans
-        // (tap width) / 64 stages, so each row's gathered offset is recomputed once per tap
-        // (9 or 3 times per tile), not per stage (no integer division in the k loop)
-        const int tapw = AMODE == CMT_A_CONV3X3 ? a.conv_c : (AMODE == CMT_A_CONV1D3 ? a.K / 3 : a.K);
-        const int ntaps = AMODE == CMT_A_CONV3X3 ? 9 : (AMODE == CMT_A_CONV1D3 ? 3 : 1);
-        (void)ntaps;
+        const int tapw = tap_width(a, AMODE);
         const int a_lo = AMODE == CMT_A_ROWS ? a.K : tapw;    // element offset of an A row's lo half
-        int ctap = -1, ccin = 0;
-        int64_t toff[APER];
+        TapCursor<AMODE, KS, APER> tc;
         auto issue = [&](int buf, int kt) {
             char* sb = smem + buf * STAGE;
             int ka, kw;   // A / W column of this stage's first k
             if constexpr (AMODE != CMT_A_ROWS) {
-                // the same per-tap cache for the 1D k = 3 conv (taps of K / 3 columns)
-                if (ctap < 0) {
-                    const int k0 = kt * KS;
-                    ctap = k0 / tapw;
-                    ccin = k0 - ctap * tapw;
-#pragma unroll
-                    for (int i = 0; i < APER; ++i)
-                        toff[i] = a_offset<AMODE>(a, ri[i], m0 + (4 * i + wave) * 8 + (lane >> 3), ctap * tapw);
-                } else if ((ccin += KS) == tapw) {
-                    ccin = 0;
-                    ++ctap;
-#pragma unroll
-                    for (int i = 0; i < APER; ++i)
-                        toff[i] = a_offset<AMODE>(a, ri[i], m0 + (4 * i + wave) * 8 + (lane >> 3), ctap * tapw);
-                }
-                ka = ccin;
-                kw = ctap * tapw + ccin;
+                tc.next(a, ri, m0, [&](int i) { return (4 * i + wave) * 8 + (lane >> 3); }, tapw, kt);
+                ka = tc.cin;
+                kw = tc.tap * tapw + tc.cin;
             } else {
                 ka = kw = kt * KS;
             }
@@ -563,17 +593,12 @@ struct DmaTile {
                 if (AMODE == CMT_A_ROWS)
                     src = asrc[i] + ka;
                 else
-                    src = toff[i] < 0 ? nullptr : (const CT*)Ab + toff[i] + ka + acs[i];
-                glds16(src ? (const void*)src : (const void*)g_zero_page, sb + (4 * i + wave) * 1024);
-                if constexpr (X3)
-                    glds16(src ? (const void*)(src + a_lo) : (const void*)g_zero_page,
-                           sb + A_BYTES + (4 * i + wave) * 1024);
+                    src = tc.off[i] < 0 ? nullptr : (const CT*)Ab + tc.off[i] + ka + acs[i];
+                issue_planes<X3, true>(src, a_lo, sb + (4 * i + wave) * 1024, A_BYTES);
             }
 #pragma unroll
-            for (int i = 0; i < BPER; ++i) {
-                glds16(bsrc[i] + kw, sb + NPL * A_BYTES + (4 * i + wave) * 1024);
-                if constexpr (X3) glds16(bsrc[i] + kw + a.K, sb + NPL * A_BYTES + B_BYTES + (4 * i + wave) * 1024);
-            }
+            for (int i = 0; i < BPER; ++i)
+                issue_planes<X3, false>(bsrc[i] + kw, a.K, sb + NPL * A_BYTES + (4 * i + wave) * 1024, B_BYTES);
         };
 
 #pragma unroll
@@ -603,41 +628,22 @@ struct DmaTile {
                 frag af[TM], bfr[TN];
                 const int kc = 2 * ks + lh;
 #pragma unroll
-                for (int tm = 0; tm < TM; ++tm) {
-                    const int r = wm * (BM / WM) + tm * 32 + lr;
-                    af[tm] = *(const frag*)(As + r * 128 + ((kc ^ ((r >> 1) & 7)) << 4));
-                }
+                for (int tm = 0; tm < TM; ++tm) af[tm] = ld_frag<128, frag>(As, wm * (BM / WM) + tm * 32 + lr, kc);
 #pragma unroll
-                for (int tn = 0; tn < TN; ++tn) {
-                    const int r = wn * (BN / WN) + tn * 32 + lr;
-                    bfr[tn] = *(const frag*)(Bs + r * 128 + ((kc ^ ((r >> 1) & 7)) << 4));
-                }
+                for (int tn = 0; tn < TN; ++tn) bfr[tn] = ld_frag<128, frag>(Bs, wn * (BN / WN) + tn * 32 + lr, kc);
                 if constexpr (X3) {
                     frag al[TM], bl[TN];
 #pragma unroll
-                    for (int tm = 0; tm < TM; ++tm) {
-                        const int r = wm * (BM / WM) + tm * 32 + lr;
-                        al[tm] = *(const frag*)(As + A_BYTES + r * 128 + ((kc ^ ((r >> 1) & 7)) << 4));
-                    }
+                    for (int tm = 0; tm < TM; ++tm)
+                        al[tm] = ld_frag<128, frag>(As + A_BYTES, wm * (BM / WM) + tm * 32 + lr, kc);
 #pragma unroll
-                    for (int tn = 0; tn < TN; ++tn) {
-                        const int r = wn * (BN / WN) + tn * 32 + lr;
-                        bl[tn] = *(const frag*)(Bs + B_BYTES + r * 128 + ((kc ^ ((r >> 1) & 7)) << 4));
-                    }
+                    for (int tn = 0; tn < TN; ++tn)
+                        bl[tn] = ld_frag<128, frag>(Bs + B_BYTES, wn * (BN / WN) + tn * 32 + lr, kc);
                     // the two small products first, then the hi product, per accumulator
-#pragma unroll
-                    for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-                        for (int tn = 0; tn < TN; ++tn) acc[tm][tn] = mfma_traits<CT>::mma(bfr[tn], al[tm], acc[tm][tn]);
-#pragma unroll
-                    for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-                        for (int tn = 0; tn < TN; ++tn) acc[tm][tn] = mfma_traits<CT>::mma(bl[tn], af[tm], acc[tm][tn]);
+                    mma_tiles<CT>(acc, bfr, al);
+                    mma_tiles<CT>(acc, bl, af);
                 }
-#pragma unroll
-                for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-                    for (int tn = 0; tn < TN; ++tn) acc[tm][tn] = mfma_traits<CT>::mma(bfr[tn], af[tm], acc[tm][tn]);
+                mma_tiles<CT>(acc, bfr, af);
             }
         }
     }
@@ -778,7 +784,7 @@ __global__ __launch_bounds__(NT) void gemm_dma_kernel(cmt_gemm_args a, int tiles
 #pragma unroll
                         for (int j = 0; j < 4; ++j) v[j] -= (float)(pair_t)v[j];   // lo = f16(x - hi)
                     }
-                    store4<CT>(dst, 0, a.c_dtype == CMT_F16P ? CMT_F16 : a.c_dtype, v);
+                    store4(dst, 0, a.c_dtype == CMT_F16P ? CMT_F16 : a.c_dtype, v);
                 }
         }
         barrier_mem();
@@ -970,7 +976,7 @@ __device__ __forceinline__ void x3_epilogue(const cmt_gemm_args& a, f32x16 (&acc
 #pragma unroll
                         for (int j = 0; j < 4; ++j) v[j] -= (float)(pair_t)v[j];   // lo = f16(x - hi)
                     }
-                    store4<pair_t>(dst, 0, a.c_dtype == CMT_F16P ? CMT_F16 : a.c_dtype, v);
+                    store4(dst, 0, a.c_dtype == CMT_F16P ? CMT_F16 : a.c_dtype, v);
                 }
         }
         barrier_mem();
@@ -989,8 +995,8 @@ __device__ __forceinline__ void x3_epilogue(const cmt_gemm_args& a, f32x16 (&acc
 
 // ---------------------------------------------------------------------------
 // Split (CMT_F16P) GEMM for the large problems of the 'ref' policy (shared_conv,
-// the BEV / RV position MLPs): BM x 128 tiles (BM 256 or 128), 8 waves, 32-deep
-// k stages in an S-slot LDS-DMA ring.
+// the BEV / RV position MLPs): 256 x 128 tiles, 8 waves in a 4 x 2 grid, 32-deep
+// k stages in a 3-slot LDS-DMA ring.
 //
 // Each stage carries A_hi, A_lo, W_hi, W_lo of 32 k (64-byte LDS rows; 16-byte
 // chunks XOR-swizzled by (row >> 2) & 3 on the source address, so the 16-lane
@@ -998,17 +1004,17 @@ __device__ __forceinline__ void x3_epilogue(const cmt_gemm_args& a, f32x16 (&acc
 // three products W_hi A_lo + W_lo A_hi + W_hi A_hi in the order of the 128 x 128
 // DmaTile<..., X3> -- the same fp32 accumulation sequence, so the two kernels
 // give bit-identical outputs.  Against that tile (2 stages of 64 k, 4 waves, one
-// wave per SIMD) a BM = 256 tile stages 1.33x the MFMA work per byte and keeps
+// wave per SIMD) this one stages 1.33x the MFMA work per byte and keeps
 // 2 stages in flight behind the one being read (the 64 KB fills of the 2-stage
 // ring were the pace: ~36 GB/s per CU against 88 for the MFMA rate).
 // Row-mode C only (fp32, f16 / bf16 or pair), bias / ReLU / residual, batch.
 // ---------------------------------------------------------------------------
-template <int BM, int AMODE>
+template <int AMODE>
 struct X3Tile {
-    static constexpr int BN = 128, KS = 32, ROWB = KS * 2, NTX = 512;
+    static constexpr int BM = 256, BN = 128, KS = 32, ROWB = KS * 2, NTX = 512;
     static constexpr int A_BYTES = BM * ROWB, B_BYTES = BN * ROWB;
     static constexpr int STAGE = 2 * (A_BYTES + B_BYTES);
-    static constexpr int S = BM == 256 ? 3 : 4;
+    static constexpr int S = 3;
     static constexpr int SMEM = S * STAGE;
     static constexpr int APER = A_BYTES / 1024 / 8, BPER = B_BYTES / 1024 / 8;   // wave copies per plane
     static constexpr int PER = 2 * (APER + BPER);                               // glds per thread per stage
@@ -1018,11 +1024,11 @@ struct X3Tile {
     static_assert(SMEM >= BM * BN * 4 && SMEM <= 160 * 1024, "x3 LDS");
 };
 
-template <int BM, int AMODE>
+template <int AMODE>
 __global__ __launch_bounds__(512) void gemm_x3_kernel(cmt_gemm_args a, int tiles_m, int tiles_n) {
-    typedef X3Tile<BM, AMODE> T;
+    typedef X3Tile<AMODE> T;
     typedef pair8_t frag;
-    constexpr int BN = T::BN, KS = T::KS, S = T::S, TM = T::TM, TN = T::TN, PER = T::PER;
+    constexpr int BM = T::BM, BN = T::BN, KS = T::KS, S = T::S, TM = T::TM, TN = T::TN, PER = T::PER;
     __shared__ __attribute__((aligned(16))) char smem[T::SMEM];
     int z, mt, nt;
     xcd_tile(tiles_m, tiles_n, a.batch, z, mt, nt);
@@ -1052,31 +1058,16 @@ __global__ __launch_bounds__(512) void gemm_x3_kernel(cmt_gemm_args a, int tiles
         const int row = (8 * i + wave) * 16 + (lane >> 2);
         bsrc[i] = Wb + (int64_t)(n0 + row) * a.ldw + (ch ^ ((row >> 2) & 3)) * 8;
     }
-    const int tapw = AMODE == CMT_A_CONV3X3 ? a.conv_c : (AMODE == CMT_A_CONV1D3 ? a.K / 3 : a.K);
+    const int tapw = tap_width(a, AMODE);
     const int a_lo = AMODE == CMT_A_ROWS ? a.K : tapw;     // element offset of an A row's lo half
-    int ctap = -1, ccin = 0;
-    int64_t toff[T::APER];
+    TapCursor<AMODE, KS, T::APER> tc;
     auto issue = [&](int buf, int kt) {
         char* sb = smem + buf * T::STAGE;
         int ka, kw;
         if constexpr (AMODE != CMT_A_ROWS) {
-            // a tap spans tapw / 32 stages: gathered row offsets once per tap
-            if (ctap < 0) {
-                const int k0 = kt * KS;
-                ctap = k0 / tapw;
-                ccin = k0 - ctap * tapw;
-#pragma unroll
-                for (int i = 0; i < T::APER; ++i)
-                    toff[i] = a_offset<AMODE>(a, ri[i], m0 + (8 * i + wave) * 16 + (lane >> 2), ctap * tapw);
-            } else if ((ccin += KS) == tapw) {
-                ccin = 0;
-                ++ctap;
-#pragma unroll
-                for (int i = 0; i < T::APER; ++i)
-                    toff[i] = a_offset<AMODE>(a, ri[i], m0 + (8 * i + wave) * 16 + (lane >> 2), ctap * tapw);
-            }
-            ka = ccin;
-            kw = ctap * tapw + ccin;
+            tc.next(a, ri, m0, [&](int i) { return (8 * i + wave) * 16 + (lane >> 2); }, tapw, kt);
+            ka = tc.cin;
+            kw = tc.tap * tapw + tc.cin;
         } else {
             ka = kw = kt * KS;
         }
@@ -1084,15 +1075,12 @@ __global__ __launch_bounds__(512) void gemm_x3_kernel(cmt_gemm_args a, int tiles
         for (int i = 0; i < T::APER; ++i) {
             const pair_t* src;
             if (AMODE == CMT_A_ROWS) src = asrc[i] + ka;
-            else src = toff[i] < 0 ? nullptr : Ab + toff[i] + ka + acs[i];
-            glds16(src ? (const void*)src : (const void*)g_zero_page, sb + (8 * i + wave) * 1024);
-            glds16(src ? (const void*)(src + a_lo) : (const void*)g_zero_page, sb + T::A_BYTES + (8 * i + wave) * 1024);
+            else src = tc.off[i] < 0 ? nullptr : Ab + tc.off[i] + ka + acs[i];
+            issue_planes<true, true>(src, a_lo, sb + (8 * i + wave) * 1024, T::A_BYTES);
         }
 #pragma unroll
-        for (int i = 0; i < T::BPER; ++i) {
-            glds16(bsrc[i] + kw, sb + 2 * T::A_BYTES + (8 * i + wave) * 1024);
-            glds16(bsrc[i] + kw + a.K, sb + 2 * T::A_BYTES + T::B_BYTES + (8 * i + wave) * 1024);
-        }
+        for (int i = 0; i < T::BPER; ++i)
+            issue_planes<true, false>(bsrc[i] + kw, a.K, sb + 2 * T::A_BYTES + (8 * i + wave) * 1024, T::B_BYTES);
     };
 
     f32x16 acc[TM][TN];
@@ -1122,41 +1110,29 @@ __global__ __launch_bounds__(512) void gemm_x3_kernel(cmt_gemm_args a, int tiles
 #pragma unroll
             for (int tm = 0; tm < TM; ++tm) {
                 const int r = wm * 64 + tm * 32 + lr;
-                const int o = r * T::ROWB + ((kc ^ ((r >> 2) & 3)) << 4);
-                af[tm] = *(const frag*)(As + o);
-                al[tm] = *(const frag*)(As + T::A_BYTES + o);
+                af[tm] = ld_frag<T::ROWB, frag>(As, r, kc);
+                al[tm] = ld_frag<T::ROWB, frag>(As + T::A_BYTES, r, kc);
             }
 #pragma unroll
             for (int tn = 0; tn < TN; ++tn) {
                 const int r = wn * (BN / T::WNW) + tn * 32 + lr;
-                const int o = r * T::ROWB + ((kc ^ ((r >> 2) & 3)) << 4);
-                bh[tn] = *(const frag*)(Bs + o);
-                bl[tn] = *(const frag*)(Bs + T::B_BYTES + o);
+                bh[tn] = ld_frag<T::ROWB, frag>(Bs, r, kc);
+                bl[tn] = ld_frag<T::ROWB, frag>(Bs + T::B_BYTES, r, kc);
             }
-#pragma unroll
-            for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-                for (int tn = 0; tn < TN; ++tn) acc[tm][tn] = mfma_traits<pair_t>::mma(bh[tn], al[tm], acc[tm][tn]);
-#pragma unroll
-            for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-                for (int tn = 0; tn < TN; ++tn) acc[tm][tn] = mfma_traits<pair_t>::mma(bl[tn], af[tm], acc[tm][tn]);
-#pragma unroll
-            for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-                for (int tn = 0; tn < TN; ++tn) acc[tm][tn] = mfma_traits<pair_t>::mma(bh[tn], af[tm], acc[tm][tn]);
+            mma_tiles<pair_t>(acc, bh, al);
+            mma_tiles<pair_t>(acc, bl, af);
+            mma_tiles<pair_t>(acc, bh, af);
         }
     }
 
     x3_epilogue<BM, TM, TN, T::WNW, T::NTX>(a, acc, smem, m0, n0, z, wm, wn);
 }
 
-template <int BM>
 int launch_x3(const cmt_gemm_args& a, hipStream_t s) {
-    const int tm = cdiv(a.M, BM), tn = a.N / 128;
+    const int tm = cdiv(a.M, 256), tn = a.N / 128;
     const unsigned nwg = (unsigned)((int64_t)tm * tn * a.batch);
-    if (a.a_mode == CMT_A_CONV3X3) gemm_x3_kernel<BM, CMT_A_CONV3X3><<<nwg, 512, 0, s>>>(a, tm, tn);
-    else gemm_x3_kernel<BM, CMT_A_ROWS><<<nwg, 512, 0, s>>>(a, tm, tn);
+    if (a.a_mode == CMT_A_CONV3X3) gemm_x3_kernel<CMT_A_CONV3X3><<<nwg, 512, 0, s>>>(a, tm, tn);
+    else gemm_x3_kernel<CMT_A_ROWS><<<nwg, 512, 0, s>>>(a, tm, tn);
     return cmt_check_launch("cmt_gemm");
 }
 
@@ -1212,19 +1188,12 @@ __device__ __forceinline__ void vm_wait() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-// VAR bits: 1 = the younger half of the workgroup (waves 4-7) at priority 1 for the whole loop
-// (cdna_hip_programming.md T5, static form); 2 = s_setprio(1) around every tap's MFMA cluster;
-// 16 = the halo loads as inline asm, waited for by a counted vmcnt of our own: hipcc's own wait
-// for a VGPR-destination load beside the W ring's LDS-DMA is vmcnt(0) (cdna_hip_programming.md
-// 'Three .s-level traps' (b)), which drained the W ring at the end of every chunk;
-// 4 / 8 = diagnostics only (no halo loads / no W refills: wrong results, for timing those streams).
 // X3 = false (round 6): one MFMA pass in the compute dtype E (f16 / bf16: the 'fp16' / 'bf16' policies'
 // shared_conv, W [N][K] in E) on the same halo / W layouts -- the lo halves are neither stored nor read
-template <int VAR, typename E = pair_t, bool X3 = true>
+template <typename E = pair_t, bool X3 = true>
 __global__ __launch_bounds__(512) void conv_halo_x3_kernel(cmt_gemm_args a, int tiles_m, int tiles_n) {
     typedef HaloConv T;
     typedef typename mfma_traits<E>::frag frag;
-    constexpr bool AH = (VAR & 16) != 0;
     constexpr int BM = T::BM, S = T::S, TM = T::TM, TN = T::TN, UPT = T::UPT;
     constexpr int HLOADS = UPT * 8;                           // halo loads per thread per chunk
     __shared__ __attribute__((aligned(16))) char smem[T::SMEM];
@@ -1272,47 +1241,18 @@ __global__ __launch_bounds__(512) void conv_halo_x3_kernel(cmt_gemm_args a, int 
             // read the zero page
             const float* src = u_ok[i] ? Xc + u_src[i] : (const float*)g_zero_page;
             const int es = u_ok[i] ? HW : 0;
-            if constexpr (VAR & 4) {
 #pragma unroll
-                for (int e = 0; e < 8; ++e) hv[i][e] = (float)(es + e) * 1e-3f;
-            } else if constexpr (AH) {
-                // SGPR base (the chunk's channel block) + a 32-bit VGPR byte offset per load;
-                // padding units load pixel 0 of the channel and are zeroed after the wait
-                uint32_t vo = (uint32_t)(u_ok[i] ? u_src[i] : 0) * 4u;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    asm volatile("global_load_dword %0, %1, %2" : "=v"(hv[i][e]) : "v"(vo), "s"(Xc) : "memory");
-                    vo += (uint32_t)HW * 4u;
-                }
-            } else {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) hv[i][e] = src[e * es];
-            }
+            for (int e = 0; e < 8; ++e) hv[i][e] = src[e * es];
         }
     };
-    auto store_halo = [&](int buf, auto first) {
+    auto store_halo = [&](int buf) {
         char* hb = smem + buf * T::HALO;
-        if constexpr (AH && !(VAR & 4)) {
-            // the halo loads went out at the chunk's first step; two W stages (3 DMAs each) since
-            // (none before chunk 0's, in the prologue): wait for the loads, naming every
-            // destination so nothing reads them before
-            asm volatile("s_waitcnt vmcnt(%24)"
-                         : "+v"(hv[0][0]), "+v"(hv[0][1]), "+v"(hv[0][2]), "+v"(hv[0][3]), "+v"(hv[0][4]),
-                           "+v"(hv[0][5]), "+v"(hv[0][6]), "+v"(hv[0][7]), "+v"(hv[1][0]), "+v"(hv[1][1]),
-                           "+v"(hv[1][2]), "+v"(hv[1][3]), "+v"(hv[1][4]), "+v"(hv[1][5]), "+v"(hv[1][6]),
-                           "+v"(hv[1][7]), "+v"(hv[2][0]), "+v"(hv[2][1]), "+v"(hv[2][2]), "+v"(hv[2][3]),
-                           "+v"(hv[2][4]), "+v"(hv[2][5]), "+v"(hv[2][6]), "+v"(hv[2][7])
-                         : "n"(decltype(first)::value ? 0 : 6)
-                         : "memory");
-            static_assert(!AH || UPT == 3, "the wait statement names three units");
-        } else {
-            // pin the halo registers here: without this the split arithmetic below (no memory
-            // dependence) is hoisted right behind the loads and waits for them there
+        // pin the halo registers here: without this the split arithmetic below (no memory
+        // dependence) is hoisted right behind the loads and waits for them there
 #pragma unroll
-            for (int i = 0; i < UPT; ++i)
-                asm volatile("" : "+v"(hv[i][0]), "+v"(hv[i][1]), "+v"(hv[i][2]), "+v"(hv[i][3]), "+v"(hv[i][4]),
-                             "+v"(hv[i][5]), "+v"(hv[i][6]), "+v"(hv[i][7]));
-        }
+        for (int i = 0; i < UPT; ++i)
+            asm volatile("" : "+v"(hv[i][0]), "+v"(hv[i][1]), "+v"(hv[i][2]), "+v"(hv[i][3]), "+v"(hv[i][4]),
+                         "+v"(hv[i][5]), "+v"(hv[i][6]), "+v"(hv[i][7]));
 #pragma unroll
         for (int i = 0; i < UPT; ++i) {
             if (!u_on[i]) continue;
@@ -1320,7 +1260,7 @@ __global__ __launch_bounds__(512) void conv_halo_x3_kernel(cmt_gemm_args a, int 
             pair8_t lo;
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                const float x = AH && !u_ok[i] ? 0.f : hv[i][e];
+                const float x = hv[i][e];
                 hi[e] = (E)x;
                 if constexpr (X3) lo[e] = (pair_t)(x - (float)hi[e]);
             }
@@ -1337,9 +1277,6 @@ __global__ __launch_bounds__(512) void conv_halo_x3_kernel(cmt_gemm_args a, int 
     auto issue_w = [&](int g) {   // step g = (chunk g / 3, kernel row g % 3): its three taps
         const int c = g / 3, dy = g - 3 * (g / 3);
         char* slot = smem + 2 * T::HALO + (g % S) * T::WSLOT + wave * 1024;
-        if constexpr (VAR & 8) {
-            if (g >= S) return;
-        }
 #pragma unroll
         for (int dx = 0; dx < 3; ++dx) glds16(wsrc + (3 * dy + dx) * Cin + c * T::CK, slot + dx * T::WTAP);
     };
@@ -1371,7 +1308,7 @@ __global__ __launch_bounds__(512) void conv_halo_x3_kernel(cmt_gemm_args a, int 
 
     // prologue: chunk 0's halo, W of steps 0 .. S-1
     load_halo(0);
-    store_halo(0, std::true_type{});
+    store_halo(0);
 #pragma unroll
     for (int g = 0; g < S; ++g) issue_w(g);
 
@@ -1381,8 +1318,6 @@ __global__ __launch_bounds__(512) void conv_halo_x3_kernel(cmt_gemm_args a, int 
     // the issue stream is the same for every chunk and each wait below counts the ops issued
     // after W(g) exactly.
     constexpr int WOPS = 3;                                   // DMAs per thread per W stage
-    if constexpr (VAR & 1)
-        if (__builtin_amdgcn_readfirstlane(threadIdx.x) >= 256) __builtin_amdgcn_s_setprio(1);
     for (int c = 0; c < nchunks; ++c) {
         const char* Hs = smem + (c & 1) * T::HALO;
 #pragma unroll
@@ -1418,30 +1353,16 @@ __global__ __launch_bounds__(512) void conv_halo_x3_kernel(cmt_gemm_args a, int 
                     bh[tn] = *(const frag*)(Ws + dx * T::WTAP + woff[tn]);
                     if constexpr (X3) bl[tn] = *(const frag*)(Ws + dx * T::WTAP + (woff[tn] ^ (2 << 4)));
                 }
-                if constexpr (VAR & 2) __builtin_amdgcn_s_setprio(1);
                 if constexpr (X3) {
-#pragma unroll
-                    for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-                        for (int tn = 0; tn < TN; ++tn)
-                            acc[tm][tn] = mfma_traits<E>::mma(bh[tn], al[tm], acc[tm][tn]);
-#pragma unroll
-                    for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-                        for (int tn = 0; tn < TN; ++tn)
-                            acc[tm][tn] = mfma_traits<E>::mma(bl[tn], af[tm], acc[tm][tn]);
+                    mma_tiles<E>(acc, bh, al);
+                    mma_tiles<E>(acc, bl, af);
                 }
-#pragma unroll
-                for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-                    for (int tn = 0; tn < TN; ++tn)
-                        acc[tm][tn] = mfma_traits<E>::mma(bh[tn], af[tm], acc[tm][tn]);
-                if constexpr (VAR & 2) __builtin_amdgcn_s_setprio(0);
+                mma_tiles<E>(acc, bh, af);
             }
         }
         // chunk c + 1's halo into the other buffer (its last readers, chunk c - 1's taps, are
         // all past this chunk's first barrier); the next step's barrier publishes it
-        store_halo((c + 1) & 1, std::false_type{});
+        store_halo((c + 1) & 1);
     }
     // the dummy W refills and the last halo loads are still in flight: drain them before
     // the epilogue reuses the LDS
@@ -1452,9 +1373,9 @@ __global__ __launch_bounds__(512) void conv_halo_x3_kernel(cmt_gemm_args a, int 
 int launch_conv_halo(const cmt_gemm_args& a, hipStream_t s) {
     const int tm = cdiv(a.conv_h * a.conv_w, HaloConv::BM), tn = a.N / HaloConv::BN;
     const unsigned nwg = (unsigned)((int64_t)tm * tn * a.batch);
-    if (a.w_dtype == CMT_F16P) conv_halo_x3_kernel<CMT_CONV_VAR><<<nwg, HaloConv::NTX, 0, s>>>(a, tm, tn);
-    else if (a.w_dtype == CMT_F16) conv_halo_x3_kernel<0, f16_t, false><<<nwg, HaloConv::NTX, 0, s>>>(a, tm, tn);
-    else conv_halo_x3_kernel<0, bf16_t, false><<<nwg, HaloConv::NTX, 0, s>>>(a, tm, tn);
+    if (a.w_dtype == CMT_F16P) conv_halo_x3_kernel<><<<nwg, HaloConv::NTX, 0, s>>>(a, tm, tn);
+    else if (a.w_dtype == CMT_F16) conv_halo_x3_kernel<f16_t, false><<<nwg, HaloConv::NTX, 0, s>>>(a, tm, tn);
+    else conv_halo_x3_kernel<bf16_t, false><<<nwg, HaloConv::NTX, 0, s>>>(a, tm, tn);
     return cmt_check_launch("cmt_gemm");
 }
 
@@ -1573,8 +1494,8 @@ __global__ __launch_bounds__(NT) void gemm_ln_kernel(cmt_gemm_args a, cmt_ln_arg
             if (ln.Yl) store_pair4((pair_t*)ln.Yl + (int64_t)m * ln.ldyl, C, n, o);
             if (ln.Yp) store_pair4((pair_t*)ln.Yp + (int64_t)m * ln.ldyp, C, n, o + pv[t]);
         } else {
-            if (ln.Yl) store4<CT>(ln.Yl, (int64_t)m * ln.ldyl + n, ln.lowp_dtype, o);
-            if (ln.Yp) store4<CT>(ln.Yp, (int64_t)m * ln.ldyp + n, ln.lowp_dtype, o + pv[t]);
+            if (ln.Yl) store4(ln.Yl, (int64_t)m * ln.ldyl + n, ln.lowp_dtype, o);
+            if (ln.Yp) store4(ln.Yp, (int64_t)m * ln.ldyp + n, ln.lowp_dtype, o + pv[t]);
         }
         if (ln.Y2) *(f32x4*)(ln.Y2 + (int64_t)m * ln.ldy2 + n) = y2[t];
     }
@@ -1584,8 +1505,8 @@ template <int BM, int BN, int S, int AMODE>
 int launch_dma_mode(const cmt_gemm_args& a, hipStream_t s) {
     const int tm = cdiv(a.M, BM), tn = a.N / BN;
     const int64_t nwg = (int64_t)tm * tn * a.batch * (a.k_splits > 1 ? a.k_splits : 1);
-    // the pair stages carry four tiles: 128 x 128 keeps 2 of them (128 KB), the others 3 or 2
-    constexpr int SP = BM * BN >= 128 * 128 ? 2 : (BM * BN >= 128 * 64 ? 2 : 3);
+    // the pair stages carry four tiles: the 128-row tiles keep 2 of them (128 / 96 KB), 64 x 64 keeps 3
+    constexpr int SP = BM >= 128 ? 2 : 3;
     if (a.w_dtype == CMT_F16P) gemm_dma_kernel<pair_t, BM, BN, SP, AMODE, true><<<(unsigned)nwg, NT, 0, s>>>(a, tm, tn);
     else if (a.w_dtype == CMT_BF16) gemm_dma_kernel<bf16_t, BM, BN, S, AMODE><<<(unsigned)nwg, NT, 0, s>>>(a, tm, tn);
     else gemm_dma_kernel<f16_t, BM, BN, S, AMODE><<<(unsigned)nwg, NT, 0, s>>>(a, tm, tn);
@@ -1603,19 +1524,8 @@ int launch_dma(const cmt_gemm_args& a, hipStream_t s) {
 
 template <int BM, int BN, int LBK, int AMODE>
 void launch_lowp(const cmt_gemm_args& a, dim3 grid, hipStream_t s) {
-    if constexpr (AMODE == CMT_A_CONV3X3) {
-        // the conv gather reads NHWC rows already in the compute dtype
-        if (a.w_dtype == CMT_BF16) gemm_lowp_kernel<bf16_t, BM, BN, LBK, AMODE, false><<<grid, NT, 0, s>>>(a);
-        else gemm_lowp_kernel<f16_t, BM, BN, LBK, AMODE, false><<<grid, NT, 0, s>>>(a);
-    } else {
-        if (a.w_dtype == CMT_BF16) {
-            if (a.a_dtype == CMT_F32) gemm_lowp_kernel<bf16_t, BM, BN, LBK, AMODE, true><<<grid, NT, 0, s>>>(a);
-            else gemm_lowp_kernel<bf16_t, BM, BN, LBK, AMODE, false><<<grid, NT, 0, s>>>(a);
-        } else {
-            if (a.a_dtype == CMT_F32) gemm_lowp_kernel<f16_t, BM, BN, LBK, AMODE, true><<<grid, NT, 0, s>>>(a);
-            else gemm_lowp_kernel<f16_t, BM, BN, LBK, AMODE, false><<<grid, NT, 0, s>>>(a);
-        }
-    }
+    if (a.w_dtype == CMT_BF16) gemm_lowp_kernel<bf16_t, BM, BN, LBK, AMODE><<<grid, NT, 0, s>>>(a);
+    else gemm_lowp_kernel<f16_t, BM, BN, LBK, AMODE><<<grid, NT, 0, s>>>(a);
 }
 
 template <int BM, int BN, int AMODE>
@@ -1623,9 +1533,12 @@ int launch_mode(const cmt_gemm_args& a, hipStream_t s) {
     dim3 grid(a.N / BN, cdiv(a.M, BM), a.batch);
     if (a.w_dtype == CMT_F32) {
         gemm_f32_kernel<BM, BN, AMODE><<<grid, NT, 0, s>>>(a);
+    } else if constexpr (AMODE == CMT_A_CONV3X3) {
+        // cmt_gemm rejects fp32 A with 16-bit W for the 3x3 gather; compute-dtype A went to the LDS-DMA path
+        return cmt_fail(CMT_EINVAL, "cmt_gemm: the conv3x3 gather needs A in the compute dtype");
     } else {
-        // deepest K step that divides K (and, for the gathered modes, the per-tap channel count)
-        const int kdiv = AMODE == CMT_A_CONV3X3 ? a.conv_c : (AMODE == CMT_A_CONV1D3 ? a.K / 3 : a.K);
+        // deepest K step that divides K (for the 1D conv, the per-tap channel count)
+        const int kdiv = tap_width(a, AMODE);
         if (BM == 64 && kdiv % 128 == 0) launch_lowp<BM, BN, 128, AMODE>(a, grid, s);
         else if (kdiv % 64 == 0) launch_lowp<BM, BN, 64, AMODE>(a, grid, s);
         else launch_lowp<BM, BN, 32, AMODE>(a, grid, s);
@@ -1674,7 +1587,7 @@ extern "C" int cmt_gemm_ln(const cmt_gemm_args* gp, const cmt_ln_args* lp, void*
 
 // the row-mode / 3x3-conv split GEMMs gemm_x3_kernel covers
 static bool x3_eligible(const cmt_gemm_args& a) {
-    const int kdiv = a.a_mode == CMT_A_CONV3X3 ? a.conv_c : a.K;
+    const int kdiv = tap_width(a, a.a_mode);
     return (a.a_mode == CMT_A_ROWS || a.a_mode == CMT_A_CONV3X3) && a.A2 == nullptr && a.c_mode == CMT_C_ROWS &&
            a.k_splits <= 1 && a.plane_max2 == nullptr && a.N % 128 == 0 && kdiv % 32 == 0 && a.K % 32 == 0;
 }
@@ -1746,16 +1659,16 @@ extern "C" int cmt_gemm(const cmt_gemm_args* ap, void* stream) {
                     "cmt_gemm: plane_max2 needs a head-split 16-bit C, compute-dtype A and plane_max_cols % 32 == 0");
     hipStream_t s = (hipStream_t)stream;
     if (a.w_dtype == CMT_F16P && x3_eligible(a)) {
-        // split GEMMs whose 256-row grid covers most CUs (tools/bench_kernels.py --only split, against
-        // the 128 x 128 DMA tile: shared_conv 265 -> 249 us, RV fc1 76 -> 59, RV fc2 76 -> 64, BEV fc2
+        // split GEMMs whose 256-row grid covers most CUs (each kernel alone, against the 128 x 128
+        // DMA tile: shared_conv 265 -> 249 us, RV fc1 76 -> 59, RV fc2 76 -> 64, BEV fc2
         // 42 -> 34, RV query fc1 33 -> 20; 128 x 128 x3 tiles everywhere: 280, 65, 69, 37, 22);
         // fusion frame 539 -> 559 frames/s alternating on one box
         const int64_t t256 = (int64_t)(a.N / 128) * cdiv(a.M, 256) * a.batch;
-        if (t256 >= 160) return launch_x3<256>(a, s);
+        if (t256 >= 160) return launch_x3(a, s);
     }
     if (a.w_dtype != CMT_F32 && a.a_dtype == a.w_dtype) {
         // LDS-DMA path: 64-deep k stages
-        const int kdiv = a.a_mode == CMT_A_CONV3X3 ? a.conv_c : (a.a_mode == CMT_A_CONV1D3 ? a.K / 3 : a.K);
+        const int kdiv = tap_width(a, a.a_mode);
         CMT_REQUIRE(kdiv % 64 == 0, "cmt_gemm: compute-dtype A needs K (per tap) % 64 == 0");
         CMT_REQUIRE(a.ldc % 4 == 0 && (a.R == nullptr || a.ldr % 4 == 0) && a.bias_bstride % 4 == 0,
                     "cmt_gemm: ldc/ldr/bias_bstride must be multiples of 4");

@@ -41,9 +41,7 @@ constexpr int KP_K = 256;             // reduction depth (embed dims)
 constexpr int KP_KS = KP_K / 16;      // MFMA k-steps
 constexpr int KP_MAXB = 2048;         // bias floats per column part held in LDS
 
-typedef const __attribute__((address_space(1))) void* kp_gaddr_t;
 typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* kp_laddr_t;
 template <typename T> using frag_of = typename mfma_traits<T>::frag;
 
 // two fp32 values rounded (RNE) into one dword of 16-bit values, x0 low (v_cvt_pk_f16_f32 for f16)
@@ -216,8 +214,7 @@ __global__ __launch_bounds__(512, 1) void kvproj_kernel(cmt_gemm_args a, int par
         const int r = piece >> 5;
         const int lc = (piece & 31) ^ (r & 15);
         const int src = min(m0 + r, a.M - 1);
-        __builtin_amdgcn_global_load_lds((kp_gaddr_t)(Ab + (int64_t)src * lda + 8 * lc),
-                                         (kp_laddr_t)(lds + piece * 16), 16, 0, 0);
+        glds16(Ab + (int64_t)src * lda + 8 * lc, lds + piece * 16);
     }
     // the part's bias -> LDS: the epilogue reads it with no vmcnt wait (a global
     // bias load there would drain the W prefetch and the stores before it, which
@@ -225,8 +222,7 @@ __global__ __launch_bounds__(512, 1) void kvproj_kernel(cmt_gemm_args a, int par
     float* bsm = (float*)(lds + KP_BM * KP_K * 2 + NW * STG);
     for (int piece = tid; piece < (ncols >> 2); piece += NTH) {
         if (a.bias)
-            __builtin_amdgcn_global_load_lds((kp_gaddr_t)(a.bias + n_part + 4 * piece), (kp_laddr_t)(bsm + 4 * piece),
-                                             16, 0, 0);
+            glds16(a.bias + n_part + 4 * piece, bsm + 4 * piece);
         else
             *(f32x4*)(bsm + 4 * piece) = f32x4{0.f, 0.f, 0.f, 0.f};
     }
@@ -301,8 +297,7 @@ __global__ __launch_bounds__(512, 1) void kvproj_x3_kernel(cmt_gemm_args a, int 
         const int r = pc >> 5;
         const int lc = (pc & 31) ^ (r & 15);
         const int src = min(m0 + r, a.M - 1);
-        __builtin_amdgcn_global_load_lds((kp_gaddr_t)(Ab + (int64_t)src * lda + plane_lo * KP_K + 8 * lc),
-                                         (kp_laddr_t)(lds + piece * 16), 16, 0, 0);
+        glds16(Ab + (int64_t)src * lda + plane_lo * KP_K + 8 * lc, lds + piece * 16);
     }
     const int planes_all = ncols / 32 / 8;                         // the wave's head planes of a whole unit
     const int h0 = planes_all >> 1;                                // a half unit: planes [0, h0) or [h0, all)

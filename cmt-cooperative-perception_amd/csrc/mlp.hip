@@ -45,13 +45,6 @@ constexpr int W2_BLK = NOT * 2 * 2 * FRAG_B;   // one hidden block of W2p: 32 KB
 constexpr int MAX_HD = 2048;
         // hidden width bound (b1 staged in LDS)
 
-typedef const __attribute__((address_space(1))) void* mlp_gaddr_t;
-typedef __attribute__((address_space(3))) void* mlp_laddr_t;
-
-__device__ __forceinline__ void mlp_glds16(const void* src, void* lds) {
-    __builtin_amdgcn_global_load_lds((mlp_gaddr_t)src, (mlp_laddr_t)lds, 16, 0, 0);
-}
-
 __device__ __forceinline__ f32x16 mma3(const pair8_t& wh, const pair8_t& wl, const pair8_t& xh, const pair8_t& xl,
                                        f32x16 acc) {
     acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xl, acc, 0, 0, 0);
@@ -87,14 +80,14 @@ __global__ __launch_bounds__(64 * MW, 1) void mlp2_x3_kernel(cmt_mlp2_args a) {
         const char* src = w1g + (int64_t)hb * W1_BLK + lane * 16;
         char* dst = s1 + (hb & 1) * W1_BLK;
 #pragma unroll
-        for (int p = wave; p < 2 * KS; p += MW) mlp_glds16(src + p * FRAG_B, dst + p * FRAG_B);
+        for (int p = wave; p < 2 * KS; p += MW) glds16(src + p * FRAG_B, dst + p * FRAG_B);
     };
     auto issue_w2 = [&](int hb) {
         if (hb >= nhb) return;
         const char* src = w2g + (int64_t)hb * W2_BLK + lane * 16;
         char* dst = s2 + (hb & 1) * W2_BLK;
 #pragma unroll
-        for (int p = wave; p < 4 * NOT; p += MW) mlp_glds16(src + p * FRAG_B, dst + p * FRAG_B);
+        for (int p = wave; p < 4 * NOT; p += MW) glds16(src + p * FRAG_B, dst + p * FRAG_B);
     };
     issue_w1(0);
     issue_w2(0);
@@ -208,12 +201,12 @@ __global__ __launch_bounds__(64 * MW, 1) void mlp2_x3_kernel(cmt_mlp2_args a) {
         if (j < NW2) {
             if (hb + 1 >= nhb) return;
             const int p = wave + MW * j;
-            mlp_glds16(w2g + (int64_t)(hb + 1) * W2_BLK + lane * 16 + p * FRAG_B,
+            glds16(w2g + (int64_t)(hb + 1) * W2_BLK + lane * 16 + p * FRAG_B,
                        s2 + ((hb + 1) & 1) * W2_BLK + p * FRAG_B);
         } else {
             const int p = wave + MW * (j - NW2);
             if (hb + 2 >= nhb || p >= 2 * KS) return;
-            mlp_glds16(w1g + (int64_t)(hb + 2) * W1_BLK + lane * 16 + p * FRAG_B, s1 + (hb & 1) * W1_BLK + p * FRAG_B);
+            glds16(w1g + (int64_t)(hb + 2) * W1_BLK + lane * 16 + p * FRAG_B, s1 + (hb & 1) * W1_BLK + p * FRAG_B);
         }
     };
     auto fc2_fc1 = [&](int hb, auto next_c) {

@@ -52,9 +52,6 @@ constexpr int OFF_RED = OFF_PRM + PRM_B * 4;
 constexpr int LDS_TOTAL = OFF_RED + 2 * NWV * RB * 4;
 constexpr int DMA_PER_STAGE = STG_BYTES / 16 / NTC;   // 16-byte LDS-DMA pieces per thread per stage
 
-typedef const __attribute__((address_space(1))) void* rc_gaddr_t;
-typedef __attribute__((address_space(3))) void* rc_laddr_t;
-
 template <typename T>
 struct Eng : RowCtx<OFF_PRM, OFF_RED> {
     typedef typename mfma_traits<T>::frag frag;
@@ -81,8 +78,7 @@ struct Eng : RowCtx<OFF_PRM, OFF_RED> {
             const int piece = tid + NTC * i;
             const int n = piece >> 2;
             const int lc = (piece & 3) ^ ((n >> 2) & 3);
-            __builtin_amdgcn_global_load_lds((rc_gaddr_t)(W + (int64_t)n * ld + kc * KSTG + 8 * lc),
-                                             (rc_laddr_t)(dst + piece * 16), 16, 0, 0);
+            glds16(W + (int64_t)n * ld + kc * KSTG + 8 * lc, dst + piece * 16);
         }
         ++issued;
     }
@@ -250,14 +246,12 @@ __global__ __launch_bounds__(NTC, 1) void chain_kernel(cmt_chain_args a) {
             const int r = piece >> 5;
             const int lc = (piece & 31) ^ (r & 15);
             const int src_row = min(m0 + r, a.rows - 1);
-            __builtin_amdgcn_global_load_lds((rc_gaddr_t)((const T*)a.X + (int64_t)src_row * CE + 8 * lc),
-                                             (rc_laddr_t)(actA + piece * 16), 16, 0, 0);
+            glds16((const T*)a.X + (int64_t)src_row * CE + 8 * lc, actA + piece * 16);
         }
     }
     const int nprm = kind == 0 ? PRM_A : PRM_B;
     for (int piece = e.tid; piece < (nprm >> 2); piece += NTC)
-        __builtin_amdgcn_global_load_lds((rc_gaddr_t)(a.prm + 4 * piece), (rc_laddr_t)(lds + OFF_PRM + piece * 16),
-                                         16, 0, 0);
+        glds16(a.prm + 4 * piece, lds + OFF_PRM + piece * 16);
 #pragma unroll
     for (int s = 0; s < NSTG - 1; ++s) e.issue();
     typename Eng<T>::frag wr[SUB_STAGES][2];

@@ -18,7 +18,7 @@ def short(n):
     return n.replace("(anonymous namespace)::", "").replace("_ZN12_GLOBAL__N_1", "").replace("void ", "")[:60]
 
 
-starts = [i for i, r in enumerate(rows) if "gemm_x3_kernel<256, 1>" in r["Kernel_Name"]]
+starts = [i for i, r in enumerate(rows) if "gemm_x3_kernel<1>" in r["Kernel_Name"]]
 starts = starts[::2]   # two agents' convs per step
 for a, b in zip(starts[-4:-1], starts[-3:]):
     st = rows[a:b]
