@@ -25,6 +25,12 @@
 // (q >= dn_pad or k / dn_group != q / dn_group).  Dropout (p > 0) keeps
 // P(q, k) with probability 1 - p by a counter hash of (seed, b, h, q, k),
 // recomputed identically in the backward.
+//
+// Three arithmetics share these definitions: the exact-f32 kernels (train_*), the
+// flash fp16 core's f16 kernels (train16_*, fp16_inputs) and, opt-in through
+// cmt_attn_train_fwd_bf16x3 / _bwd_bf16x3, the fp32 core with every product in
+// three bf16 MFMA passes on split operands (train_x3_*: the arithmetic of the
+// training GEMMs, ~2^-16 per product, fp32 softmax and statistics).
 #include "cmt_common.h"
 
 #include <cstdlib>
@@ -1045,6 +1051,359 @@ __global__ __launch_bounds__(64 * (8 / QB)) void train16_dq2_kernel(AP p, const 
     }
 }
 
+// ---------------------------------------------------------------------------
+// bf16x3 forms of the three kernels (cmt_attn_train_fwd_bf16x3 / _bwd_bf16x3:
+// the fp32 core on the arithmetic of the training GEMMs, train.hip
+// gemm_x3_kernel).  Every fp32 operand is split x = hi + lo, hi = bf16(x) (RNE),
+// lo = bf16(x - hi) -- bf16 keeps the fp32 exponent, so gradient-sized dO and dS
+// split without underflow -- and every product runs as lo*hi + hi*lo + hi*hi
+// (small terms first, lo*lo dropped) on v_mfma_f32_32x32x16_bf16, fp32
+// accumulate: ~2^-16 relative per product.  The kernels have the form of the
+// general f16 ones (train16_*: 4 waves, 64-row tiles, S^T = K Q^T with the lane
+// owning a query, accumulator tiles fed on as B operands) with two row-major
+// images (hi, lo) per staged tile in rm_off's swizzle -- Q, K, V and dO are split
+// as they are staged, a lane's own row and the accumulator tiles P / dS (fp32) in
+// registers.  A product over a tile's rows reads its A operand from the same
+// row-major images by transposed LDS reads (tr_frag, as the long-key kernels): no
+// transposed image is written.  Nothing is rounded on the way out (O unrounded,
+// LSE2 = m + log2 l), and the dK/dV kernel takes the query splits of the
+// exact-f32 one.  Scores, softmax statistics, delta, dS = P (dP - delta),
+// the DN mask and the dropout hash are the fp32 code of the kernels above.
+// ---------------------------------------------------------------------------
+constexpr int X3P = KT * RMB;   // bytes of one row-major image (64 rows x 64 B); the lo image follows the hi one
+
+__device__ __forceinline__ bf16x8 as_bf16(h8_t v) { return __builtin_bit_cast(bf16x8, v); }
+__device__ __forceinline__ void split_x3(float x, bf16_t& hi, bf16_t& lo) {
+    hi = (bf16_t)x;
+    lo = (bf16_t)(x - (float)hi);
+}
+
+// stage16's row-major image with the rows split: hi image at rm, lo image X3P bytes behind it
+__device__ __forceinline__ void stage_x3(char* rm, const float* X, int64_t rs, int r0, int nrows, int tid) {
+    const int r = tid >> 2, c = tid & 3;
+    f32x4 a = {0.f, 0.f, 0.f, 0.f}, b = a;
+    if (r0 + r < nrows) {
+        a = *(const f32x4*)(X + (int64_t)(r0 + r) * rs + 8 * c);
+        b = *(const f32x4*)(X + (int64_t)(r0 + r) * rs + 8 * c + 4);
+    }
+    bf16x8 hv, lv;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        bf16_t h, l;
+        split_x3(a[j], h, l);
+        hv[j] = h; lv[j] = l;
+        split_x3(b[j], h, l);
+        hv[4 + j] = h; lv[4 + j] = l;
+    }
+    *(bf16x8*)(rm + rm_off(r, c)) = hv;
+    *(bf16x8*)(rm + X3P + rm_off(r, c)) = lv;
+}
+
+// B fragments from accumulator registers 8 ss .. 8 ss + 7 (fp32), split
+__device__ __forceinline__ void acc_x3(const f32x16& x, int ss, bf16x8& hi, bf16x8& lo) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        bf16_t h, l;
+        split_x3(x[8 * ss + j], h, l);
+        hi[j] = h; lo[j] = l;
+    }
+}
+// a lane's own row of 32 fp32 values as the two split B fragments (d = 16 kk + 8 lh + j)
+__device__ __forceinline__ void own_row_x3(const float* row, int lh, bf16x8 (&hi)[2], bf16x8 (&lo)[2]) {
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+        const f32x4 a = *(const f32x4*)(row + 16 * kk + 8 * lh), b = *(const f32x4*)(row + 16 * kk + 8 * lh + 4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            bf16_t h, l;
+            split_x3(a[j], h, l);
+            hi[kk][j] = h; lo[kk][j] = l;
+            split_x3(b[j], h, l);
+            hi[kk][4 + j] = h; lo[kk][4 + j] = l;
+        }
+    }
+}
+// keep() in two steps -- the same hash, the same kept set: its (seed, b, h, q) part once per query
+// (per lane in the forward / dQ kernels, per staged query in the dK/dV kernel), the key's part per
+// element.  With the MFMA time cut to 3/16 the per-element integer multiplies are what is left.
+__device__ __forceinline__ uint32_t keep_row(const AP& p, int bh, int q) {
+    return mix32(p.a.seed ^ mix32((uint32_t)bh * 0x9e3779b9U + (uint32_t)q));
+}
+__device__ __forceinline__ bool keep_col(const AP& p, uint32_t hrow, int k) {
+    if constexpr ((CMT_AT_VAR & 2) != 0) return true;
+    return mix32(hrow ^ (uint32_t)k * 0x85ebca6bU) >= p.drop_thr;
+}
+// c += A B in three passes, small terms first
+__device__ __forceinline__ f32x16 mma_x3(bf16x8 ah, bf16x8 al, bf16x8 bh, bf16x8 bl, f32x16 c) {
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, c, 0, 0, 0);
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, c, 0, 0, 0);
+}
+// rows of a row-major image pair times a lane's own split row
+__device__ __forceinline__ f32x16 mma_x3_rm(const char* rm, int rb, int kk, int lane, bf16x8 bh, bf16x8 bl, f32x16 c) {
+    return mma_x3(as_bf16(frag_rm(rm, rb, kk, lane)), as_bf16(frag_rm(rm + X3P, rb, kk, lane)), bh, bl, c);
+}
+// c^T += Z^T W: Z the rows of a row-major image pair read transposed, W an fp32 accumulator tile
+// (k half ss of block rb: rows rb * 32 + 16 ss .. + 15 in the accumulator order)
+__device__ __forceinline__ f32x16 mma_x3_tr(const char* rm, int rb, int ss, int lane, const f32x16& w, f32x16 c) {
+    bf16x8 wh, wl;
+    acc_x3(w, ss, wh, wl);
+    const int r0 = rb * 32 + 16 * ss;
+    return mma_x3(as_bf16(tr_frag(rm, r0, lane)), as_bf16(tr_frag(rm + X3P, r0, lane)), wh, wl, c);
+}
+
+template <bool MASK, bool DROP>
+__global__ __launch_bounds__(256) void train_x3_fwd_kernel(AP p) {
+    resolve_seed(p);
+    const cmt_attn_train_args& a = p.a;
+    __shared__ __attribute__((aligned(16))) char Ks[2 * X3P];   // [key][d], hi | lo
+    __shared__ __attribute__((aligned(16))) char Vs[2 * X3P];   // [key][d], hi | lo
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 31, lh = lane >> 5;
+    const int bh = blockIdx.y, b = bh / a.H, h = bh - b * a.H, split = blockIdx.z;
+    const float* Qb = a.Q + (int64_t)b * a.q_bs + (int64_t)h * a.q_hs;
+    const float* Kb = a.K + (int64_t)b * a.k_bs + (int64_t)h * a.k_hs;
+    const float* Vb = a.V + (int64_t)b * a.v_bs + (int64_t)h * a.v_hs;
+    const int q = blockIdx.x * 128 + wave * 32 + lr;
+    const DnRange dnr = dn_query_range(a, q);
+    const uint32_t hrow = keep_row(p, bh, q);
+    const int qc = min(q, a.Nq - 1);
+    bf16x8 qh[2], ql[2];
+    own_row_x3(Qb + (int64_t)qc * a.q_rs, lh, qh, ql);
+    const int ntiles = (a.Nk + KT - 1) / KT;
+    const int t0 = split * p.tiles_per_split, t1 = min(ntiles, t0 + p.tiles_per_split);
+    f32x16 o;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) o[r] = 0.f;
+    float m_run = -__builtin_inff(), l_run = 0.f;
+    for (int t = t0; t < t1; ++t) {
+        __syncthreads();
+        stage_x3(Ks, Kb, a.k_rs, t * KT, a.Nk, tid);
+        stage_x3(Vs, Vb, a.v_rs, t * KT, a.Nk, tid);
+        __syncthreads();
+        const bool edge = (t + 1) * KT > a.Nk;
+        f32x16 s[2];
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) s[kb][r] = 0.f;
+#pragma unroll
+            for (int kk = 0; kk < 2; ++kk) s[kb] = mma_x3_rm(Ks, kb, kk, lane, qh[kk], ql[kk], s[kb]);   // S^T
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int k = t * KT + kb * 32 + key_of(r, lh);
+                const bool hide = (edge && k >= a.Nk) || (MASK && dn_hidden_key(a, dnr, k));
+                s[kb][r] = hide ? -__builtin_inff() : s[kb][r] * p.c;
+            }
+        }
+        float mt = -__builtin_inff();
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) mt = fmaxf(mt, s[kb][r]);
+        mt = fmaxf(mt, __shfl_xor(mt, 32));
+        const float m_new = fmaxf(m_run, mt);
+        const float m_use = m_new == -__builtin_inff() ? 0.f : m_new;   // fully masked so far
+        const float alpha = xexp2(m_run - m_use);
+        float ls = 0.f;
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float e = xexp2(s[kb][r] - m_use);
+                ls += e;
+                float pe = e;
+                if (DROP) {
+                    const int k = t * KT + kb * 32 + key_of(r, lh);
+                    pe = keep_col(p, hrow, k) ? pe : 0.f;
+                }
+                s[kb][r] = pe;
+            }
+        l_run = l_run * alpha + ls;
+        m_run = m_new;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[r] *= alpha;
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+            for (int ss = 0; ss < 2; ++ss) o = mma_x3_tr(Vs, kb, ss, lane, s[kb], o);   // O^T += V^T P^T
+    }
+    const float l_tot = l_run + __shfl_xor(l_run, 32);
+    if (DROP) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[r] *= p.keep_scale;
+    }
+    if (q >= a.Nq) return;
+    if (a.kv_splits <= 1) {
+        const float inv = 1.f / l_tot;
+        float* Ob = a.O + (int64_t)b * a.o_bs + (int64_t)h * a.o_hs + (int64_t)q * a.o_rs;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) Ob[key_of(r, lh)] = o[r] * inv;
+        if (lh == 0) a.LSE[(int64_t)bh * a.Nq + q] = m_run + log2f(l_tot);
+    } else {
+        float* ws = (float*)a.workspace;
+        const int64_t rows = (int64_t)a.B * a.H * a.Nq;
+        const int64_t row = (int64_t)split * rows + (int64_t)bh * a.Nq + q;
+        float* Op = ws + row * D;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) Op[key_of(r, lh)] = o[r];
+        if (lh == 0) {
+            ws[(int64_t)a.kv_splits * rows * D + row] = m_run;
+            ws[(int64_t)a.kv_splits * rows * (D + 1) + row] = l_tot;
+        }
+    }
+}
+
+template <bool MASK, bool DROP>
+__global__ __launch_bounds__(256) void train_x3_dq_kernel(AP p) {
+    resolve_seed(p);
+    const cmt_attn_train_args& a = p.a;
+    __shared__ __attribute__((aligned(16))) char Ks[2 * X3P];   // [key][d], hi | lo
+    __shared__ __attribute__((aligned(16))) char Vs[2 * X3P];   // [key][d]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 31, lh = lane >> 5;
+    const int bh = blockIdx.y, b = bh / a.H, h = bh - b * a.H, split = blockIdx.z;
+    const float* Qb = a.Q + (int64_t)b * a.q_bs + (int64_t)h * a.q_hs;
+    const float* Kb = a.K + (int64_t)b * a.k_bs + (int64_t)h * a.k_hs;
+    const float* Vb = a.V + (int64_t)b * a.v_bs + (int64_t)h * a.v_hs;
+    const float* dOb = a.dO + (int64_t)b * a.o_bs + (int64_t)h * a.o_hs;
+    const int q = blockIdx.x * 128 + wave * 32 + lr;
+    const DnRange dnr = dn_query_range(a, q);
+    const uint32_t hrow = keep_row(p, bh, q);
+    const int qc = min(q, a.Nq - 1);
+    bf16x8 qh[2], ql[2], dh[2], dl2[2];
+    own_row_x3(Qb + (int64_t)qc * a.q_rs, lh, qh, ql);
+    own_row_x3(dOb + (int64_t)qc * a.o_rs, lh, dh, dl2);
+    const float lse = a.LSE[(int64_t)bh * a.Nq + qc];
+    const float dl = a.delta[(int64_t)bh * a.Nq + qc];
+    const int ntiles = (a.Nk + KT - 1) / KT;
+    const int t0 = split * p.tiles_per_split, t1 = min(ntiles, t0 + p.tiles_per_split);
+    f32x16 dq;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) dq[r] = 0.f;
+    for (int t = t0; t < t1; ++t) {
+        __syncthreads();
+        stage_x3(Ks, Kb, a.k_rs, t * KT, a.Nk, tid);
+        stage_x3(Vs, Vb, a.v_rs, t * KT, a.Nk, tid);
+        __syncthreads();
+        const bool edge = (t + 1) * KT > a.Nk;
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb) {
+            f32x16 s, dp;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) s[r] = dp[r] = 0.f;
+#pragma unroll
+            for (int kk = 0; kk < 2; ++kk) {
+                s = mma_x3_rm(Ks, kb, kk, lane, qh[kk], ql[kk], s);       // S^T
+                dp = mma_x3_rm(Vs, kb, kk, lane, dh[kk], dl2[kk], dp);    // dP^T = V dO^T
+            }
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int k = t * KT + kb * 32 + key_of(r, lh);
+                const bool hide = (edge && k >= a.Nk) || (MASK && dn_hidden_key(a, dnr, k));
+                const float pr = hide ? 0.f : xexp2(s[r] * p.c - lse);
+                float g = dp[r];
+                if (DROP) g = keep_col(p, hrow, k) ? g * p.keep_scale : 0.f;
+                s[r] = pr * (g - dl);                                   // dS^T
+            }
+#pragma unroll
+            for (int ss = 0; ss < 2; ++ss) dq = mma_x3_tr(Ks, kb, ss, lane, s, dq);   // dQ^T += K^T dS^T
+        }
+    }
+    if (q >= a.Nq) return;
+    float* dQb = a.dQ + (int64_t)b * a.q_bs + (int64_t)h * a.q_hs + (int64_t)q * a.q_rs;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const float v = dq[r] * a.scale;
+        if (a.kv_splits > 1) atomicAdd(dQb + key_of(r, lh), v);
+        else dQb[key_of(r, lh)] = v;
+    }
+}
+
+// query tiles [z qt_per, (z + 1) qt_per) of split z = blockIdx.z, f32 atomics into zeroed dK / dV
+// when split (as train_dkv_kernel)
+template <bool MASK, bool DROP>
+__global__ __launch_bounds__(256) void train_x3_dkv_kernel(AP p, int qt_per) {
+    resolve_seed(p);
+    const cmt_attn_train_args& a = p.a;
+    __shared__ __attribute__((aligned(16))) char Qs[2 * X3P];   // [q][d], hi | lo
+    __shared__ __attribute__((aligned(16))) char Ds[2 * X3P];   // dO [q][d]
+    __shared__ float Ls[KT], Dl[KT];
+    __shared__ uint32_t Hq[KT];                                 // keep_row of the tile's queries
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 31, lh = lane >> 5;
+    const int bh = blockIdx.y, b = bh / a.H, h = bh - b * a.H;
+    const float* Qb = a.Q + (int64_t)b * a.q_bs + (int64_t)h * a.q_hs;
+    const float* Kb = a.K + (int64_t)b * a.k_bs + (int64_t)h * a.k_hs;
+    const float* Vb = a.V + (int64_t)b * a.v_bs + (int64_t)h * a.v_hs;
+    const float* dOb = a.dO + (int64_t)b * a.o_bs + (int64_t)h * a.o_hs;
+    const int k = blockIdx.x * 128 + wave * 32 + lr;
+    const DnRange dnr = dn_key_range(a, k);
+    const int kc = min(k, a.Nk - 1);
+    bf16x8 kh[2], kl[2], vh[2], vl[2];
+    own_row_x3(Kb + (int64_t)kc * a.k_rs, lh, kh, kl);
+    own_row_x3(Vb + (int64_t)kc * a.v_rs, lh, vh, vl);
+    f32x16 dk, dv;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) dk[r] = dv[r] = 0.f;
+    const int nqt = (a.Nq + KT - 1) / KT;
+    const int tq0 = blockIdx.z * qt_per, tq1 = min(nqt, tq0 + qt_per);
+    for (int t = tq0; t < tq1; ++t) {
+        __syncthreads();
+        stage_x3(Qs, Qb, a.q_rs, t * KT, a.Nq, tid);
+        stage_x3(Ds, dOb, a.o_rs, t * KT, a.Nq, tid);
+        if (tid < KT) {
+            const int qq = min(t * KT + tid, a.Nq - 1);
+            Ls[tid] = a.LSE[(int64_t)bh * a.Nq + qq];
+            Dl[tid] = a.delta[(int64_t)bh * a.Nq + qq];
+            if (DROP) Hq[tid] = keep_row(p, bh, t * KT + tid);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int qb = 0; qb < 2; ++qb) {
+            f32x16 s, dp;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) s[r] = dp[r] = 0.f;
+#pragma unroll
+            for (int kk = 0; kk < 2; ++kk) {
+                s = mma_x3_rm(Qs, qb, kk, lane, kh[kk], kl[kk], s);      // S = Q K^T (lane = key)
+                dp = mma_x3_rm(Ds, qb, kk, lane, vh[kk], vl[kk], dp);    // dP = dO V^T
+            }
+            f32x16 pd;                                                 // P, dropped (dV operand; scale later)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int qi = qb * 32 + key_of(r, lh), qq = t * KT + qi;
+                const bool valid = qq < a.Nq && k < a.Nk && !(MASK && dn_hidden_query(dnr, qq));
+                const float pr = valid ? xexp2(s[r] * p.c - Ls[qi]) : 0.f;
+                float g = dp[r], pe = pr;
+                if (DROP) {
+                    const bool kp = keep_col(p, Hq[qi], k);
+                    g = kp ? g * p.keep_scale : 0.f;
+                    pe = kp ? pe : 0.f;
+                }
+                pd[r] = pe;
+                s[r] = pr * (g - Dl[qi]);                              // dS
+            }
+#pragma unroll
+            for (int ss = 0; ss < 2; ++ss) {
+                dv = mma_x3_tr(Ds, qb, ss, lane, pd, dv);   // dV^T += dO^T P
+                dk = mma_x3_tr(Qs, qb, ss, lane, s, dk);    // dK^T += Q^T dS
+            }
+        }
+    }
+    if (k >= a.Nk) return;
+    float* dKb = a.dK + (int64_t)b * a.k_bs + (int64_t)h * a.k_hs + (int64_t)k * a.k_rs;
+    float* dVb = a.dV + (int64_t)b * a.v_bs + (int64_t)h * a.v_hs + (int64_t)k * a.v_rs;
+    const float vs = DROP ? p.keep_scale : 1.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        if (gridDim.z > 1) {
+            atomicAdd(dKb + key_of(r, lh), dk[r] * a.scale);
+            atomicAdd(dVb + key_of(r, lh), dv[r] * vs);
+        } else {
+            dKb[key_of(r, lh)] = dk[r] * a.scale;
+            dVb[key_of(r, lh)] = dv[r] * vs;
+        }
+    }
+}
+
 AP make_ap(const cmt_attn_train_args& a, int splits) {
     AP p;
     p.a = a;
@@ -1292,4 +1651,87 @@ extern "C" int cmt_attn_train_bwd(const cmt_attn_train_args* ap, void* stream) {
         train_dkv_kernel<<<dim3(gk.x, gk.y, ks), 256, 0, s>>>(p, cdiv(nqt, ks));
     }
     return cmt_check_launch("cmt_attn_train_bwd");
+}
+
+// ---------------------------------------------------------------------------
+// The fp32 core on three bf16 MFMA passes (train_x3_* kernels above).  Grids and splits, chosen at
+// the coop self-attention shape (B 2, H 8, Nq = Nk = 1 100, DN 200 / 20, p 0.1: 144 workgroups per
+// split in every kernel, 18 tiles; kernel-trace averages, profiles/train_attn_x3.txt):
+//   forward   key splits train_splits() as the exact-f32 entry point (+ train_combine_kernel, same
+//             workspace layout): 4 splits; kernel + combine 36.1 + 9.5 us at 3, 32.4 + 11.5 at 4,
+//             35.5 + 14.5 at 6
+//   dQ        key splits min(tiles / 2, 432 / workgroups), f32 atomics into a zeroed dQ: 3 splits;
+//             78.4 us at 2, 72.7 at 3, 92.1 at 5 (the exact-f32 rule's 768) -- the atomic
+//             traffic grows with the splits and these kernels no longer hide it behind the MFMAs
+//   dK / dV   query splits min(query tiles / 2, 288 / workgroups), f32 atomics into zeroed dK / dV:
+//             2 splits; 115.2 us at 2, 120.3 at 3 (the exact-f32 rule's 512), 145.3 at 4; one split
+//             (144 workgroups on 256 CUs) measured 175.6 us against 163.3 / 141.9 at 2 / 3 before the
+//             transposed LDS reads
+// ---------------------------------------------------------------------------
+namespace {
+
+int check_args_x3(const cmt_attn_train_args* ap, const char* who) {
+    CMT_REQUIRE(ap != nullptr, std::string(who) + ": null args");
+    if (int rc = check_args(*ap, who)) return rc;
+    CMT_REQUIRE(ap->fp16_inputs == 0, std::string(who) + ": fp16_inputs is the flash fp16 core (cmt_attn_train_fwd / _bwd)");
+    return 0;
+}
+
+// one of the <MASK, DROP> instantiations of a train_x3_* kernel template
+#define CMT_X3_LAUNCH(kernel, grid, ...)                                                  \
+    do {                                                                                  \
+        if (mask && drop) kernel<true, true><<<grid, 256, 0, s>>>(__VA_ARGS__);           \
+        else if (mask) kernel<true, false><<<grid, 256, 0, s>>>(__VA_ARGS__);             \
+        else if (drop) kernel<false, true><<<grid, 256, 0, s>>>(__VA_ARGS__);             \
+        else kernel<false, false><<<grid, 256, 0, s>>>(__VA_ARGS__);                      \
+    } while (0)
+
+}  // namespace
+
+extern "C" int64_t cmt_attn_train_bf16x3_workspace_bytes(const cmt_attn_train_args* a) {
+    if (!a) return 0;
+    const int s = train_splits(*a);
+    if (s <= 1) return 0;
+    return (int64_t)s * a->B * a->H * a->Nq * (D + 2) * (int64_t)sizeof(float);
+}
+
+extern "C" int cmt_attn_train_fwd_bf16x3(const cmt_attn_train_args* ap, void* stream) {
+    if (int rc = check_args_x3(ap, "cmt_attn_train_fwd_bf16x3")) return rc;
+    const int splits = train_splits(*ap);
+    if (splits > 1 && (ap->workspace == nullptr || ap->workspace_bytes < cmt_attn_train_bf16x3_workspace_bytes(ap)))
+        return cmt_fail(CMT_EWORKSPACE, "cmt_attn_train_fwd_bf16x3: workspace too small");
+    AP p = make_ap(*ap, splits);
+    hipStream_t s = (hipStream_t)stream;
+    const bool mask = ap->dn_pad > 0, drop = ap->dropout_p > 0.f;
+    const dim3 grid(cdiv(ap->Nq, 128), ap->B * ap->H, splits);
+    CMT_X3_LAUNCH(train_x3_fwd_kernel, grid, p);
+    if (splits > 1) {
+        const int64_t n = (int64_t)ap->B * ap->H * ap->Nq * D;
+        train_combine_kernel<<<(unsigned)cdiv64(n, 256), 256, 0, s>>>(p);
+    }
+    return cmt_check_launch("cmt_attn_train_fwd_bf16x3");
+}
+
+extern "C" int cmt_attn_train_bwd_bf16x3(const cmt_attn_train_args* ap, void* stream) {
+    if (int rc = check_args_x3(ap, "cmt_attn_train_bwd_bf16x3")) return rc;
+    CMT_REQUIRE(ap->dO && ap->dQ && ap->dK && ap->dV && ap->delta, "cmt_attn_train_bwd_bf16x3: null gradient pointer");
+    const cmt_attn_train_args& a = *ap;
+    const int ntiles = cdiv(a.Nk, KT), nqt = cdiv(a.Nq, KT);
+    const dim3 gk(cdiv(a.Nk, 128), a.B * a.H);
+    const int qs = max(1, min(ntiles / 2, 432 / (cdiv(a.Nq, 128) * a.B * a.H)));   // dQ key splits
+    const int ks = max(1, min(nqt / 2, (int)(288 / ((int64_t)gk.x * gk.y))));      // dK / dV query splits
+    AP p = make_ap(a, qs);
+    hipStream_t s = (hipStream_t)stream;
+    const bool mask = a.dn_pad > 0, drop = a.dropout_p > 0.f;
+    const int64_t rows = (int64_t)a.B * a.H * a.Nq;
+    train_delta_kernel<<<(unsigned)cdiv64(rows, 4), 256, 0, s>>>(p);
+    if (qs > 1) zero_heads(a.dQ, a.q_bs, a.q_hs, a.q_rs, a.B, a.H, a.Nq, s);
+    if (ks > 1) {
+        zero_heads(a.dK, a.k_bs, a.k_hs, a.k_rs, a.B, a.H, a.Nk, s);
+        zero_heads(a.dV, a.v_bs, a.v_hs, a.v_rs, a.B, a.H, a.Nk, s);
+    }
+    const dim3 gq(cdiv(a.Nq, 128), a.B * a.H, qs);
+    CMT_X3_LAUNCH(train_x3_dq_kernel, gq, p);
+    CMT_X3_LAUNCH(train_x3_dkv_kernel, dim3(gk.x, gk.y, ks), p, cdiv(nqt, ks));
+    return cmt_check_launch("cmt_attn_train_bwd_bf16x3");
 }

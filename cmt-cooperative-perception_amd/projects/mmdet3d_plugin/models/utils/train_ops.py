@@ -141,7 +141,7 @@ class _Attention(torch.autograd.Function):
     """q [B, Nq, H*32], k / v [B, Nk, H*32] (contiguous rows) -> o [B, Nq, H*32]."""
 
     @staticmethod
-    def forward(ctx, q, k, v, H, scale, dn_pad, dn_group, fp16, dropout_p, seed, seed_dev):
+    def forward(ctx, q, k, v, H, scale, dn_pad, dn_group, fp16, dropout_p, seed, seed_dev, mode):
         B, Nq, C = q.shape
         Nk = k.shape[1]
         o = torch.empty_like(q)
@@ -149,6 +149,8 @@ class _Attention(torch.autograd.Function):
         kw = dict(B=B, H=H, Nq=Nq, Nk=Nk, q_strides=(Nq * C, 32, C), k_strides=(Nk * C, 32, C),
                   v_strides=(Nk * C, 32, C), o_strides=(Nq * C, 32, C), scale=scale, dn_pad=dn_pad,
                   dn_group=dn_group, fp16_inputs=fp16, dropout_p=dropout_p, seed=seed, seed_dev=seed_dev)
+        # the backward runs the arithmetic the forward ran, whatever set_train_attn says by then
+        kw["mode"] = mode or T.train_attn()
         ctx.ws = T.attn_train_fwd(q, k, v, o, lse, **kw)
         ctx.kw = kw
         ctx.save_for_backward(q, k, v, o, lse)
@@ -160,7 +162,7 @@ class _Attention(torch.autograd.Function):
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
         T.attn_train_bwd(q, k, v, o, lse, do.contiguous(), dq, dk, dv, ws=ctx.ws, **ctx.kw)
         ctx.ws = None
-        return dq, dk, dv, None, None, None, None, None, None, None, None
+        return dq, dk, dv, None, None, None, None, None, None, None, None, None
 
 
 class KVAll:
@@ -252,7 +254,7 @@ class _CrossAttn(torch.autograd.Function):
         lse = torch.empty((B * H * Nq,), dtype=torch.float32, device=q.device)
         kw = dict(B=B, H=H, Nq=Nq, Nk=Nk, q_strides=(Nq * C, 32, C), k_strides=(K.stride(0), 32, ld),
                   v_strides=(V.stride(0), 32, V.stride(1)), o_strides=(Nq * C, 32, C), scale=scale, dn_pad=0,
-                  dn_group=0, fp16_inputs=fp16, dropout_p=0.0, seed=0, seed_dev=None)
+                  dn_group=0, fp16_inputs=fp16, dropout_p=0.0, seed=0, seed_dev=None, mode=T.train_attn())
         # the workspace holds the f16 copies of q / K / V the backward reuses (ABI 25)
         ctx.ws = T.attn_train_fwd(q, K, V, o, lse, **kw)
         ctx.kw, ctx.holder, ctx.l = kw, holder, l
@@ -283,11 +285,13 @@ def cross_attention(q, token, holder, l, num_heads, *, fp16=True):
                             fp16)
 
 
-def attention(q, k, v, num_heads, *, dn_pad=0, dn_group=0, fp16=False, dropout_p=0.0, seed=0, seed_dev=None):
-    """seed_dev: optional int32 device tensor [1] added to seed on the device (graph-replayed steps)"""
+def attention(q, k, v, num_heads, *, dn_pad=0, dn_group=0, fp16=False, dropout_p=0.0, seed=0, seed_dev=None,
+              mode=None):
+    """seed_dev: optional int32 device tensor [1] added to seed on the device (graph-replayed steps);
+    mode: the fp32 core's arithmetic (native_train.set_train_attn; None = the current mode)"""
     return _Attention.apply(q.contiguous(), k.contiguous(), v.contiguous(), num_heads,
                             1.0 / math.sqrt(q.shape[-1] // num_heads), dn_pad, dn_group, fp16, dropout_p, seed,
-                            seed_dev)
+                            seed_dev, mode)
 
 
 class _Taps3(torch.autograd.Function):

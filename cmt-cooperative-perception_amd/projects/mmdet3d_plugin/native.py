@@ -225,6 +225,9 @@ def _load():
         "cmt_attn_train_workspace_bytes": ([P(AttnTrainArgs)], _i64),
         "cmt_attn_train_fwd": ([P(AttnTrainArgs), _vp], _int),
         "cmt_attn_train_bwd": ([P(AttnTrainArgs), _vp], _int),
+        "cmt_attn_train_bf16x3_workspace_bytes": ([P(AttnTrainArgs)], _i64),
+        "cmt_attn_train_fwd_bf16x3": ([P(AttnTrainArgs), _vp], _int),
+        "cmt_attn_train_bwd_bf16x3": ([P(AttnTrainArgs), _vp], _int),
         "cmt_ln_train_fwd": ([P(LnTrainArgs), _vp], _int),
         "cmt_ln_train_bwd": ([P(LnTrainArgs), _vp], _int),
         "cmt_bn_workspace_bytes": ([_int], _i64),

@@ -2,13 +2,14 @@
 PATH": train.hip, attn_train.hip).  Same contract as native.py: device
 tensors only, the current torch stream, no CPU or eager-PyTorch fallback."""
 import ctypes
+import os
 import threading
 
 import torch
 
 from . import native as N
 
-__all__ = ["gemm_ex", "set_train_gemm", "linear_fwd", "linear_bwd", "attn_train_fwd", "attn_train_bwd", "ln_train_fwd", "ln_train_bwd",
+__all__ = ["gemm_ex", "set_train_gemm", "set_train_attn", "linear_fwd", "linear_bwd", "attn_train_fwd", "attn_train_bwd", "ln_train_fwd", "ln_train_bwd",
            "bn_relu_train_fwd", "bn_relu_train_bwd", "im2col3x3", "conv3x3_wgrad", "det_loss", "match_cost", "lsap", "sumsq", "adamw_step"]
 
 
@@ -38,6 +39,39 @@ def set_train_gemm(mode):
         raise ValueError(f"train gemm mode must be one of {sorted(_GEMM_ENTRY)}")
     old, _gemm_mode = _gemm_mode, mode
     return old
+
+
+# Arithmetic of the training step's fp32 attention core (every attn_train_fwd / _bwd call with
+# fp16_inputs=False: the decoder's self-attention, and the cross-attention when it runs fp32):
+# "f32" (cmt_attn_train_fwd / _bwd, the exact-f32 MFMA) or "bf16x3" (cmt_attn_train_fwd_bf16x3 /
+# _bwd_bf16x3, every product in three bf16 MFMA passes on split operands like the bf16x3 GEMM,
+# ~2^-16 relative per product).  The fp16 flash core (fp16_inputs=True) is not affected.  The
+# initial mode is the environment variable CMT_TRAIN_ATTN, read once here.
+_ATTN_ENTRY = {"f32": ("cmt_attn_train_workspace_bytes", "cmt_attn_train_fwd", "cmt_attn_train_bwd"),
+               "bf16x3": ("cmt_attn_train_bf16x3_workspace_bytes", "cmt_attn_train_fwd_bf16x3",
+                          "cmt_attn_train_bwd_bf16x3")}
+
+
+def _attn_mode_name(mode, what):
+    if mode not in _ATTN_ENTRY:
+        raise ValueError(f"{what} must be one of {sorted(_ATTN_ENTRY)}, got {mode!r}")
+    return mode
+
+
+_attn_mode = _attn_mode_name(os.environ.get("CMT_TRAIN_ATTN") or "f32", "CMT_TRAIN_ATTN")
+
+
+def set_train_attn(mode):
+    """Select the arithmetic of the fp32 training attention core ("f32" or "bf16x3"); returns
+    the previous mode."""
+    global _attn_mode
+    old, _attn_mode = _attn_mode, _attn_mode_name(mode, "train attn mode")
+    return old
+
+
+def train_attn():
+    """the current mode of set_train_attn"""
+    return _attn_mode
 
 
 _tls = threading.local()
@@ -205,35 +239,50 @@ def _attn_args(Q, K, V, O, LSE, *, B, H, Nq, Nk, q_strides, k_strides, v_strides
     return a
 
 
-def attn_train_fwd(Q, K, V, O, LSE, **kw):
+def _attn_entries(mode, fp16_inputs):
+    """(workspace_bytes, fwd, bwd) symbol names: ``mode`` (None = the current set_train_attn mode)
+    governs the fp32 core only"""
+    return _ATTN_ENTRY["f32" if fp16_inputs else _attn_mode_name(mode or _attn_mode, "train attn mode")]
+
+
+def _attn_call(entry, a):
+    N._check(getattr(N.lib(), entry)(ctypes.byref(a), N._stream()), entry)
+
+
+def attn_train_fwd(Q, K, V, O, LSE, mode=None, **kw):
     """Returns the workspace (or None): handed to attn_train_bwd(ws=...) for the same Q / K / V,
-    the backward reuses the forward's f16 copies of them (ABI 25 ws_reuse)."""
+    the backward reuses the forward's f16 copies of them (ABI 25 ws_reuse).  ``mode``: see
+    set_train_attn."""
     _f32(Q, K, V, O, LSE)
+    ws_bytes, fwd, _ = _attn_entries(mode, kw.get("fp16_inputs", False))
     a = _attn_args(Q, K, V, O, LSE, **kw)
-    need = N.lib().cmt_attn_train_workspace_bytes(ctypes.byref(a))
+    need = getattr(N.lib(), ws_bytes)(ctypes.byref(a))
     ws = None
     if need > 0:
         ws = torch.empty(need, dtype=torch.uint8, device=O.device)
         a.workspace, a.workspace_bytes = ws.data_ptr(), need
-    N._check(N.lib().cmt_attn_train_fwd(ctypes.byref(a), N._stream()), "cmt_attn_train_fwd")
+    _attn_call(fwd, a)
     return ws
 
 
-def attn_train_bwd(Q, K, V, O, LSE, dO, dQ, dK, dV, ws=None, **kw):
-    """ws: the workspace attn_train_fwd returned for these Q / K / V (unchanged since), or None"""
+def attn_train_bwd(Q, K, V, O, LSE, dO, dQ, dK, dV, ws=None, mode=None, **kw):
+    """ws: the workspace attn_train_fwd returned for these Q / K / V (unchanged since), or None.
+    ``mode``: the one the forward ran with."""
     _f32(Q, K, V, O, LSE, dO, dQ, dK, dV)
+    ws_bytes, _, bwd = _attn_entries(mode, kw.get("fp16_inputs", False))
     a = _attn_args(Q, K, V, O, LSE, **kw)
     delta = torch.empty(kw["B"] * kw["H"] * kw["Nq"], dtype=torch.float32, device=O.device)
     a.dO, a.dQ, a.dK, a.dV, a.delta = dO.data_ptr(), dQ.data_ptr(), dK.data_ptr(), dV.data_ptr(), delta.data_ptr()
-    # the long-key fp16 path takes f16 copies of Q, dO, K, V in the workspace (cmt_hip.h)
-    need = N.lib().cmt_attn_train_workspace_bytes(ctypes.byref(a))
+    # the long-key fp16 path takes f16 copies of Q, dO, K, V in the workspace (cmt_hip.h); the
+    # bf16x3 backward takes none (its size is the forward's key-split partials)
+    need = getattr(N.lib(), ws_bytes)(ctypes.byref(a)) if bwd == "cmt_attn_train_bwd" else 0
     if need > 0:
         if ws is not None and ws.numel() >= need:
             a.ws_reuse = 1
         else:
             ws = torch.empty(need, dtype=torch.uint8, device=O.device)
         a.workspace, a.workspace_bytes = ws.data_ptr(), need
-    N._check(N.lib().cmt_attn_train_bwd(ctypes.byref(a), N._stream()), "cmt_attn_train_bwd")
+    _attn_call(bwd, a)
 
 
 def _ln_args(X, W, Bv, *, C, eps, rows_per_wset=0):

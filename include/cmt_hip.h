@@ -615,6 +615,20 @@ typedef struct cmt_attn_train_args {
 int64_t cmt_attn_train_workspace_bytes(const cmt_attn_train_args* args);
 int cmt_attn_train_fwd(const cmt_attn_train_args* args, void* stream);
 int cmt_attn_train_bwd(const cmt_attn_train_args* args, void* stream);
+/* cmt_attn_train_fwd_bf16x3 / _bwd_bf16x3: the same contract on the same struct
+ * (fp16_inputs must be 0; ws_reuse is ignored) with the arithmetic of
+ * cmt_gemm_bf16x3_ex in place of the 1/16-rate exact-f32 MFMA of the fp32 core:
+ * every product (Q K^T, P V, dO^T P, dO V^T, K^T dS, Q^T dS) takes its fp32
+ * operands split into a bf16 pair (hi + lo, RNE; Q, K, V, dO as they are staged,
+ * P and dS from the fp32 accumulator) and runs as three bf16 MFMA passes
+ * (lo*hi + hi*lo + hi*hi, fp32 accumulate): ~2^-16 relative per product, fp32
+ * exponent range.  Scores, softmax statistics, LSE, delta, dS, the DN mask and
+ * the dropout's kept set are those of the exact-f32 kernels; O is not rounded.
+ * The workspace holds the forward's key-split partials only
+ * (cmt_attn_train_bf16x3_workspace_bytes; CMT_EWORKSPACE with less). */
+int64_t cmt_attn_train_bf16x3_workspace_bytes(const cmt_attn_train_args* args);
+int cmt_attn_train_fwd_bf16x3(const cmt_attn_train_args* args, void* stream);
+int cmt_attn_train_bwd_bf16x3(const cmt_attn_train_args* args, void* stream);
 
 /* Row LayerNorm with saved statistics (C = 64 or 256): nn.LayerNorm
  * (mmcv LN, eps 1e-5) of the decoder and, with C = 64, eps 1e-6 and one weight
