@@ -6,10 +6,10 @@ Importing the package registers the reference's type names
 CmtImageHeadCoop, CmtTransformer, CmtLidarTransformer, CmtImageTransformer,
 PETRTransformerDecoder, PETRTransformerDecoderLayer,
 PETRMultiheadFlashAttention, MultiheadAttention, FFN, SeparateTaskHead,
-MultiTaskBBoxCoder, SPConvVoxelization) so the reference's
+MultiTaskBBoxCoder, SPConvVoxelization, SparseEncoder) so the reference's
 ``pts_bbox_head`` config dicts build unchanged with ``build_head``.
 """
 from . import core, mmcv_custom, models  # noqa: F401
-from .registry import (ATTENTION, BBOX_CODERS, HEADS, TRANSFORMER, TRANSFORMER_LAYER,  # noqa: F401
-                       TRANSFORMER_LAYER_SEQUENCE, build_from_cfg, build_head)
+from .registry import (ATTENTION, BBOX_CODERS, HEADS, MIDDLE_ENCODERS, TRANSFORMER, TRANSFORMER_LAYER,  # noqa: F401
+                       TRANSFORMER_LAYER_SEQUENCE, build_from_cfg, build_head, build_middle_encoder)
 from .runtime import get_precision, set_precision  # noqa: F401

@@ -154,9 +154,36 @@ class Mlp2Args(ctypes.Structure):
                 ("rx", _vp), ("C2", _vp), ("ldc2", _i64), ("c2_bstride", _i64), ("range_flag", _vp)]
 
 
+class SparseIndexArgs(ctypes.Structure):
+    _fields_ = [("B", _int), ("D", _int), ("H", _int), ("W", _int), ("n_cap", _int), ("reserved", _int),
+                ("coors", _vp), ("count", _vp), ("index", _vp), ("index_bytes", _i64)]
+
+
+class SparseRulebookArgs(ctypes.Structure):
+    _fields_ = [("B", _int), ("D", _int), ("H", _int), ("W", _int),
+                ("kernel3", _int * 3), ("stride3", _int * 3), ("padding3", _int * 3),
+                ("K", _int), ("n_cap", _int), ("cap", _int),
+                ("coors", _vp), ("count", _vp), ("index", _vp), ("index_bytes", _i64),
+                ("out_index", _vp), ("out_index_bytes", _i64), ("out_coors", _vp), ("out_count", _vp),
+                ("nbr", _vp)]
+
+
+class SparseConvArgs(ctypes.Structure):
+    _fields_ = [("cap", _int), ("n_in_cap", _int), ("Cin", _int), ("Cout", _int), ("K", _int), ("relu", _int),
+                ("X", _vp), ("ldx", _i64), ("nbr", _vp), ("count", _vp), ("Wp", _vp), ("wp_bytes", _i64),
+                ("scale", _vp), ("shift", _vp), ("R", _vp), ("ldr", _i64), ("Y", _vp), ("ldy", _i64)]
+
+
+class SparseDenseArgs(ctypes.Structure):
+    _fields_ = [("B", _int), ("D", _int), ("H", _int), ("W", _int), ("C", _int), ("n_cap", _int),
+                ("X", _vp), ("ldx", _i64), ("coors", _vp), ("count", _vp), ("out", _vp)]
+
+
 STRUCTS = {"gemm": GemmArgs, "attn": AttnArgs, "ln": LnArgs, "chain": ChainArgs, "gemm_ex": GemmExArgs,
            "attn_train": AttnTrainArgs, "ln_train": LnTrainArgs, "bn": BnArgs, "det_loss": DetLossArgs,
-           "match_cost": MatchCostArgs, "adamw": AdamwArgs, "mlp2": Mlp2Args, "lsap": LsapArgs}
+           "match_cost": MatchCostArgs, "adamw": AdamwArgs, "mlp2": Mlp2Args, "lsap": LsapArgs,
+           "sparse_index": SparseIndexArgs, "sparse_rulebook": SparseRulebookArgs, "sparse_conv": SparseConvArgs,
+           "sparse_dense": SparseDenseArgs}
 
 _LIB = None
 
@@ -240,6 +267,17 @@ def _load():
         "cmt_lsap_workspace_bytes": ([_int, _int, _int], _i64),
         "cmt_lsap": ([P(LsapArgs), _vp], _int),
         "cmt_sumsq": ([_vp, _i64, _vp, _vp], _int),
+        "cmt_sparse_index_args_size": ([], _i64),
+        "cmt_sparse_rulebook_args_size": ([], _i64),
+        "cmt_sparse_conv_args_size": ([], _i64),
+        "cmt_sparse_dense_args_size": ([], _i64),
+        "cmt_sparse_index_bytes": ([_int, _int, _int, _int, _int], _i64),
+        "cmt_sparse_pack_bytes": ([_int, _int, _int], _i64),
+        "cmt_sparse_index": ([P(SparseIndexArgs), _vp], _int),
+        "cmt_sparse_rulebook_subm": ([P(SparseRulebookArgs), _vp], _int),
+        "cmt_sparse_rulebook_down": ([P(SparseRulebookArgs), _vp], _int),
+        "cmt_sparse_conv": ([P(SparseConvArgs), _vp], _int),
+        "cmt_sparse_to_dense": ([P(SparseDenseArgs), _vp], _int),
         "cmt_adamw_step": ([P(AdamwArgs), _vp], _int),
     }
     for name, (args, res) in sig.items():

@@ -15,7 +15,8 @@ import inspect
 
 __all__ = ["Registry", "build_from_cfg", "HEADS", "TRANSFORMER", "ATTENTION", "TRANSFORMER_LAYER",
            "TRANSFORMER_LAYER_SEQUENCE", "FEEDFORWARD_NETWORK", "BBOX_CODERS", "VOXEL_LAYERS",
-           "NORM_LAYERS", "build_head", "build_transformer", "build_bbox_coder"]
+           "NORM_LAYERS", "MIDDLE_ENCODERS", "build_head", "build_transformer", "build_bbox_coder",
+           "build_middle_encoder"]
 
 
 class Registry:
@@ -82,6 +83,7 @@ TRANSFORMER_LAYER = Registry("transformerLayer", parent=MODELS)
 TRANSFORMER_LAYER_SEQUENCE = Registry("transformer-layers sequence", parent=MODELS)
 FEEDFORWARD_NETWORK = Registry("feed-forward Network", parent=MODELS)
 NORM_LAYERS = Registry("norm layer", parent=MODELS)
+MIDDLE_ENCODERS = Registry("middle_encoder", parent=MODELS)
 BBOX_CODERS = Registry("bbox_coder")
 VOXEL_LAYERS = Registry("voxel_layer")
 
@@ -96,3 +98,7 @@ def build_transformer(cfg, **kw):
 
 def build_bbox_coder(cfg, **kw):
     return build_from_cfg(cfg, BBOX_CODERS, kw or None)
+
+
+def build_middle_encoder(cfg, **kw):
+    return build_from_cfg(cfg, MIDDLE_ENCODERS, kw or None)

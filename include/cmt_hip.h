@@ -763,6 +763,95 @@ typedef struct cmt_adamw_args {
 } cmt_adamw_args;
 int cmt_adamw_step(const cmt_adamw_args* args, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Sparse 3-D convolution (additive to ABI 25): the spconv half of mmdet3d's
+ * SparseEncoder (pts_middle_encoder, models/detectors/cmt.py:78-86 of the
+ * reference), inference only.  Rows are active sites: coors [n][4] int32
+ * (b, z, y, x) and fp32 feature rows; every row count is an int32 in DEVICE
+ * memory (a negative count reads as 0), buffers and launch grids are sized by a
+ * host-side capacity, and no call synchronises with the host.
+ *
+ * Site index (cmt_sparse_index): for a grid (B, D, H, W) with B*D*H*W < 2^31
+ * (CMT_EINVAL beyond) one bit per site, the number of set bits before each
+ * 32-bit word, and a rank -> row table, so that "which row is site (b,z,y,x)"
+ * is two loads and a popcount.  The table makes any row order valid (the
+ * voxelizer emits first-appearance order); of several rows with equal
+ * coordinates the lowest row index answers.  Rows outside the grid are ignored.
+ * cmt_sparse_index_bytes(B, D, H, W, cap): ~ B*D*H*W / 4 + 4 cap bytes (21 MB for
+ * one 41 x 1440 x 1440 sample); 0 for an invalid grid.
+ *
+ * Rulebooks.  K = kD*kH*kW taps, tap k = (kz*kH + ky)*kW + kx, nbr [rows][K]
+ * int32, -1 where the neighbour is inactive or outside the grid.
+ *   cmt_sparse_rulebook_subm (SubMConv3d: odd kernel3, stride 1, padding
+ *     kernel3/2): nbr[m][k] = row of coors[m] + (kz,ky,kx) - padding3.  Output
+ *     rows are the input rows.  Writes all n_cap rows (-1 beyond the count).
+ *   cmt_sparse_rulebook_down (SparseConv3d, per-axis kernel3/stride3/padding3):
+ *     output extent (n + 2p - k)/s + 1 per axis; an output site is active iff an
+ *     active input lies in its window.  Writes out_coors [cap][4] in ascending
+ *     (b, z, y, x) order -- independent of the input row order --, out_count (-1
+ *     when more than cap outputs exist: nothing else is then valid), nbr
+ *     [cap][K] with nbr[m][k] = row of out*stride3 - padding3 + (kz,ky,kx), and
+ *     builds out_index (capacity cap) for the output set, so the next stage needs
+ *     no cmt_sparse_index call.
+ *
+ * cmt_sparse_conv: Y[m] = act(scale * sum_k X[nbr[m][k]] W[k] + shift (+ R[m])),
+ * fp32 rows in and out, Cin, Cout <= 128, K <= 27, for the first *count rows
+ * (count <= cap).  nbr entries outside [0, n_in_cap) count as -1.  Arithmetic:
+ * each operand split hi = bf16(x), lo = bf16(x - hi), products lo*hi + hi*lo +
+ * hi*hi on v_mfma_f32_32x32x16_bf16 with fp32 accumulation in fixed tap order
+ * (no atomics: bit-reproducible; fp32 exponent range, ~2^-16 relative per
+ * product).  Wp is the packed weight image of cmt_sparse_pack_bytes(K, Cin, Cout)
+ * bytes: bf16 [K][KC][NB][2][64][8] with KC = ceil(Cin/16), NB = ceil(Cout/32),
+ * [.][.][.][0] the hi and [1] the lo parts, element [l][j] = W[k][cin = 16 kc +
+ * 8 (l >> 5) + j][cout = 32 nb + (l & 31)], zero beyond Cin / Cout.
+ *
+ * cmt_sparse_to_dense: out [B, C*D, H, W] fp32 (spconv's .dense() [B,C,D,H,W]
+ * viewed as the reference does), zero-filled here, out[b][c*D + z][y][x] = X[m][c]. */
+typedef struct cmt_sparse_index_args {
+    int B, D, H, W;
+    int n_cap, reserved;
+    const int* coors; const int* count;
+    void* index; int64_t index_bytes;
+} cmt_sparse_index_args;
+typedef struct cmt_sparse_rulebook_args {
+    int B, D, H, W;                               /* the input grid */
+    int kernel3[3], stride3[3], padding3[3];
+    int K;                                        /* kD*kH*kW */
+    int n_cap;                                    /* input rows (capacity of coors and of index) */
+    int cap;                                      /* down: capacity of the outputs */
+    const int* coors; const int* count;
+    const void* index; int64_t index_bytes;       /* the input set's index */
+    void* out_index; int64_t out_index_bytes;     /* down */
+    int* out_coors; int* out_count;               /* down */
+    int* nbr;                                     /* subm [n_cap][K]; down [cap][K] */
+} cmt_sparse_rulebook_args;
+typedef struct cmt_sparse_conv_args {
+    int cap, n_in_cap, Cin, Cout, K, relu;
+    const float* X; int64_t ldx;
+    const int* nbr; const int* count;
+    const void* Wp; int64_t wp_bytes;
+    const float* scale; const float* shift;       /* [Cout] */
+    const float* R; int64_t ldr;                  /* optional residual rows */
+    float* Y; int64_t ldy;
+} cmt_sparse_conv_args;
+typedef struct cmt_sparse_dense_args {
+    int B, D, H, W, C, n_cap;
+    const float* X; int64_t ldx;
+    const int* coors; const int* count;
+    float* out;
+} cmt_sparse_dense_args;
+int64_t cmt_sparse_index_args_size(void);
+int64_t cmt_sparse_rulebook_args_size(void);
+int64_t cmt_sparse_conv_args_size(void);
+int64_t cmt_sparse_dense_args_size(void);
+int64_t cmt_sparse_index_bytes(int B, int D, int H, int W, int cap);
+int64_t cmt_sparse_pack_bytes(int K, int Cin, int Cout);
+int cmt_sparse_index(const cmt_sparse_index_args* args, void* stream);
+int cmt_sparse_rulebook_subm(const cmt_sparse_rulebook_args* args, void* stream);
+int cmt_sparse_rulebook_down(const cmt_sparse_rulebook_args* args, void* stream);
+int cmt_sparse_conv(const cmt_sparse_conv_args* args, void* stream);
+int cmt_sparse_to_dense(const cmt_sparse_dense_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
