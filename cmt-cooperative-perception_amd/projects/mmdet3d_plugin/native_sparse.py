@@ -38,10 +38,23 @@ def index_bytes(grid, cap):
 
 
 def _coors(coors):
-    _dev(coors)
     if coors.dtype != torch.int32 or coors.dim() != 2 or coors.shape[1] != 4 or not coors.is_contiguous():
         raise ValueError("coors must be a contiguous int32 [n, 4] tensor (b, z, y, x)")
+    _dev(coors)
     return coors
+
+
+def _rows(name, t, rows, cols):
+    """an fp32 operand the kernels index as t[row * stride(0) + col], row < rows, col < cols"""
+    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] < rows or t.shape[1] < cols or \
+            (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < cols):
+        raise ValueError(f"{name} must be fp32 rows [>= {rows}, >= {cols}] with unit column stride, got "
+                         f"{t.dtype} {tuple(t.shape)} strides {tuple(t.stride())}")
+
+
+def _per_channel(name, t, n):
+    if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < n:
+        raise ValueError(f"{name} must be contiguous fp32 of at least {n} elements")
 
 
 def _count(count, dev):
@@ -131,14 +144,22 @@ def pack_weight(w):
 
 def conv(X, nbr, count, Wp, scale, shift, *, Cin, Cout, relu=True, R=None, out=None):
     """Y[m] = act(scale * sum_k X[nbr[m][k]] W[k] + shift (+ R[m])) for m < count: fp32 rows [cap, Cout]."""
-    _dev(X, nbr, count, Wp, scale, shift, R, out)
+    if nbr.dim() != 2 or nbr.dtype != torch.int32 or not nbr.is_contiguous():
+        raise ValueError("nbr must be a contiguous int32 [rows, K] tensor")
     cap, K = int(nbr.shape[0]), int(nbr.shape[1])
     if X.dtype != torch.float32 or X.dim() != 2 or X.stride(1) != 1 or X.shape[1] < Cin:
         raise ValueError("X must be fp32 rows [n, >= Cin] with unit column stride")
-    if nbr.dtype != torch.int32 or not nbr.is_contiguous():
-        raise ValueError("nbr must be a contiguous int32 [rows, K] tensor")
+    if X.shape[0] == 0 and nbr.numel() > 0:
+        raise ValueError("X has no rows but nbr is not empty")
     if Wp.dtype != torch.bfloat16 or not Wp.is_contiguous():
         raise ValueError("Wp must be the contiguous bf16 image of pack_weight")
+    _per_channel("scale", scale, Cout)
+    _per_channel("shift", shift, Cout)
+    if R is not None:
+        _rows("R", R, cap, Cout)
+    if out is not None:
+        _rows("out", out, cap, Cout)
+    _dev(X, nbr, count, Wp, scale, shift, R, out)
     Y = out if out is not None else torch.empty((max(cap, 1), Cout), dtype=torch.float32, device=X.device)
     if cap == 0:
         return Y[:0]
@@ -156,6 +177,9 @@ def conv(X, nbr, count, Wp, scale, shift, *, Cin, Cout, relu=True, R=None, out=N
 
 def to_dense(X, coors, count, grid, C):
     """Rows -> [B, C * D, H, W] fp32 (zero elsewhere), channel-major then depth as the reference's view."""
+    if coors.dim() != 2:
+        raise ValueError("coors must be a contiguous int32 [n, 4] tensor (b, z, y, x)")
+    _rows("X", X, int(coors.shape[0]), int(C))
     coors = _coors(coors)
     _dev(X, count)
     B, D, H, W = [int(g) for g in grid]

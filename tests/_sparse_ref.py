@@ -1,5 +1,5 @@
 """Float64 restatement of spconv's sparse 3-D convolutions and of mmdet3d's SparseEncoder for the
-tests (tests/test_sparse_host.py, tests/test_gpu_sparse.py), on the CPU: densify the rows, run
+tests (tests/test_sparse_host.py, tests/test_gpu_sparse.py, tests/test_gpu_sparse_edges.py), on the CPU: densify the rows, run
 torch.nn.functional.conv3d in double, mask.  The active mask of a strided convolution is
 ``conv3d(mask, ones, stride, padding) > 0``; BN uses the running statistics.  The rulebook
 restatement is a coordinate -> row dictionary.  Nothing here touches the native library."""
@@ -15,6 +15,10 @@ REF_ENCODER_CFG = dict(
 
 # the strided forms of the reference encoder: (kernel, stride, padding)
 DOWN_FORMS = {"k3s2p1": (3, 2, 1), "k3s2p011": (3, 2, (0, 1, 1)), "k311s211p0": ((3, 1, 1), (2, 1, 1), 0)}
+# further forms the C entry points accept (tests/test_gpu_sparse_edges.py).  In k3s2p0, k2s2p0, k3s3p0 and k1s2p0
+# some inputs of the (9, 16, 24) active set lie in no window; k3s1p1 grows the set twelvefold.
+MORE_FORMS = {"k3s2p0": (3, 2, 0), "k2s2p0": (2, 2, 0), "k3s3p0": (3, 3, 0), "k3s1p1": (3, 1, 1),
+              "k133s122p011": ((1, 3, 3), (1, 2, 2), (0, 1, 1)), "k3s2p2": (3, 2, 2), "k1s2p0": (1, 2, 0)}
 
 
 def triple(v):
@@ -119,6 +123,54 @@ def nbr_down(coors, out_coors, kernel, stride, padding):
     return torch.tensor(out, dtype=torch.int32).reshape(len(out), k[0] * k[1] * k[2])
 
 
+def _taps(k):
+    return [(kz, ky, kx) for kz in range(k[0]) for ky in range(k[1]) for kx in range(k[2])]
+
+
+def nbr_table(coors, grid, kernel=3, out_coors=None, stride=1, padding=None):
+    """nbr_subm (and, with ``out_coors``, nbr_down) without a Python loop over rows: a padded int64 table of
+    row numbers, -1 elsewhere, gathered at the K shifted positions.  Equal coordinates: the lowest row."""
+    B, D, H, W = grid
+    k, s = triple(kernel), triple(stride)
+    p = tuple(v // 2 for v in k) if padding is None else triple(padding)
+    c = coors.long()
+    Dp, Hp, Wp = D + 2 * p[0], H + 2 * p[1], W + 2 * p[2]
+    site = ((c[:, 0] * Dp + c[:, 1] + p[0]) * Hp + c[:, 2] + p[1]) * Wp + c[:, 3] + p[2]
+    table = torch.full((B * Dp * Hp * Wp,), -1, dtype=torch.int64)
+    table.scatter_reduce_(0, site, torch.arange(c.shape[0]), "amin", include_self=False)
+    table = table.view(B, Dp, Hp, Wp)
+    q = c if out_coors is None else out_coors.long()
+    b, z, y, x = q[:, 0], q[:, 1] * s[0], q[:, 2] * s[1], q[:, 3] * s[2]   # window start, in padded coordinates
+    cols = [table[b, z + kz, y + ky, x + kx] for kz, ky, kx in _taps(k)]
+    return torch.stack(cols, 1).to(torch.int32)
+
+
+def down_coors(coors, shape, kernel, stride, padding):
+    """The output coordinates of a strided convolution from the input coordinates alone (no dense tensor):
+    every (c + p - kk) that is non-negative, divisible by the stride and inside out_shape; unique, ascending."""
+    k, s, p = triple(kernel), triple(stride), triple(padding)
+    c = coors.long()
+    out = out_shape(shape, k, s, p)
+    st, lim = torch.tensor(s), torch.tensor(out)
+    found = []
+    for kk in _taps(k):
+        t = c[:, 1:] + torch.tensor(p) - torch.tensor(kk)
+        o = torch.div(t, st, rounding_mode="floor")
+        ok = (t >= 0).all(1) & (o * st == t).all(1) & (o < lim).all(1)
+        b, o = c[ok, 0], o[ok]
+        found.append(((b * out[0] + o[:, 0]) * out[1] + o[:, 1]) * out[2] + o[:, 2])   # ascending = (b, z, y, x)
+    site = torch.unique(torch.cat(found))
+    cols = [site // (out[0] * out[1] * out[2]), site // (out[1] * out[2]) % out[0], site // out[2] % out[1],
+            site % out[2]]
+    return torch.stack(cols, 1).to(torch.int32)
+
+
+def rows_in_no_window(coors, out_coors, kernel, stride, padding):
+    """how many input rows no output row's window holds (nbr_down names them nowhere)"""
+    named = nbr_down(coors, out_coors, kernel, stride, padding)
+    return coors.shape[0] - torch.unique(named[named >= 0]).numel()
+
+
 def conv_rows(feats, nbr, w, scale=None, shift=None, residual=None, relu=True):
     """The same convolution evaluated only at the rows of a rulebook (no dense tensor): float64 [rows, Cout]"""
     K = nbr.shape[1]
@@ -129,6 +181,33 @@ def conv_rows(feats, nbr, w, scale=None, shift=None, residual=None, relu=True):
     y = torch.zeros((nbr.shape[0], w.shape[0]), dtype=torch.float64)
     for k in range(K):
         y += x[idx[:, k]] @ wk[:, k].t()
+    if scale is not None:
+        y = y * scale.double() + shift.double()
+    if residual is not None:
+        y = y + residual.double()
+    return torch.relu(y) if relu else y
+
+
+def _split_bf16(t):
+    t32 = t.float()
+    hi = t32.bfloat16().float()
+    lo = (t32 - hi).bfloat16().float()       # t32 - hi is exact in fp32
+    return hi.double(), lo.double()
+
+
+def conv_rows_x3(feats, nbr, w, scale=None, shift=None, residual=None, relu=True):
+    """conv_rows on the kernel's three-pass arithmetic, in float64: hi = bf16(x) RNE, lo = bf16(x - hi) of both
+    operands, every product lo*hi + hi*lo + hi*hi (lo*lo dropped), sums and epilogue exact."""
+    K = nbr.shape[1]
+    wh, wl = _split_bf16(w.reshape(w.shape[0], K, w.shape[-1]))   # [Cout][K][Cin]
+    zero = torch.zeros((1, feats.shape[1]), dtype=torch.float64)
+    xh, xl = (torch.cat([t, zero], 0) for t in _split_bf16(feats))
+    idx = nbr.long()
+    idx = torch.where(idx < 0, torch.full_like(idx, feats.shape[0]), idx)
+    y = torch.zeros((nbr.shape[0], w.shape[0]), dtype=torch.float64)
+    for k in range(K):
+        h, l = xh[idx[:, k]], xl[idx[:, k]]
+        y += l @ wh[:, k].t() + h @ wl[:, k].t() + h @ wh[:, k].t()
     if scale is not None:
         y = y * scale.double() + shift.double()
     if residual is not None:

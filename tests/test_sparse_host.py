@@ -258,3 +258,121 @@ def test_pack_weight_index_map():
         hi, lo = f[k, 0, nb, 0, lane, j].item(), f[k, 0, nb, 1, lane, j].item()
         assert hi == torch.tensor(want).bfloat16().item()
         assert abs(hi + lo - want) <= 2.0 ** -16 * abs(want)
+
+
+# ---- the restatement's own helpers (tests/_sparse_ref.py), used by tests/test_gpu_sparse_edges.py ------------
+
+def test_vectorised_restatement_matches_the_dictionary_one():
+    """nbr_table against nbr_subm / nbr_down and down_coors against the dense mask, on the (2, 9, 16, 24)
+    active set and every strided form; the figures the GPU tests rely on as preconditions."""
+    import _sparse_ref as R
+    shape, B = (9, 16, 24), 2
+    grid = (B,) + shape
+    coors = R.active_set(shape, B)[:300]
+    assert coors.shape[0] == 300
+    for kernel in (3, (1, 3, 3), (3, 1, 3), 1):
+        assert torch.equal(R.nbr_table(coors, grid, kernel), R.nbr_subm(coors, kernel)), kernel
+    _, mask = R.densify(torch.zeros(300, 1), coors, grid)
+    outputs = {"k3s2p1": 503, "k3s2p011": 434, "k311s211p0": 349, "k3s2p0": 362, "k2s2p0": 195, "k3s3p0": 145,
+               "k3s1p1": 3717, "k133s122p011": 442, "k3s2p2": 621, "k1s2p0": 45}
+    outside = {"k3s2p0": 51, "k2s2p0": 39, "k3s3p0": 29, "k1s2p0": 255}
+    forms = {**R.DOWN_FORMS, **R.MORE_FORMS}
+    assert set(forms) == set(outputs)
+    for name, (k, s, p) in forms.items():
+        want = R.mask_coors(R.down_mask(mask, k, s, p))
+        got = R.down_coors(coors, shape, k, s, p)
+        assert got.dtype == torch.int32 and torch.equal(got, want), name
+        assert want.shape[0] == outputs[name], name
+        assert torch.equal(R.nbr_table(coors, grid, k, want, s, p), R.nbr_down(coors, want, k, s, p)), name
+        assert R.rows_in_no_window(coors, want, k, s, p) == outside.get(name, 0), name
+    # rows 200..299 are neighbours of earlier rows: dropping them changes 111 entries of the first 200 rows
+    assert (R.nbr_subm(coors)[:200] != R.nbr_subm(coors[:200])).sum().item() == 111
+
+
+def test_restatement_duplicates_resolve_to_the_lowest_row():
+    import _sparse_ref as R
+    grid = (2, 9, 16, 24)
+    base = R.active_set(grid[1:], 2)[:300]
+    pick = torch.arange(7, 300, 15)[:20]
+    ref = R.nbr_subm(base)
+    got = R.nbr_table(torch.cat([base, base[pick]]), grid)
+    assert torch.equal(got[:300], ref) and torch.equal(got[300:], ref[pick])
+
+
+def test_conv_rows_x3_is_the_three_pass_arithmetic():
+    import _sparse_ref as R
+    g = torch.Generator().manual_seed(8)
+    x, w = torch.randn(50, 20, generator=g), torch.randn(33, 9, 1, 1, 20, generator=g)
+    nbr = torch.randint(-1, 50, (40, 9), generator=g).to(torch.int32)
+    want, got = R.conv_rows(x, nbr, w, relu=False), R.conv_rows_x3(x, nbr, w, relu=False)
+    err = (got - want).abs().max().item()
+    assert 0 < err <= 2.0 ** -15 * (9 * 20) ** 0.5 * 4               # not exact, well inside the kernels' bound
+    # operands that are bf16 already have no lo part: the emulation is exact on them
+    xb, wb = x.bfloat16().float(), w.bfloat16().float()
+    assert torch.equal(R.conv_rows_x3(xb, nbr, wb, relu=False), R.conv_rows(xb, nbr, wb, relu=False))
+    # the epilogue is conv_rows'
+    sc, sh, res = 0.5 + torch.rand(33, generator=g), torch.randn(33, generator=g), torch.randn(40, 33, generator=g)
+    full = R.conv_rows_x3(x, nbr, w, sc, sh, res)
+    assert torch.equal(full, torch.relu(got * sc.double() + sh.double() + res.double()))
+
+
+# ---- the wrappers refuse operands the kernels would index out of bounds, before the device check -------------
+
+def _conv_call(**over):
+    from projects.mmdet3d_plugin import native_sparse as S
+    kw = dict(X=torch.zeros(4, 16), nbr=torch.zeros(6, 27, dtype=torch.int32), count=torch.zeros(1, dtype=torch.int32),
+              Wp=S.pack_weight(torch.zeros(24, 3, 3, 3, 16)), scale=torch.zeros(24), shift=torch.zeros(24), R=None,
+              out=None)
+    kw.update(over)
+    return S.conv(kw["X"], kw["nbr"], kw["count"], kw["Wp"], kw["scale"], kw["shift"], Cin=16, Cout=24, R=kw["R"],
+                  out=kw["out"])
+
+
+@pytest.mark.parametrize("name", ["out", "R"])
+def test_conv_refuses_a_malformed_out_or_residual(name):
+    for bad in (torch.zeros(6, 24, dtype=torch.float64), torch.zeros(6, 24, dtype=torch.bfloat16),
+                torch.zeros(5, 24), torch.zeros(6, 23), torch.zeros(6, 48)[:, ::2], torch.zeros(24, 6).t(),
+                torch.zeros(6 * 24)):
+        with pytest.raises(ValueError, match=name):
+            _conv_call(**{name: bad})
+    for good in (torch.zeros(6, 24), torch.zeros(9, 40)[:, 3:27], torch.zeros(6, 24)[:, :24]):
+        with pytest.raises(RuntimeError, match="HIP device"):          # well-formed: only the device is missing
+            _conv_call(**{name: good})
+
+
+@pytest.mark.parametrize("name", ["scale", "shift"])
+def test_conv_refuses_a_malformed_scale_or_shift(name):
+    for bad in (torch.zeros(23), torch.zeros(24, dtype=torch.float64), torch.zeros(48)[::2], torch.zeros(0)):
+        with pytest.raises(ValueError, match=name):
+            _conv_call(**{name: bad})
+    with pytest.raises(RuntimeError, match="HIP device"):
+        _conv_call(**{name: torch.zeros(32)})
+
+
+def test_conv_refuses_a_malformed_rulebook_or_input():
+    with pytest.raises(ValueError, match="nbr"):
+        _conv_call(nbr=torch.zeros(6 * 27, dtype=torch.int32))
+    with pytest.raises(ValueError, match="nbr"):
+        _conv_call(nbr=torch.zeros(6, 2, 27, dtype=torch.int32))
+    with pytest.raises(ValueError, match="nbr"):
+        _conv_call(nbr=torch.zeros(6, 27, dtype=torch.int64))
+    with pytest.raises(ValueError, match="no rows"):
+        _conv_call(X=torch.zeros(0, 16))
+    with pytest.raises(ValueError, match="X must"):
+        _conv_call(X=torch.zeros(4, 15))
+    with pytest.raises(RuntimeError, match="HIP device"):
+        _conv_call()
+
+
+def test_to_dense_refuses_a_malformed_input():
+    from projects.mmdet3d_plugin import native_sparse as S
+    coors, count = torch.zeros(6, 4, dtype=torch.int32), torch.zeros(1, dtype=torch.int32)
+    for bad in (torch.zeros(6, 8, dtype=torch.float64), torch.zeros(6, 8, dtype=torch.float16), torch.zeros(5, 8),
+                torch.zeros(6, 7), torch.zeros(6, 16)[:, ::2], torch.zeros(8, 6).t(), torch.zeros(48)):
+        with pytest.raises(ValueError, match="X must"):
+            S.to_dense(bad, coors, count, (1, 4, 4, 4), 8)
+    with pytest.raises(ValueError, match="coors"):
+        S.to_dense(torch.zeros(6, 8), coors.long(), count, (1, 4, 4, 4), 8)
+    for good in (torch.zeros(6, 8), torch.zeros(9, 12)[:, 2:10]):
+        with pytest.raises(RuntimeError, match="HIP device"):
+            S.to_dense(good, coors, count, (1, 4, 4, 4), 8)
