@@ -30,6 +30,10 @@
 // fused camera rows, profiles/r6_experiments.txt r6j).  One wave per SIMD: the 8 output
 // accumulator tiles (128 registers), the A fragments (96 at K = 192) and the
 // hidden tile need the whole 512-register file.
+//
+// The camera rows' default form is cmt_mlp2_affine (mlp2_affine_kernel below): the frustum
+// coordinates are affine in the pixel, so fc1 over them is two FMAs per hidden unit with
+// per-camera coefficients and only fc2 runs on the matrix pipe; the epilogues are shared.
 #include "cmt_common.h"
 
 #include <type_traits>
@@ -50,6 +54,136 @@ __device__ __forceinline__ f32x16 mma3(const pair8_t& wh, const pair8_t& wl, con
     acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xl, acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl, xh, acc, 0, 0, 0);
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xh, acc, 0, 0, 0);
+}
+
+#ifndef CMT_MLP_DIAG
+#define CMT_MLP_DIAG 0   // dev diagnostics (wrong results): 1 no C2 stores, 2 no NCHW loads, 4 no coordinates,
+                         // 8 no weight DMA after the prologue
+#endif
+
+// ---- the epilogues, shared by the GEMM form (mlp2_x3_kernel) and the affine form
+// (mlp2_affine_kernel).  Both hold the output as oacc[ot][4 g + e]: row lr = lane & 31, column
+// 32 ot + 8 g + 4 lh + e (lh = lane >> 5).
+
+// RX: the 256 NCHW feature values of the lane's row (view image gimg, pixel gpix of ghw)
+__device__ __forceinline__ void rx_load(const cmt_mlp2_args& a, int gimg, int gpix, int ghw, int lh,
+                                        float (&xv)[4][2][4][4]) {
+    const float* const xrow = a.rx + (int64_t)gimg * NOUT * ghw + gpix;
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    xv[q][tt][g][e] = (CMT_MLP_DIAG & 2) ? 0.f
+                                                         : xrow[(int64_t)((2 * q + tt) * 32 + 8 * g + 4 * lh + e) * ghw];
+}
+__device__ __forceinline__ void rx_load(const cmt_mlp2_args&, int, int, int, int, float (&)[1][2][4][4]) {}
+
+// The fused camera rows: the memory-row pair (C2) from the NCHW features and
+// out = acc + (b2 + pair value) (C), both staged through LDS per column quarter so every
+// global store is 16 contiguous bytes of a 128-byte row segment (8 lanes per row).  lds: the
+// workgroup's weight rings (at least 64 KB), which become the staging once every wave is past them
+__device__ __forceinline__ void rx_epilogue(const cmt_mlp2_args& a, char* lds, const f32x16 (&oacc)[NOT],
+                                            const float (&xv)[4][2][4][4]) {
+    const int lane = threadIdx.x & 63, lr = lane & 31, lh = lane >> 5;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int z = blockIdx.y;
+    __syncthreads();   // every wave is past its last weight-ring read: the rings become staging
+    char* const stg = lds + wave * 16384;            // 4 slices [32 rows][64 cols] f16: C hi / lo, C2 hi / lo
+    const int mw0 = blockIdx.x * MROWS + wave * 32;  // the wave's first row
+    bool bad = false;
+    typedef pair_t p4 __attribute__((ext_vector_type(4)));
+    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+    auto sw = [](int r, int c16) { return r * 128 + ((c16 ^ ((r >> 1) & 7)) << 4); };
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int ot = 2 * q + tt;
+                const int n = ot * 32 + 8 * g + 4 * lh;
+                const f32x4 bv = *(const f32x4*)(a.b2 + n);
+                p4 h2, l2, hc, lc;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    // the pair cmt_nchw_to_rows writes, and its value as the pair R row reads back
+                    const float x = xv[q][tt][g][e];
+                    bad |= f16_unrepresentable(x);
+                    h2[e] = (pair_t)x;
+                    l2[e] = (pair_t)(x - (float)h2[e]);
+                    const float rv = (float)h2[e] + (float)l2[e];
+                    const float v = oacc[ot][4 * g + e] + (bv[e] + rv);
+                    hc[e] = (pair_t)v;
+                    lc[e] = (pair_t)(v - (float)hc[e]);
+                }
+                const int off = sw(lr, 4 * tt + g) + 8 * lh;
+                *(p4*)(stg + off) = hc;
+                *(p4*)(stg + 4096 + off) = lc;
+                *(p4*)(stg + 8192 + off) = h2;
+                *(p4*)(stg + 12288 + off) = l2;
+            }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int r = 8 * i + (lane >> 3), ch = lane & 7;
+            const int mr = mw0 + r;
+            const int off = sw(r, ch);
+            const u4 v0 = *(const u4*)(stg + off), v1 = *(const u4*)(stg + 4096 + off);
+            const u4 v2 = *(const u4*)(stg + 8192 + off), v3 = *(const u4*)(stg + 12288 + off);
+            if (mr < a.M && !(CMT_MLP_DIAG & 1)) {
+                pair_t* cr = (pair_t*)a.C + (int64_t)z * a.c_bstride + (int64_t)mr * a.ldc + 64 * q + 8 * ch;
+                pair_t* c2 = (pair_t*)a.C2 + (int64_t)z * a.c2_bstride + (int64_t)mr * a.ldc2 + 64 * q + 8 * ch;
+                *(u4*)cr = v0;
+                *(u4*)(cr + NOUT) = v1;
+                *(u4*)c2 = v2;
+                *(u4*)(c2 + NOUT) = v3;
+            }
+        }
+    }
+    raise_range_flag(a.range_flag, bad);
+}
+__device__ __forceinline__ void rx_epilogue(const cmt_mlp2_args&, char*, const f32x16 (&)[NOT],
+                                            const float (&)[1][2][4][4]) {}
+
+// out = acc + (b2 + R) (cmt_gemm's order) for row m (row = min(m, M - 1))
+__device__ __forceinline__ void rows_epilogue(const cmt_mlp2_args& a, int m, int row, const f32x16 (&oacc)[NOT]) {
+    const int lh = (threadIdx.x & 63) >> 5;
+    const int z = blockIdx.y;
+    if (m >= a.M) return;
+    const char* Rrow = nullptr;
+    if (a.R) {
+        const int resz = a.r_dtype == CMT_F32 ? 4 : 2;
+        Rrow = (const char*)a.R + ((int64_t)z * a.r_bstride + (int64_t)row * a.ldr) * resz;
+    }
+    const int cesz = a.c_dtype == CMT_F32 ? 4 : 2;
+    char* Crow = (char*)a.C + ((int64_t)z * a.c_bstride + (int64_t)row * a.ldc) * cesz;
+    typedef pair_t p4 __attribute__((ext_vector_type(4)));
+#pragma unroll
+    for (int ot = 0; ot < NOT; ++ot)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int n = ot * 32 + 8 * g + 4 * lh;
+            const f32x4 bv = *(const f32x4*)(a.b2 + n);
+            f32x4 rv = {0.f, 0.f, 0.f, 0.f};
+            if (Rrow) {
+                if (a.r_dtype == CMT_F32) {
+                    rv = *(const f32x4*)((const float*)Rrow + n);
+                } else {
+                    const p4 h = *(const p4*)((const pair_t*)Rrow + n);
+                    const p4 l = *(const p4*)((const pair_t*)Rrow + NOUT + n);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) rv[e] = (float)h[e] + (float)l[e];
+                }
+            }
+            f32x4 v;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = oacc[ot][4 * g + e] + (bv[e] + rv[e]);
+            if (a.c_dtype == CMT_F32) *(f32x4*)((float*)Crow + n) = v;
+            else store_pair4((pair_t*)Crow, NOUT, n, v);
+        }
 }
 
 // KS = K / 16; PD = the LDS fragment prefetch distance in steps (3: same time, 4: +8 %,
@@ -99,10 +233,6 @@ __global__ __launch_bounds__(64 * MW, 1) void mlp2_x3_kernel(cmt_mlp2_args a) {
     const int ghw = GEO || RX ? a.geo_h * a.geo_w : 1;
     const int gview = row / ghw, gpix = row - gview * ghw;      // GEO / RX: view and pixel of the row
     const int gimg = z * (a.M / ghw) + gview;
-#ifndef CMT_MLP_DIAG
-#define CMT_MLP_DIAG 0   // dev diagnostics (wrong results): 1 no C2 stores, 2 no NCHW loads, 4 no coordinates,
-                         // 8 no weight DMA after the prologue
-#endif
     if constexpr (GEO && (CMT_MLP_DIAG & 4)) {
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) { ah[ks] = pair8_t{}; al[ks] = pair8_t{}; }
@@ -262,119 +392,222 @@ __global__ __launch_bounds__(64 * MW, 1) void mlp2_x3_kernel(cmt_mlp2_args a) {
     barrier_mem();
     // RX: the row's 256 NCHW feature values are loaded here, into the registers fc1's A operand
     // held, so their memory round trip runs under the last block's fc2 instead of the epilogue's
-    const float* const xrow = RX ? a.rx + (int64_t)gimg * NOUT * ghw + gpix : nullptr;
     float xv[RX ? 4 : 1][2][4][4];
-    if constexpr (RX) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-                for (int g = 0; g < 4; ++g)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        xv[q][tt][g][e] = (CMT_MLP_DIAG & 2) ? 0.f
-                                                             : xrow[(int64_t)((2 * q + tt) * 32 + 8 * g + 4 * lh + e) * ghw];
-    }
+    if constexpr (RX) rx_load(a, gimg, gpix, ghw, lh, xv);
     fc2_fc1(nhb - 1, std::false_type{});   // the last block: fc2 only
 
-    if constexpr (RX) {
-        // ---- fused camera rows: the memory-row pair (C2) from the NCHW features and
-        // out = acc + (b2 + pair value) (C), both staged through LDS per column quarter so every
-        // global store is 16 contiguous bytes of a 128-byte row segment (8 lanes per row)
-        __syncthreads();   // every wave is past its last weight-ring read: the rings become staging
-        char* const stg = lds + wave * 16384;            // 4 slices [32 rows][64 cols] f16: C hi / lo, C2 hi / lo
-        const int mw0 = blockIdx.x * MROWS + wave * 32;  // the wave's first row
-        bool bad = false;
-        typedef pair_t p4 __attribute__((ext_vector_type(4)));
-        typedef uint32_t u4 __attribute__((ext_vector_type(4)));
-        auto sw = [](int r, int c16) { return r * 128 + ((c16 ^ ((r >> 1) & 7)) << 4); };
+    if constexpr (RX) rx_epilogue(a, lds, oacc, xv);
+    else rows_epilogue(a, m, row, oacc);
+}
+
+// ---- the affine form (cmt_mlp2_affine, cmt_hip.h): the frustum coordinates are affine in the
+// pixel and nothing nonlinear stands before fc1, so hidden unit j of a row of view b is
+// relu(alpha_bj u + beta_bj v + gamma_bj): no fc1 GEMM, no coordinates.  The workgroup contracts
+// the weight-only tables with the inverse camera matrices of the views its rows lie in (float64,
+// rounded to fp32 into LDS); a wave's 32 rows lie in one view (h w % 32 == 0), so each hidden
+// block's 16 coefficient triples per lane half are broadcast LDS reads.  fc2, the W2 ring and the
+// epilogues are the GEMM form's.  The two FMAs and the pair split of block hb + 1's hidden tile
+// run one unit per MFMA step inside block hb's fc2 stream, in the matrix pipe's shadow.
+constexpr int AFF_MAX_HD = 1024;    // hidden width bound (coefficient tables in LDS)
+constexpr int AFF_VIEWS = MROWS / 32;   // views a workgroup's rows can lie in
+
+template <bool RX, int PD = 2>
+__global__ __launch_bounds__(64 * MW, 1) void mlp2_affine_kernel(cmt_mlp2_affine_args aa) {
+    const cmt_mlp2_args& a = aa.m;
+    __shared__ __attribute__((aligned(16))) char lds[2 * W2_BLK + AFF_VIEWS * 3 * AFF_MAX_HD * 4];
+    char* const s2 = lds;                                  // W2 ring: 2 x W2_BLK
+    float* const sco = (float*)(lds + 2 * W2_BLK);         // [view slot][alpha, beta, gamma][AFF_MAX_HD]
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lr = lane & 31, lh = lane >> 5;
+    const int z = blockIdx.y;
+    const int m = blockIdx.x * MROWS + wave * 32 + lr;
+    const int row = min(m, a.M - 1);
+    const int nhb = a.Hd / 32;
+    const char* const w2g = (const char*)a.W2p;
+    const int ghw = a.geo_h * a.geo_w, nview = a.M / ghw;
+    const int gview = row / ghw, gpix = row - gview * ghw;
+    const int gimg = z * nview + gview;
+
+    // W2(0): piece p by wave p % MW
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
+    for (int p = wave; p < 4 * NOT; p += MW) glds16(w2g + lane * 16 + p * FRAG_B, s2 + p * FRAG_B);
+
+    // the coefficients of the workgroup's views: alpha = sum_c T1[j][c] M[c][0], beta likewise with
+    // M[c][1], gamma = sum_c (T1[j][c] M[c][2] + T0[j][c] (M[c][3] - lo_c)) + b0[j]
+    const int v0 = blockIdx.x * MROWS / ghw;
+    const int nv = min(blockIdx.x * MROWS + MROWS - 1, a.M - 1) / ghw - v0 + 1;   // <= AFF_VIEWS: h w >= 32
+    for (int s = 0; s < nv; ++s) {
+        const float* Mx = a.geo_i2l + (int64_t)(z * nview + v0 + s) * 16;
+        double mm[3][4];
 #pragma unroll
-            for (int tt = 0; tt < 2; ++tt)
+        for (int c = 0; c < 3; ++c) {
 #pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int ot = 2 * q + tt;
-                    const int n = ot * 32 + 8 * g + 4 * lh;
-                    const f32x4 bv = *(const f32x4*)(a.b2 + n);
-                    p4 h2, l2, hc, lc;
+            for (int i = 0; i < 3; ++i) mm[c][i] = (double)Mx[4 * c + i];
+            mm[c][3] = (double)Mx[4 * c + 3] - (double)a.geo_pc[c];
+        }
+        // four units per thread and trip: their table loads are in flight together (one unit per
+        // trip waited for each load, a memory round trip per 256 units)
+#pragma unroll 4
+        for (int j = tid; j < a.Hd; j += 64 * MW) {
+            const double* t = aa.tab + 8 * j;
+            double al = 0.0, be = 0.0, ga = t[6];
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        // the pair cmt_nchw_to_rows writes, and its value as the pair R row reads back
-                        const float x = xv[q][tt][g][e];
-                        bad |= f16_unrepresentable(x);
-                        h2[e] = (pair_t)x;
-                        l2[e] = (pair_t)(x - (float)h2[e]);
-                        const float rv = (float)h2[e] + (float)l2[e];
-                        const float v = oacc[ot][4 * g + e] + (bv[e] + rv);
-                        hc[e] = (pair_t)v;
-                        lc[e] = (pair_t)(v - (float)hc[e]);
-                    }
-                    const int off = sw(lr, 4 * tt + g) + 8 * lh;
-                    *(p4*)(stg + off) = hc;
-                    *(p4*)(stg + 4096 + off) = lc;
-                    *(p4*)(stg + 8192 + off) = h2;
-                    *(p4*)(stg + 12288 + off) = l2;
-                }
+            for (int c = 0; c < 3; ++c) {
+                const double t1 = t[c], t0 = t[3 + c];
+                al = fma(t1, mm[c][0], al);
+                be = fma(t1, mm[c][1], be);
+                ga = fma(t1, mm[c][2], ga);
+                ga = fma(t0, mm[c][3], ga);
+            }
+            float* o = sco + s * 3 * AFF_MAX_HD + j;
+            o[0] = (float)al;
+            o[AFF_MAX_HD] = (float)be;
+            o[2 * AFF_MAX_HD] = (float)ga;
+        }
+    }
+    const int gw = gpix % a.geo_w, gh = gpix / a.geo_w;
+    const float u = (float)gw * a.geo_pad_w / (float)a.geo_w;
+    const float v = (float)gh * a.geo_pad_h / (float)a.geo_h;
+    const int slot = __builtin_amdgcn_readfirstlane(gview - v0);
+    const float* const co = sco + slot * 3 * AFF_MAX_HD + 4 * lh;   // the lane half's alpha of unit 0
+
+    f32x16 oacc[NOT];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int r = 8 * i + (lane >> 3), ch = lane & 7;
-                const int mr = mw0 + r;
-                const int off = sw(r, ch);
-                const u4 v0 = *(const u4*)(stg + off), v1 = *(const u4*)(stg + 4096 + off);
-                const u4 v2 = *(const u4*)(stg + 8192 + off), v3 = *(const u4*)(stg + 12288 + off);
-                if (mr < a.M && !(CMT_MLP_DIAG & 1)) {
-                    pair_t* cr = (pair_t*)a.C + (int64_t)z * a.c_bstride + (int64_t)mr * a.ldc + 64 * q + 8 * ch;
-                    pair_t* c2 = (pair_t*)a.C2 + (int64_t)z * a.c2_bstride + (int64_t)mr * a.ldc2 + 64 * q + 8 * ch;
-                    *(u4*)cr = v0;
-                    *(u4*)(cr + NOUT) = v1;
-                    *(u4*)c2 = v2;
-                    *(u4*)(c2 + NOUT) = v3;
+    for (int t = 0; t < NOT; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) oacc[t][r] = 0.f;
+    // the hidden tile as fc2's B operand (k-steps 0, 1), hi and lo: this block's and the next one's.
+    // Register 4 g + e of lane half lh is hidden unit 8 g + 4 lh + e, as in the GEMM form
+    pair8_t hh[2], hl[2], nh[2], nl[2];
+    f32x4 ca, cb, cc;
+    auto coef_read = [&](int hb, int g) {
+        const float* p = co + 32 * hb + 8 * g;
+        ca = *(const f32x4*)p;
+        cb = *(const f32x4*)(p + AFF_MAX_HD);
+        cc = *(const f32x4*)(p + 2 * AFF_MAX_HD);
+    };
+    auto unit = [&](pair8_t (&H)[2], pair8_t (&L)[2], int g, int e) {
+        const float x = fmaxf(fmaf(ca[e], u, fmaf(cb[e], v, cc[e])), 0.f) + 0.f;
+        const pair_t h = (pair_t)x;
+        H[g >> 1][4 * (g & 1) + e] = h;
+        L[g >> 1][4 * (g & 1) + e] = (pair_t)(x - (float)h);
+    };
+    // fc2 over block hb (its W2 slot): 16 steps, each a triple on one accumulator whose two weight
+    // fragments are read from LDS PD steps ahead.  With a next block, steps 0 .. 4 NOT / MW - 1 also
+    // issue this wave's LDS-DMA pieces of W2(hb + 1), one per step behind the step's MFMAs, and
+    // steps 4 g .. 4 g + 3 read group g's coefficients of block hb + 1 and form its four units
+    constexpr int NW2 = 4 * NOT / MW;
+    auto fc2 = [&](int hb, auto next_c) {
+        constexpr bool next = decltype(next_c)::value;
+        const char* w2 = s2 + (hb & 1) * W2_BLK + lane * 16;
+        pair8_t fh[PD + 1], fl[PD + 1];
+#pragma unroll
+        for (int t = 0; t < PD; ++t) {
+            fh[t] = *(const pair8_t*)(w2 + t * 2 * FRAG_B);
+            fl[t] = *(const pair8_t*)(w2 + t * 2 * FRAG_B + FRAG_B);
+        }
+#pragma unroll
+        for (int t = 0; t < 2 * NOT; ++t) {
+            if constexpr (next)
+                if (t % 4 == 0) coef_read(hb + 1, t / 4);
+            if (t + PD < 2 * NOT) {
+                fh[(t + PD) % (PD + 1)] = *(const pair8_t*)(w2 + (t + PD) * 2 * FRAG_B);
+                fl[(t + PD) % (PD + 1)] = *(const pair8_t*)(w2 + (t + PD) * 2 * FRAG_B + FRAG_B);
+            }
+            const int sl = t % (PD + 1);
+            oacc[t >> 1] = mma3(fh[sl], fl[sl], hh[t & 1], hl[t & 1], oacc[t >> 1]);
+            if constexpr (next) {
+                // the coefficients read at step 4 g are used from step 4 g + 1 on
+                if (t % 4 >= 1) unit(nh, nl, t / 4, t % 4 - 1);
+                if (t % 4 == 3) unit(nh, nl, t / 4, 3);
+                if (t < NW2 && !(CMT_MLP_DIAG & 8)) {
+                    const int p = wave + MW * t;
+                    glds16(w2g + (int64_t)(hb + 1) * W2_BLK + lane * 16 + p * FRAG_B,
+                           s2 + ((hb + 1) & 1) * W2_BLK + p * FRAG_B);
                 }
             }
+            __builtin_amdgcn_sched_barrier(0);
         }
-        raise_range_flag(a.range_flag, bad);
-        return;
+    };
+
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    barrier_mem();   // W2(0) landed for every wave's pieces, the coefficients are written
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        coef_read(0, g);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) unit(hh, hl, g, e);
     }
-    // ---- epilogue: out = acc + (b2 + R) (cmt_gemm's order), row lr, columns 32 ot + 8 g + 4 lh + 0..3
-    if (m >= a.M) return;
-    const char* Rrow = nullptr;
-    if (a.R) {
-        const int resz = a.r_dtype == CMT_F32 ? 4 : 2;
-        Rrow = (const char*)a.R + ((int64_t)z * a.r_bstride + (int64_t)row * a.ldr) * resz;
+    for (int hb = 0; hb + 1 < nhb; ++hb) {
+        // W2(hb) (issued one block ago) landed; every wave is past block hb - 1, whose slot takes
+        // W2(hb + 1)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        barrier_mem();
+        fc2(hb, std::true_type{});
+#pragma unroll
+        for (int i = 0; i < 2; ++i) { hh[i] = nh[i]; hl[i] = nl[i]; }
     }
-    const int cesz = a.c_dtype == CMT_F32 ? 4 : 2;
-    char* Crow = (char*)a.C + ((int64_t)z * a.c_bstride + (int64_t)row * a.ldc) * cesz;
-    typedef pair_t p4 __attribute__((ext_vector_type(4)));
-#pragma unroll
-    for (int ot = 0; ot < NOT; ++ot)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int n = ot * 32 + 8 * g + 4 * lh;
-            const f32x4 bv = *(const f32x4*)(a.b2 + n);
-            f32x4 rv = {0.f, 0.f, 0.f, 0.f};
-            if (Rrow) {
-                if (a.r_dtype == CMT_F32) {
-                    rv = *(const f32x4*)((const float*)Rrow + n);
-                } else {
-                    const p4 h = *(const p4*)((const pair_t*)Rrow + n);
-                    const p4 l = *(const p4*)((const pair_t*)Rrow + NOUT + n);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) rv[e] = (float)h[e] + (float)l[e];
-                }
-            }
-            f32x4 v;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = oacc[ot][4 * g + e] + (bv[e] + rv[e]);
-            if (a.c_dtype == CMT_F32) *(f32x4*)((float*)Crow + n) = v;
-            else store_pair4((pair_t*)Crow, NOUT, n, v);
-        }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    barrier_mem();
+    // RX: the NCHW loads' memory round trip runs under the last block's fc2, as in the GEMM form
+    float xv[RX ? 4 : 1][2][4][4];
+    if constexpr (RX) rx_load(a, gimg, gpix, ghw, lh, xv);
+    fc2(nhb - 1, std::false_type{});
+
+    if constexpr (RX) rx_epilogue(a, lds, oacc, xv);
+    else rows_epilogue(a, m, row, oacc);
+}
+
+// the checks of C and R both entry points share
+int check_rows(const cmt_mlp2_args& a, const char* who) {
+    const std::string w(who);
+    CMT_REQUIRE(a.c_dtype == CMT_F32 || a.c_dtype == CMT_F16P, w + ": C must be fp32 or an f16 pair");
+    CMT_REQUIRE(a.c_dtype == CMT_F32 ? a.ldc >= NOUT && a.ldc % 4 == 0 && a.c_bstride % 4 == 0
+                                     : a.ldc >= 2 * NOUT && a.ldc % 4 == 0 && a.c_bstride % 4 == 0,
+                w + ": bad C row stride");
+    CMT_REQUIRE(a.R == nullptr || ((a.r_dtype == CMT_F32 && a.ldr >= NOUT) ||
+                                   (a.r_dtype == CMT_F16P && a.ldr >= 2 * NOUT)) && a.ldr % 4 == 0 &&
+                                      a.r_bstride % 4 == 0,
+                w + ": R must be fp32 or f16-pair rows of 256");
+    return 0;
+}
+// ... and of the fused camera-row outputs (rx, C2)
+bool rx_ok(const cmt_mlp2_args& a) {
+    return a.geo_i2l && a.rx && a.C2 && a.geo_h > 0 && a.geo_w > 0 && a.M % (a.geo_h * a.geo_w) == 0 &&
+           a.c_dtype == CMT_F16P && a.R == nullptr && a.ldc2 >= 2 * NOUT && a.ldc2 % 4 == 0 &&
+           a.c2_bstride % 4 == 0 && (uintptr_t)a.C2 % 8 == 0;
 }
 
 }  // namespace
 
 extern "C" int64_t cmt_mlp2_args_size(void) { return (int64_t)sizeof(cmt_mlp2_args); }
+extern "C" int64_t cmt_mlp2_affine_args_size(void) { return (int64_t)sizeof(cmt_mlp2_affine_args); }
+
+extern "C" int cmt_mlp2_affine(const cmt_mlp2_affine_args* ap, void* stream) {
+    CMT_REQUIRE(ap != nullptr, "cmt_mlp2_affine: null args");
+    const cmt_mlp2_args& a = ap->m;
+    CMT_REQUIRE(a.M > 0 && a.batch > 0, "cmt_mlp2_affine: empty problem");
+    CMT_REQUIRE(a.N == NOUT, "cmt_mlp2_affine: the output width must be 256");
+    CMT_REQUIRE(a.Hd > 0 && a.Hd % 32 == 0, "cmt_mlp2_affine: the hidden width must be a multiple of 32");
+    CMT_REQUIRE(ap->tab && a.geo_i2l && a.W2p && a.b2 && a.C, "cmt_mlp2_affine: null pointer");
+    CMT_REQUIRE(a.geo_h > 0 && a.geo_w > 0 && a.M % (a.geo_h * a.geo_w) == 0,
+                "cmt_mlp2_affine: M must be a multiple of geo_h * geo_w");
+    if (int rc = check_rows(a, "cmt_mlp2_affine")) return rc;
+    CMT_REQUIRE(((uintptr_t)ap->tab | (uintptr_t)a.W2p | (uintptr_t)a.b2) % 16 == 0,
+                "cmt_mlp2_affine: the tables, the pack and the bias must be 16-byte aligned");
+    CMT_REQUIRE((a.rx == nullptr && a.C2 == nullptr) || rx_ok(a),
+                "cmt_mlp2_affine: the fused camera-row form takes rx and C2 together, a pair C and no R");
+    if (a.geo_h * a.geo_w % 32 != 0)
+        return cmt_fail(CMT_ENOTSUP, "cmt_mlp2_affine: geo_h * geo_w must be a multiple of 32 (a wave's rows lie in "
+                                     "one view)");
+    if (a.Hd > AFF_MAX_HD) return cmt_fail(CMT_ENOTSUP, "cmt_mlp2_affine: the hidden width is at most 1024");
+    const dim3 grid((unsigned)cdiv(a.M, MROWS), (unsigned)a.batch);
+    hipStream_t s = (hipStream_t)stream;
+    if (a.rx) mlp2_affine_kernel<true><<<grid, 64 * MW, 0, s>>>(*ap);
+    else mlp2_affine_kernel<false><<<grid, 64 * MW, 0, s>>>(*ap);
+    return cmt_check_launch("cmt_mlp2_affine");
+}
 
 extern "C" int cmt_mlp2_x3(const cmt_mlp2_args* ap, void* stream) {
     CMT_REQUIRE(ap != nullptr, "cmt_mlp2_x3: null args");
@@ -387,24 +620,14 @@ extern "C" int cmt_mlp2_x3(const cmt_mlp2_args* ap, void* stream) {
     CMT_REQUIRE((a.A || a.geo_i2l) && a.W1p && a.W2p && a.b1 && a.b2 && a.C, "cmt_mlp2_x3: null pointer");
     CMT_REQUIRE(a.geo_i2l || (a.lda >= 2 * a.K && a.lda % 8 == 0 && a.a_bstride % 8 == 0),
                 "cmt_mlp2_x3: A pair rows need lda >= 2K, 16-byte aligned");
-    CMT_REQUIRE(a.c_dtype == CMT_F32 || a.c_dtype == CMT_F16P, "cmt_mlp2_x3: C must be fp32 or an f16 pair");
-    CMT_REQUIRE(a.c_dtype == CMT_F32 ? a.ldc >= NOUT && a.ldc % 4 == 0 && a.c_bstride % 4 == 0
-                                     : a.ldc >= 2 * NOUT && a.ldc % 4 == 0 && a.c_bstride % 4 == 0,
-                "cmt_mlp2_x3: bad C row stride");
-    CMT_REQUIRE(a.R == nullptr || ((a.r_dtype == CMT_F32 && a.ldr >= NOUT) ||
-                                   (a.r_dtype == CMT_F16P && a.ldr >= 2 * NOUT)) && a.ldr % 4 == 0 &&
-                                      a.r_bstride % 4 == 0,
-                "cmt_mlp2_x3: R must be fp32 or f16-pair rows of 256");
+    if (int rc = check_rows(a, "cmt_mlp2_x3")) return rc;
     CMT_REQUIRE(((uintptr_t)a.A | (uintptr_t)a.W1p | (uintptr_t)a.W2p) % 16 == 0 && (uintptr_t)a.b1 % 16 == 0 &&
                     (uintptr_t)a.b2 % 16 == 0,
                 "cmt_mlp2_x3: A / packs / biases must be 16-byte aligned");
     const dim3 grid((unsigned)cdiv(a.M, MROWS), (unsigned)a.batch);
     hipStream_t s = (hipStream_t)stream;
     if (a.geo_i2l || a.rx) {
-        CMT_REQUIRE(a.geo_i2l && a.rx && a.C2 && a.K == 192 && a.geo_D * 3 == a.K && a.geo_h > 0 && a.geo_w > 0 &&
-                        a.M % (a.geo_h * a.geo_w) == 0 && a.c_dtype == CMT_F16P && a.R == nullptr &&
-                        a.ldc2 >= 2 * NOUT && a.ldc2 % 4 == 0 && a.c2_bstride % 4 == 0 &&
-                        (uintptr_t)a.C2 % 8 == 0,
+        CMT_REQUIRE(rx_ok(a) && a.K == 192 && a.geo_D * 3 == a.K,
                     "cmt_mlp2_x3: the fused camera-row form takes geo_i2l, rx and C2 together, K = 3 geo_D = 192, "
                     "M a multiple of geo_h * geo_w, a pair C and no R");
         mlp2_x3_kernel<12, 2, true, true><<<grid, 64 * MW, 0, s>>>(a);

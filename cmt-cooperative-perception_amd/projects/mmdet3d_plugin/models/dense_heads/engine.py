@@ -9,7 +9,8 @@ fixed sequence of gfx950 kernels over HBM-resident buffers:
                   written straight into the pos rows (cmt_head.py:324-337, 489)
   image memory    layout kernel "(bs v) c h w -> bs (v h w) c" into the memory rows
   rv pos          frustum geometry kernel (fp64 host inverse) -> 2 GEMMs into pos rows
-                  (cmt_head.py:417-433)
+                  (cmt_head.py:417-433); at the reference's numerics one launch whose
+                  first layer is an affine map of the pixel per camera (cmt_mlp2_affine)
   query embed     pos2embed(sigmoid(inverse_sigmoid(ref))) -> 2 GEMMs, plus the
                   projected-view geometry kernel -> 2 GEMMs -> masked view sum
                   (cmt_head.py:435-473)
@@ -73,6 +74,12 @@ class HeadEngineMixin:
                         and w0.shape[-1] <= 192):
                     # fragment packs of the one-launch MLP (cmt_mlp2_x3)
                     pk["rv_fused"] = native.mlp2_pack(w0, w2)
+                    if w0.shape[0] <= 1024:
+                        # the affine form's first layer (cmt_mlp2_affine): rv_embedding[0] summed over
+                        # the depth bins, from the fp32 master weights in float64
+                        pk["rv_affine"] = native.mlp2_affine_tables(
+                            re[0].weight.detach().float(), re[0].bias.detach().float(), D=self.depth_num,
+                            depth_max=float(self.pc_range[3]), pc_range=self.pc_range)
             return pk
         return self._pack.get("engine", params, prec.name, build)
 
@@ -251,6 +258,19 @@ class HeadEngineMixin:
         that path applies (split policy, CMT_MLP_FUSED), else None."""
         return pk.get("rv_fused") if OPTIONS.mlp_fused else None
 
+    def _rv_affine(self, pk, h, w):
+        """The tables of the affine first layer (cmt_mlp2_affine) when that form applies: the
+        one-launch MLP, CMT_RV_AFFINE, and feature maps whose h * w is a multiple of 32 (a wave's
+        rows lie in one view); else None and the coordinates + fc1 GEMM form runs."""
+        ok = OPTIONS.rv_affine and self._rv_fused(pk) is not None and (h * w) % 32 == 0
+        return pk.get("rv_affine") if ok else None
+
+    def _rv_geo_args(self, x_img, metas, cams):
+        _, _, h, w = x_img.shape
+        pad_h, pad_w, _ = metas[0]["pad_shape"][0]
+        return dict(i2l=cams[1], h=h, w=w, D=self.depth_num, pad_h=float(pad_h), pad_w=float(pad_w),
+                    depth_max=float(self.pc_range[3]), pc_range=self.pc_range)
+
     def _rv_pe_hidden(self, x_img, metas, B, pk, cams=None):
         """First half of _rv_pe + rv_embedding (cmt_head.py:417-433, 297-301):
         the frustum coordinates and rv_embedding[0] + ReLU -- they read only
@@ -259,8 +279,12 @@ class HeadEngineMixin:
         BV, _, h, w = x_img.shape
         pad_h, pad_w, _ = metas[0]["pad_shape"][0]
         dev = x_img.device
-        i2l = (cams if cams is not None else self._cams(metas, dev))[1]
+        cams = cams if cams is not None else self._cams(metas, dev)
+        i2l = cams[1]
         D = self.depth_num
+        if self._rv_affine(pk, h, w) is not None:
+            # nothing to compute ahead: _rv_pe_out forms the hidden units from the camera matrices
+            return dict(M=BV // B * h * w, geo=self._rv_geo_args(x_img, metas, cams))
         w0, b0, _, _ = pk["rv"]
         cdt = w0.dtype if (3 * D) % 64 == 0 else torch.float32
         coords = op_empty(BV * h * w, 3 * D, cdt, dev)
@@ -275,8 +299,14 @@ class HeadEngineMixin:
         """Second half: rv_embedding[2] into the camera pos rows (+ R as in _bev_pos_out)."""
         C = self.hidden_dim
         _, b0, w2, b2 = pk["rv"]
-        M = hid.shape[0] // B   # V * h * w rows per batch element
         fused = self._rv_fused(pk)
+        if isinstance(hid, dict):
+            # the affine form: the same hidden arithmetic as _rv_rows_geo, R rows for its NCHW read
+            native.mlp2_affine(pk["rv_affine"], fused[1], b2, pos, M=hid["M"], Hd=w2.shape[-1], geo=hid["geo"], R=R,
+                               batch=B, c_offset=offset * C, c_bstride=Nk * C, r_offset=offset * C,
+                               r_bstride=Nk * C)
+            return
+        M = hid.shape[0] // B   # V * h * w rows per batch element
         if fused is not None and hid.shape[-1] != w2.shape[-1]:
             # hid holds the coordinates: both layers in one launch, the hidden rows stay on chip
             native.mlp2(hid, fused[0], b0, fused[1], b2, pos, M=M, K=native.width(hid), Hd=w2.shape[-1], R=R,
@@ -302,12 +332,17 @@ class HeadEngineMixin:
         rows (mem) and the residual of lowp(memory + pos) (pos)."""
         C = self.hidden_dim
         BV, _, h, w = x_img.shape
-        pad_h, pad_w, _ = metas[0]["pad_shape"][0]
         _, b0, w2, b2 = pk["rv"]
         fused = self._rv_fused(pk)
         M = BV // B * h * w
-        geo = dict(i2l=cams[1], h=h, w=w, D=self.depth_num, pad_h=float(pad_h), pad_w=float(pad_w),
-                   depth_max=float(self.pc_range[3]), pc_range=self.pc_range)
+        geo = self._rv_geo_args(x_img, metas, cams)
+        tab = self._rv_affine(pk, h, w)
+        if tab is not None:
+            # no coordinates and no fc1 GEMM: the hidden units are affine in the pixel
+            native.mlp2_affine(tab, fused[1], b2, pos, M=M, Hd=w2.shape[-1], geo=geo, batch=B, c_offset=offset * C,
+                               c_bstride=Nk * C, rx=x_img.contiguous().float(), C2=mem, c2_offset=offset * C,
+                               c2_bstride=Nk * C, range_flag=self._range_flag(x_img.device))
+            return
         native.mlp2(None, fused[0], b0, fused[1], b2, pos, M=M, K=3 * self.depth_num, Hd=w2.shape[-1], batch=B,
                     c_offset=offset * C, c_bstride=Nk * C, geo=geo, rx=x_img.contiguous().float(), C2=mem,
                     c2_offset=offset * C, c2_bstride=Nk * C, range_flag=self._range_flag(x_img.device))
@@ -479,7 +514,7 @@ class HeadEngineMixin:
                                                first_ops=(state["tl"], state["tp"]))
                 dec.lowp_layer0(state, qpos, B=B, Nq=Nq, prec=prec, first_ops_ready=firsts)
             for t in (qpos, hb, hr) + (tuple(cams) if late_cams else ()):
-                if t is not None:
+                if isinstance(t, torch.Tensor):
                     t.record_stream(main)
             if geo:
                 if late_cams:

@@ -154,6 +154,10 @@ class Mlp2Args(ctypes.Structure):
                 ("rx", _vp), ("C2", _vp), ("ldc2", _i64), ("c2_bstride", _i64), ("range_flag", _vp)]
 
 
+class Mlp2AffineArgs(ctypes.Structure):
+    _fields_ = [("m", Mlp2Args), ("tab", _vp)]
+
+
 class SparseIndexArgs(ctypes.Structure):
     _fields_ = [("B", _int), ("D", _int), ("H", _int), ("W", _int), ("n_cap", _int), ("reserved", _int),
                 ("coors", _vp), ("count", _vp), ("index", _vp), ("index_bytes", _i64)]
@@ -181,7 +185,7 @@ class SparseDenseArgs(ctypes.Structure):
 
 STRUCTS = {"gemm": GemmArgs, "attn": AttnArgs, "ln": LnArgs, "chain": ChainArgs, "gemm_ex": GemmExArgs,
            "attn_train": AttnTrainArgs, "ln_train": LnTrainArgs, "bn": BnArgs, "det_loss": DetLossArgs,
-           "match_cost": MatchCostArgs, "adamw": AdamwArgs, "mlp2": Mlp2Args, "lsap": LsapArgs,
+           "match_cost": MatchCostArgs, "adamw": AdamwArgs, "mlp2": Mlp2Args, "mlp2_affine": Mlp2AffineArgs, "lsap": LsapArgs,
            "sparse_index": SparseIndexArgs, "sparse_rulebook": SparseRulebookArgs, "sparse_conv": SparseConvArgs,
            "sparse_dense": SparseDenseArgs}
 
@@ -212,6 +216,8 @@ def _load():
         "cmt_kv_proj": ([P(GemmArgs), _vp], _int),
         "cmt_mlp2_x3": ([P(Mlp2Args), _vp], _int),
         "cmt_mlp2_args_size": ([], _i64),
+        "cmt_mlp2_affine": ([P(Mlp2AffineArgs), _vp], _int),
+        "cmt_mlp2_affine_args_size": ([], _i64),
         "cmt_add_cast": ([_vp, _vp, _int, _int, _int, _vp, _vp, _vp], _int),
         "cmt_pos2embed": ([_vp, _i64, _int, _int, _int, _int, _int, _vp, _int, _i64, _vp], _int),
         "cmt_rv_pe_coords": ([_int, _int, _int, _int, _flt, _flt, _flt, _vp, P(_flt), _vp, _int, _vp], _int),
@@ -457,22 +463,35 @@ def mlp2(A, W1p, b1, W2p, b2, C, *, M, K, Hd, R=None, batch=1, a_bstride=0, c_of
     if A is not None:
         g.A, g.lda, g.a_bstride = A.data_ptr(), lstride(A) * 2, a_bstride * 2
     else:
-        _dev(geo["i2l"])
-        if rx.dtype != torch.float32 or not rx.is_contiguous() or C2.dtype != torch.uint16:
-            raise RuntimeError("mlp2: rx must be contiguous NCHW fp32, C2 pair rows")
-        g.geo_i2l = geo["i2l"].data_ptr()
-        g.geo_h, g.geo_w, g.geo_D = geo["h"], geo["w"], geo["D"]
-        g.geo_pad_h, g.geo_pad_w, g.geo_depth_max = geo["pad_h"], geo["pad_w"], geo["depth_max"]
-        for i in range(6):
-            g.geo_pc[i] = float(geo["pc_range"][i])
-        g.rx = rx.data_ptr()
-        g.C2 = C2.data_ptr() + c2_offset * 2 * C2.element_size()   # logical elements (pair: 2 words each)
-        g.ldc2, g.c2_bstride = lstride(C2) * 2, c2_bstride * 2
-        if range_flag is not None:
-            if range_flag.dtype != torch.int32:
-                raise RuntimeError("mlp2: range_flag must be an int32 device word")
-            g.range_flag = range_flag.data_ptr()
+        _mlp2_geo(g, geo)
+        _mlp2_rx(g, rx, C2, c2_offset, c2_bstride, range_flag)
     g.W1p, g.b1, g.W2p, g.b2 = W1p.data_ptr(), b1.data_ptr(), W2p.data_ptr(), b2.data_ptr()
+    _mlp2_rows(g, C, c_offset, c_bstride, R, r_offset, r_bstride)
+    _check(lib().cmt_mlp2_x3(ctypes.byref(g), _stream()), "cmt_mlp2_x3")
+
+
+def _mlp2_geo(g, geo):
+    _dev(geo["i2l"])
+    g.geo_i2l = geo["i2l"].data_ptr()
+    g.geo_h, g.geo_w, g.geo_D = geo["h"], geo["w"], geo["D"]
+    g.geo_pad_h, g.geo_pad_w, g.geo_depth_max = geo["pad_h"], geo["pad_w"], geo["depth_max"]
+    for i in range(6):
+        g.geo_pc[i] = float(geo["pc_range"][i])
+
+
+def _mlp2_rx(g, rx, C2, c2_offset, c2_bstride, range_flag):
+    if rx.dtype != torch.float32 or not rx.is_contiguous() or C2.dtype != torch.uint16:
+        raise RuntimeError("mlp2: rx must be contiguous NCHW fp32, C2 pair rows")
+    g.rx = rx.data_ptr()
+    g.C2 = C2.data_ptr() + c2_offset * 2 * C2.element_size()   # logical elements (pair: 2 words each)
+    g.ldc2, g.c2_bstride = lstride(C2) * 2, c2_bstride * 2
+    if range_flag is not None:
+        if range_flag.dtype != torch.int32:
+            raise RuntimeError("mlp2: range_flag must be an int32 device word")
+        g.range_flag = range_flag.data_ptr()
+
+
+def _mlp2_rows(g, C, c_offset, c_bstride, R, r_offset, r_bstride):
     sc = _ps(C)
     g.C = C.data_ptr() + c_offset * sc * C.element_size()
     g.ldc, g.c_bstride, g.c_dtype = lstride(C) * sc, c_bstride * sc, DT[C.dtype]
@@ -482,7 +501,48 @@ def mlp2(A, W1p, b1, W2p, b2, C, *, M, K, Hd, R=None, batch=1, a_bstride=0, c_of
         g.ldr, g.r_bstride, g.r_dtype = lstride(R) * sr, r_bstride * sr, DT[R.dtype]
     else:
         g.R, g.ldr, g.r_bstride, g.r_dtype = None, 0, 0, F32
-    _check(lib().cmt_mlp2_x3(ctypes.byref(g), _stream()), "cmt_mlp2_x3")
+
+
+def mlp2_affine_tables(W0, b0, *, D, depth_max, pc_range):
+    """The weight-only tables of cmt_mlp2_affine (cmt_hip.h) from the fp32 master weights of
+    rv_embedding[0] (W0 [Hd, 3 D], b0 [Hd]): float64 [Hd, 8] = T1[j][0..2], T0[j][0..2], b0[j], 0
+    with T1[j][c] = sum_d W0[j][3 d + c] depth_d / span_c and T0[j][c] = sum_d W0[j][3 d + c] / span_c.
+    The depths and the spans are formed in fp32 as _rv_pe forms them (cmt_head.py:417-432), then
+    widened; the sums run in float64."""
+    hd = W0.shape[0]
+    if W0.dim() != 2 or W0.shape[1] != 3 * D or b0.shape != (hd,):
+        raise RuntimeError("mlp2_affine_tables: W0 [Hd, 3 D] and b0 [Hd]")
+    depth = (1 + torch.arange(D).float() * (float(depth_max) - 1) / D).double().to(W0.device)
+    pcr = torch.tensor([float(v) for v in pc_range], dtype=torch.float32)
+    span = (pcr[3:] - pcr[:3]).double().to(W0.device)
+    w = W0.detach().double().view(hd, D, 3)
+    tab = torch.zeros((hd, 8), dtype=torch.float64, device=W0.device)
+    tab[:, 0:3] = (w * depth[None, :, None]).sum(1) / span
+    tab[:, 3:6] = w.sum(1) / span
+    tab[:, 6] = b0.detach().double()
+    return tab
+
+
+def mlp2_affine(tab, W2p, b2, C, *, M, Hd, geo, R=None, batch=1, c_offset=0, c_bstride=0, r_offset=0, r_bstride=0,
+                rx=None, C2=None, c2_offset=0, c2_bstride=0, range_flag=None):
+    """rv_embedding over the _rv_pe frustum coordinates without the first GEMM
+    (cmt_mlp2_affine): tab from mlp2_affine_tables, W2p from mlp2_pack, geo as for mlp2
+    (h * w % 32 == 0); with rx + C2 the fused camera-row epilogue of mlp2, else C = out (+ R)."""
+    _dev(tab, W2p, b2, C, R, rx, C2, range_flag)
+    if tab.dtype != torch.float64 or tab.shape != (Hd, 8) or not tab.is_contiguous() or W2p.dtype != torch.uint16:
+        raise RuntimeError("mlp2_affine: tab must be float64 [Hd, 8], W2p a split pair pack")
+    if (rx is None) != (C2 is None):
+        raise RuntimeError("mlp2_affine: rx and C2 go together")
+    ga = Mlp2AffineArgs()
+    g = ga.m
+    g.M, g.Hd, g.N, g.batch = M, Hd, 256, batch
+    _mlp2_geo(g, geo)
+    if rx is not None:
+        _mlp2_rx(g, rx, C2, c2_offset, c2_bstride, range_flag)
+    g.W2p, g.b2 = W2p.data_ptr(), b2.data_ptr()
+    _mlp2_rows(g, C, c_offset, c_bstride, R, r_offset, r_bstride)
+    ga.tab = tab.data_ptr()
+    _check(lib().cmt_mlp2_affine(ctypes.byref(ga), _stream()), "cmt_mlp2_affine")
 
 
 def _ps(t):

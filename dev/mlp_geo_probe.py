@@ -1,6 +1,6 @@
 """Times the camera memory rows at the fusion frame's shape (6 x 40 x 100 tokens, depth_num 64):
 the one-launch form (cmt_mlp2_x3 with geo + rx, ABI 20) against coordinates kernel + layout pass +
-one-launch MLP.  HIP events, mean of 20 launches after 3 warm-ups.
+one-launch MLP, and against the affine form (cmt_mlp2_affine: no coordinates, no fc1 GEMM).  HIP events, mean of 20 launches after 3 warm-ups.
     python dev/mlp_geo_probe.py"""
 import os
 import sys
@@ -43,6 +43,14 @@ def fused():
                 geo=geo, rx=xi, C2=mem, c2_offset=32400 * C, c2_bstride=Nk * C)
 
 
+tab = native.mlp2_affine_tables(W1.to(dev), b1, D=D, depth_max=54.0, pc_range=pc)
+
+
+def affine():
+    native.mlp2_affine(tab, W2p, b2, pos, M=M, Hd=Hd, geo=geo, batch=B, c_offset=32400 * C, c_bstride=Nk * C,
+                       rx=xi, C2=mem, c2_offset=32400 * C, c2_bstride=Nk * C)
+
+
 def three():
     native.rv_pe_coords(i2l, coords, BV=B * V, h=h, w=w, D=D, pad_h=640.0, pad_w=1600.0, depth_max=54.0,
                         pc_range=pc)
@@ -70,4 +78,4 @@ def t(fn):
 
 
 tag = os.environ.get("TAG", "")
-print(f"{tag} fused {t(fused):.1f} us | three launches {t(three):.1f} us | one-launch MLP alone {t(mlp_only):.1f} us")
+print(f"{tag} affine {t(affine):.1f} us | fused {t(fused):.1f} us | three launches {t(three):.1f} us | one-launch MLP alone {t(mlp_only):.1f} us")

@@ -219,6 +219,31 @@ typedef struct cmt_mlp2_args {
 int cmt_mlp2_x3(const cmt_mlp2_args* args, void* stream);
 int64_t cmt_mlp2_args_size(void);
 
+/* cmt_mlp2_affine (additive to ABI 25): rv_embedding over the _rv_pe frustum coordinates
+ * without the fc1 GEMM.  The normalised coordinate of view b, pixel (u, v), depth d, axis c is
+ *   (d (M_b[c][0] u + M_b[c][1] v + M_b[c][2]) + M_b[c][3] - lo_c) / span_c      (M_b = geo_i2l),
+ * affine in (u, v), and nothing nonlinear stands before rv_embedding[0]; so hidden unit j is
+ *   relu(alpha_bj u + beta_bj v + gamma_bj),   evaluated as fmaf(alpha, u, fmaf(beta, v, gamma)),
+ *   alpha_bj = sum_c T1[j][c] M_b[c][0],   beta_bj = sum_c T1[j][c] M_b[c][1],
+ *   gamma_bj = sum_c (T1[j][c] M_b[c][2] + T0[j][c] (M_b[c][3] - lo_c)) + b0[j]
+ * with the weight-only tables T1[j][c] = sum_d W0[j][3 d + c] depth_d / span_c and
+ * T0[j][c] = sum_d W0[j][3 d + c] / span_c.  The kernel contracts them with the camera matrices
+ * per workgroup in float64 and rounds the coefficients to fp32.
+ *   tab  float64 [Hd][8]: T1[j][0..2], T0[j][0..2], b0[j], 0     (16-byte aligned)
+ *   m    as for cmt_mlp2_x3: Hd (% 32 == 0, at most 1024; CMT_ENOTSUP beyond), W2p, b2, C and
+ *        the row strides; geo_i2l, geo_h, geo_w, geo_pad_h, geo_pad_w and geo_pc[0..2] (lo) give
+ *        the rows' views and pixels (M % (geo_h * geo_w) == 0, and geo_h * geo_w % 32 == 0 --
+ *        CMT_ENOTSUP otherwise: a wave's 32 rows lie in one view); rx and C2 together select the
+ *        fused camera-row epilogue of cmt_mlp2_x3, else C = out (+ R) rows.  A, K, W1p, b1,
+ *        geo_D and geo_depth_max are not read (the depths and spans are in the tables). */
+typedef struct cmt_mlp2_affine_args {
+    cmt_mlp2_args m;
+    const double* tab;
+} cmt_mlp2_affine_args;
+
+int cmt_mlp2_affine(const cmt_mlp2_affine_args* args, void* stream);
+int64_t cmt_mlp2_affine_args_size(void);
+
 /* ------------------------------------------------------------------------
  * Multi-head attention core, head_dim = 32 (flash-style, online softmax,
  * f16/bf16 MFMA with fp32 accumulate, or exact-f32 MFMA for dtype CMT_F32;
