@@ -1,3 +1,5 @@
+from .backbones import *  # noqa: F401,F403
 from .dense_heads import *  # noqa: F401,F403
 from .middle_encoders import *  # noqa: F401,F403
+from .necks import *  # noqa: F401,F403
 from .utils import *  # noqa: F401,F403

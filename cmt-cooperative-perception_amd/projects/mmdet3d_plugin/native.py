@@ -183,11 +183,25 @@ class SparseDenseArgs(ctypes.Structure):
                 ("X", _vp), ("ldx", _i64), ("coors", _vp), ("count", _vp), ("out", _vp)]
 
 
+class BevConvArgs(ctypes.Structure):
+    _fields_ = [("B", _int), ("H", _int), ("W", _int), ("Cin", _int), ("Cout", _int), ("stride", _int),
+                ("relu", _int), ("reserved", _int),
+                ("X", _vp), ("ldx", _i64), ("Wt", _vp), ("ldw", _i64), ("shift", _vp), ("Y", _vp), ("ldy", _i64),
+                ("range_flag", _vp)]
+
+
+class BevDeblockArgs(ctypes.Structure):
+    _fields_ = [("B", _int), ("H", _int), ("W", _int), ("Cin", _int), ("Cout", _int), ("k", _int), ("c0", _int),
+                ("Ctot", _int), ("relu", _int), ("reserved", _int),
+                ("X", _vp), ("ldx", _i64), ("Wt", _vp), ("ldw", _i64), ("shift", _vp), ("Y", _vp),
+                ("range_flag", _vp)]
+
+
 STRUCTS = {"gemm": GemmArgs, "attn": AttnArgs, "ln": LnArgs, "chain": ChainArgs, "gemm_ex": GemmExArgs,
            "attn_train": AttnTrainArgs, "ln_train": LnTrainArgs, "bn": BnArgs, "det_loss": DetLossArgs,
            "match_cost": MatchCostArgs, "adamw": AdamwArgs, "mlp2": Mlp2Args, "mlp2_affine": Mlp2AffineArgs, "lsap": LsapArgs,
            "sparse_index": SparseIndexArgs, "sparse_rulebook": SparseRulebookArgs, "sparse_conv": SparseConvArgs,
-           "sparse_dense": SparseDenseArgs}
+           "sparse_dense": SparseDenseArgs, "bev_conv": BevConvArgs, "bev_deblock": BevDeblockArgs}
 
 _LIB = None
 
@@ -284,6 +298,10 @@ def _load():
         "cmt_sparse_rulebook_down": ([P(SparseRulebookArgs), _vp], _int),
         "cmt_sparse_conv": ([P(SparseConvArgs), _vp], _int),
         "cmt_sparse_to_dense": ([P(SparseDenseArgs), _vp], _int),
+        "cmt_bev_conv_args_size": ([], _i64),
+        "cmt_bev_deblock_args_size": ([], _i64),
+        "cmt_bev_conv3x3": ([P(BevConvArgs), _vp], _int),
+        "cmt_bev_deblock": ([P(BevDeblockArgs), _vp], _int),
         "cmt_adamw_step": ([P(AdamwArgs), _vp], _int),
     }
     for name, (args, res) in sig.items():

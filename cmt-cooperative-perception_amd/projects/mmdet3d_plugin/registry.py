@@ -15,8 +15,8 @@ import inspect
 
 __all__ = ["Registry", "build_from_cfg", "HEADS", "TRANSFORMER", "ATTENTION", "TRANSFORMER_LAYER",
            "TRANSFORMER_LAYER_SEQUENCE", "FEEDFORWARD_NETWORK", "BBOX_CODERS", "VOXEL_LAYERS",
-           "NORM_LAYERS", "MIDDLE_ENCODERS", "build_head", "build_transformer", "build_bbox_coder",
-           "build_middle_encoder"]
+           "NORM_LAYERS", "MIDDLE_ENCODERS", "BACKBONES", "NECKS", "build_head", "build_transformer",
+           "build_bbox_coder", "build_middle_encoder", "build_backbone", "build_neck"]
 
 
 class Registry:
@@ -84,6 +84,8 @@ TRANSFORMER_LAYER_SEQUENCE = Registry("transformer-layers sequence", parent=MODE
 FEEDFORWARD_NETWORK = Registry("feed-forward Network", parent=MODELS)
 NORM_LAYERS = Registry("norm layer", parent=MODELS)
 MIDDLE_ENCODERS = Registry("middle_encoder", parent=MODELS)
+BACKBONES = Registry("backbone", parent=MODELS)
+NECKS = Registry("neck", parent=MODELS)
 BBOX_CODERS = Registry("bbox_coder")
 VOXEL_LAYERS = Registry("voxel_layer")
 
@@ -102,3 +104,11 @@ def build_bbox_coder(cfg, **kw):
 
 def build_middle_encoder(cfg, **kw):
     return build_from_cfg(cfg, MIDDLE_ENCODERS, kw or None)
+
+
+def build_backbone(cfg, **kw):
+    return build_from_cfg(cfg, BACKBONES, kw or None)
+
+
+def build_neck(cfg, **kw):
+    return build_from_cfg(cfg, NECKS, kw or None)

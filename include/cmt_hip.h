@@ -877,6 +877,62 @@ int cmt_sparse_rulebook_down(const cmt_sparse_rulebook_args* args, void* stream)
 int cmt_sparse_conv(const cmt_sparse_conv_args* args, void* stream);
 int cmt_sparse_to_dense(const cmt_sparse_dense_args* args, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Dense BEV backbone and neck (additive to ABI 25): the convolutions of mmdet3d's
+ * SECOND (pts_backbone) and SECONDFPN (pts_neck) that cmt_gemm does not cover,
+ * inference only, BN folded by the caller (W' = scale * W, shift per channel).
+ * Semantics restated from mmdet3d 1.0.0rc6 (models/backbones/second.py,
+ * models/necks/second_fpn.py; neither is a dependency):
+ *   SECOND    blocks[i] = conv3x3(in_i, out_i, stride s_i, pad 1) BN ReLU, then
+ *             layer_nums[i] x [conv3x3(out_i, out_i, pad 1) BN ReLU]
+ *   SECONDFPN deblocks[i] = ConvTranspose2d(in_i, out_i, k_i, stride k_i) (or a 1 x 1
+ *             Conv2d for k_i = 1) BN ReLU; outputs concatenated along channels
+ * The stride-1 convs run on cmt_gemm (CMT_A_CONV3X3_NCHW from the fp32 map,
+ * CMT_A_CONV3X3 on pair rows).  Operands here are CMT_F16P rows (leading dimensions
+ * in 16-bit words) and split W; arithmetic as the split cmt_gemm: lo*Whi + hi*Wlo +
+ * hi*Whi on v_mfma_f32_32x32x16_f16, fp32 accumulation in fixed K order, bitwise
+ * repeatable.  range_flag as cmt_gemm_args.range_flag (a pre-activation value that is
+ * non-finite or |x| >= 65520 ORs 1 into the word; NULL: off).  No call synchronises
+ * with the host.
+ *
+ * cmt_bev_conv3x3: Y[(b, yo, xo)][n] = act(sum_{ky,kx,c} X[(b, s yo - 1 + ky,
+ *   s xo - 1 + kx)][c] * Wt[n][(ky*3 + kx) * Cin + c] + shift[n]), zero outside the
+ *   map, Ho = (H - 1) / s + 1, Wo = (W - 1) / s + 1 (an odd extent pads both ends of
+ *   the strided output, an even one only the low end).  X: NHWC pair rows
+ *   [B*H*W][2 Cin]; Wt: pair rows [Cout][2][9 Cin], tap-major K; Y: pair rows
+ *   [B*Ho*Wo][2 Cout]; rows beyond B*Ho*Wo are not written.
+ *   Requirements: stride 1 or 2, Cin % 32 == 0, Cout % 128 == 0, W <= 180,
+ *   ldx, ldw % 8 == 0, X and Wt 16-byte aligned.
+ *
+ * cmt_bev_deblock: Y[b][c0 + n][k y + dy][k x + dx] = act(sum_c X[(b, y, x)][c] *
+ *   Wt[(dy*k + dx) * Cout + n][c] + shift[n]), k in {1, 2, 4} (kernel = stride).
+ *   X: pair rows [B*H*W][2 Cin]; Wt: pair rows [k*k*Cout][2][Cin]; Y: fp32 NCHW
+ *   [B, Ctot, k H, k W], only channels [c0, c0 + Cout) are written (one writer per
+ *   element, stores are runs along x staged through LDS) -- the concatenation of the
+ *   neck costs nothing and the result is what CMT_A_CONV3X3_NCHW reads.
+ *   Requirements: Cin % 32 == 0, Cout % 128 == 0, c0 + Cout <= Ctot, ldx, ldw % 8 == 0,
+ *   X and Wt 16-byte aligned. */
+typedef struct cmt_bev_conv_args {
+    int B, H, W, Cin, Cout, stride, relu, reserved;
+    const void* X; int64_t ldx;
+    const void* Wt; int64_t ldw;
+    const float* shift;                           /* [Cout] */
+    void* Y; int64_t ldy;
+    int* range_flag;
+} cmt_bev_conv_args;
+typedef struct cmt_bev_deblock_args {
+    int B, H, W, Cin, Cout, k, c0, Ctot, relu, reserved;
+    const void* X; int64_t ldx;
+    const void* Wt; int64_t ldw;
+    const float* shift;                           /* [Cout] */
+    float* Y;
+    int* range_flag;
+} cmt_bev_deblock_args;
+int64_t cmt_bev_conv_args_size(void);
+int64_t cmt_bev_deblock_args_size(void);
+int cmt_bev_conv3x3(const cmt_bev_conv_args* args, void* stream);
+int cmt_bev_deblock(const cmt_bev_deblock_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
