@@ -143,7 +143,7 @@ def _mix32(x):
 
 
 def keep_mask(seed, B, H, Nq, Nk, p):
-    """Host restatement of attn_train.hip keep(): keep iff hash >= p * 2^32."""
+    """Host restatement of attn_train.hip keep_row() / keep_col(): keep iff hash >= p * 2^32."""
     bh = np.arange(B * H, dtype=np.uint64)[:, None, None]
     q = np.arange(Nq, dtype=np.uint64)[None, :, None]
     k = np.arange(Nk, dtype=np.uint64)[None, None, :]
@@ -163,6 +163,9 @@ def dn_mask(Nq, Nk, pad, grp):
                                                     (1, 140, 140, 40, 8, False, 0.25), (1, 96, 3000, 0, 0, True, 0.0),
                                                     (2, 150, 1100, 50, 10, True, 0.25), (1, 200, 2049, 0, 0, True, 0.1),
                                                     (1, 77, 300, 40, 8, True, 0.0),
+                                                    # mask + dropout with dQ key splits (2) and, f32, dK / dV query
+                                                    # splits (2) above one: the smallest such shape
+                                                    (1, 300, 300, 60, 20, False, 0.1), (1, 300, 300, 60, 20, True, 0.1),
                                                     # the long-key fp16 path (cross-attention of the training step:
                                                     # attention core with the row statistic, LDS-resident dK/dV,
                                                     # K/V-streaming dQ): ragged key tiles, two batch elements, the
