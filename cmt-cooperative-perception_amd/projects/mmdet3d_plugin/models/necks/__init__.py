@@ -1,3 +1,4 @@
+from .cp_fpn import CPFPN  # noqa: F401
 from .second_fpn import SECONDFPN  # noqa: F401
 
-__all__ = ["SECONDFPN"]
+__all__ = ["SECONDFPN", "CPFPN"]

@@ -197,11 +197,23 @@ class BevDeblockArgs(ctypes.Structure):
                 ("range_flag", _vp)]
 
 
+class FpnLateralArgs(ctypes.Structure):
+    _fields_ = [("B", _int), ("H", _int), ("W", _int), ("Cin", _int), ("Cout", _int), ("Htop", _int), ("Wtop", _int),
+                ("relu", _int),
+                ("X", _vp), ("x_bstride", _i64), ("Wt", _vp), ("ldw", _i64), ("shift", _vp), ("T", _vp), ("ldt", _i64),
+                ("L", _vp), ("ldl", _i64), ("range_flag", _vp)]
+
+
+class RowsToNchwArgs(ctypes.Structure):
+    _fields_ = [("B", _int), ("C", _int), ("HW", _int), ("reserved", _int), ("X", _vp), ("ldx", _i64), ("Y", _vp)]
+
+
 STRUCTS = {"gemm": GemmArgs, "attn": AttnArgs, "ln": LnArgs, "chain": ChainArgs, "gemm_ex": GemmExArgs,
            "attn_train": AttnTrainArgs, "ln_train": LnTrainArgs, "bn": BnArgs, "det_loss": DetLossArgs,
            "match_cost": MatchCostArgs, "adamw": AdamwArgs, "mlp2": Mlp2Args, "mlp2_affine": Mlp2AffineArgs, "lsap": LsapArgs,
            "sparse_index": SparseIndexArgs, "sparse_rulebook": SparseRulebookArgs, "sparse_conv": SparseConvArgs,
-           "sparse_dense": SparseDenseArgs, "bev_conv": BevConvArgs, "bev_deblock": BevDeblockArgs}
+           "sparse_dense": SparseDenseArgs, "bev_conv": BevConvArgs, "bev_deblock": BevDeblockArgs,
+           "fpn_lateral": FpnLateralArgs, "rows_to_nchw": RowsToNchwArgs}
 
 _LIB = None
 
@@ -302,6 +314,10 @@ def _load():
         "cmt_bev_deblock_args_size": ([], _i64),
         "cmt_bev_conv3x3": ([P(BevConvArgs), _vp], _int),
         "cmt_bev_deblock": ([P(BevDeblockArgs), _vp], _int),
+        "cmt_fpn_lateral_args_size": ([], _i64),
+        "cmt_rows_to_nchw_args_size": ([], _i64),
+        "cmt_fpn_lateral": ([P(FpnLateralArgs), _vp], _int),
+        "cmt_rows_to_nchw": ([P(RowsToNchwArgs), _vp], _int),
         "cmt_adamw_step": ([P(AdamwArgs), _vp], _int),
     }
     for name, (args, res) in sig.items():

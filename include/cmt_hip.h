@@ -933,6 +933,55 @@ int64_t cmt_bev_deblock_args_size(void);
 int cmt_bev_conv3x3(const cmt_bev_conv_args* args, void* stream);
 int cmt_bev_deblock(const cmt_bev_deblock_args* args, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Camera neck (additive to ABI 25): the two launches of the FPN over the image
+ * backbone's maps (img_neck, CPFPN) that cmt_gemm does not cover, inference only, BN
+ * folded by the caller.  The 3 x 3 output conv runs on cmt_gemm CMT_A_CONV3X3.
+ * Operands and arithmetic as the cmt_bev_* block: CMT_F16P rows (leading dimensions in
+ * 16-bit words), split W, lo*Whi + hi*Wlo + hi*Whi on v_mfma_f32_32x32x16_f16 with
+ * fp32 accumulation in fixed K order, one writer per element, no atomics on the data
+ * path, bitwise repeatable.  No call synchronises with the host.
+ *
+ * cmt_fpn_lateral: L[(b, y, x)][n] = act(sum_c X[b][c][y][x] * Wt[n][c] + shift[n])
+ *   + T[(b, sy(y), sx(x))][n]: a 1 x 1 conv read transposed from the fp32 NCHW map with
+ *   the coarser level's nearest-upsampled rows added in the epilogue.
+ *   X: fp32 [B][Cin][H*W], channel stride H*W, batch stride x_bstride (floats); every
+ *   value is split in registers (hi = f16(x), lo = f16(x - hi)), no pair-row copy of X
+ *   is written.  Wt: pair rows [Cout][2][Cin].  T: the coarser level's output of this
+ *   same entry, pair rows [B*Htop*Wtop][2 Cout], or NULL for no top-down term; it is
+ *   added in fp32 (hi + lo) after the activation and before the output is split.
+ *   L: pair rows [B*H*W][2 Cout]; rows beyond B*H*W are not written.
+ *   Nearest indices as torch's F.interpolate(size=...): sy(y) = min((int)floorf(y * s),
+ *   Htop - 1) with s = (float)Htop / (float)H (one fp32 multiply); sx alike.
+ *   range_flag: an input value, a pre-activation value or a pre-split output that is
+ *   non-finite or |x| >= 65520 ORs 1 into the word (NULL: off).
+ *   Requirements: Cin % 16 == 0, Cout % 128 == 0, x_bstride >= Cin*H*W, with T
+ *   1 <= Htop <= H and 1 <= Wtop <= W, ldw >= 2 Cin, ldt, ldl >= 2 Cout, all % 8,
+ *   Wt, T and L 16-byte aligned.  H*W is arbitrary.
+ *
+ * cmt_rows_to_nchw: Y[b][c][p] = (float)hi + (float)lo of pair row b*HW + p, element c:
+ *   the inverse of cmt_nchw_to_rows for CMT_F16P rows, through an LDS transpose (loads
+ *   along channels, stores along pixels).  X: pair rows [B*HW][2 C] (ldx >= 2 C, % 8,
+ *   16-byte aligned); Y: fp32 contiguous [B][C][HW].  C % 8 == 0, HW arbitrary. */
+typedef struct cmt_fpn_lateral_args {
+    int B, H, W, Cin, Cout, Htop, Wtop, relu;
+    const float* X; int64_t x_bstride;
+    const void* Wt; int64_t ldw;
+    const float* shift;                           /* [Cout] */
+    const void* T; int64_t ldt;
+    void* L; int64_t ldl;
+    int* range_flag;
+} cmt_fpn_lateral_args;
+typedef struct cmt_rows_to_nchw_args {
+    int B, C, HW, reserved;
+    const void* X; int64_t ldx;
+    float* Y;
+} cmt_rows_to_nchw_args;
+int64_t cmt_fpn_lateral_args_size(void);
+int64_t cmt_rows_to_nchw_args_size(void);
+int cmt_fpn_lateral(const cmt_fpn_lateral_args* args, void* stream);
+int cmt_rows_to_nchw(const cmt_rows_to_nchw_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
