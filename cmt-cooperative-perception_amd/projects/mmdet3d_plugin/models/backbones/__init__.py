@@ -1,3 +1,4 @@
 from .second import SECOND  # noqa: F401
+from .vovnet import VoVNet  # noqa: F401
 
-__all__ = ["SECOND"]
+__all__ = ["SECOND", "VoVNet"]

@@ -208,12 +208,53 @@ class RowsToNchwArgs(ctypes.Structure):
     _fields_ = [("B", _int), ("C", _int), ("HW", _int), ("reserved", _int), ("X", _vp), ("ldx", _i64), ("Y", _vp)]
 
 
+IMG_MAX_SRC = 8   # cmt_hip.h CMT_IMG_MAX_SRC
+
+
+class ImgStemArgs(ctypes.Structure):
+    _fields_ = [("B", _int), ("H", _int), ("W", _int), ("Cin", _int), ("Cout", _int), ("relu", _int),
+                ("X", _vp), ("x_bstride", _i64), ("Wt", _vp), ("shift", _vp), ("Y", _vp), ("ldy", _i64),
+                ("range_flag", _vp)]
+
+
+class ImgConvArgs(ctypes.Structure):
+    _fields_ = [("B", _int), ("H", _int), ("W", _int), ("Cin", _int), ("Cout", _int), ("stride", _int),
+                ("relu", _int), ("nb", _int),
+                ("X", _vp), ("ldx", _i64), ("Wt", _vp), ("ldw", _i64), ("shift", _vp), ("Y", _vp), ("ldy", _i64),
+                ("range_flag", _vp)]
+
+
+class ImgConcatArgs(ctypes.Structure):
+    _fields_ = [("B", _int), ("HW", _int), ("Cout", _int), ("nsrc", _int), ("relu", _int), ("reserved", _int),
+                ("C", _int * IMG_MAX_SRC), ("X", _vp * IMG_MAX_SRC), ("ldx", _i64 * IMG_MAX_SRC),
+                ("Wt", _vp), ("ldw", _i64), ("shift", _vp), ("Y", _vp), ("ldy", _i64), ("part", _vp),
+                ("range_flag", _vp)]
+
+
+class ImgGateArgs(ctypes.Structure):
+    _fields_ = [("B", _int), ("C", _int), ("tiles", _int), ("HW", _int),
+                ("part", _vp), ("Wfc", _vp), ("bias", _vp), ("gate", _vp)]
+
+
+class ImgApplyArgs(ctypes.Structure):
+    _fields_ = [("B", _int), ("HW", _int), ("C", _int), ("reserved", _int),
+                ("X", _vp), ("ldx", _i64), ("gate", _vp), ("R", _vp), ("ldr", _i64), ("Y", _vp), ("ldy", _i64),
+                ("range_flag", _vp)]
+
+
+class ImgPoolArgs(ctypes.Structure):
+    _fields_ = [("B", _int), ("H", _int), ("W", _int), ("C", _int),
+                ("X", _vp), ("ldx", _i64), ("Y", _vp), ("ldy", _i64)]
+
+
 STRUCTS = {"gemm": GemmArgs, "attn": AttnArgs, "ln": LnArgs, "chain": ChainArgs, "gemm_ex": GemmExArgs,
            "attn_train": AttnTrainArgs, "ln_train": LnTrainArgs, "bn": BnArgs, "det_loss": DetLossArgs,
            "match_cost": MatchCostArgs, "adamw": AdamwArgs, "mlp2": Mlp2Args, "mlp2_affine": Mlp2AffineArgs, "lsap": LsapArgs,
            "sparse_index": SparseIndexArgs, "sparse_rulebook": SparseRulebookArgs, "sparse_conv": SparseConvArgs,
            "sparse_dense": SparseDenseArgs, "bev_conv": BevConvArgs, "bev_deblock": BevDeblockArgs,
-           "fpn_lateral": FpnLateralArgs, "rows_to_nchw": RowsToNchwArgs}
+           "fpn_lateral": FpnLateralArgs, "rows_to_nchw": RowsToNchwArgs,
+           "img_stem": ImgStemArgs, "img_conv": ImgConvArgs, "img_concat": ImgConcatArgs, "img_gate": ImgGateArgs,
+           "img_apply": ImgApplyArgs, "img_pool": ImgPoolArgs}
 
 _LIB = None
 
@@ -318,6 +359,19 @@ def _load():
         "cmt_rows_to_nchw_args_size": ([], _i64),
         "cmt_fpn_lateral": ([P(FpnLateralArgs), _vp], _int),
         "cmt_rows_to_nchw": ([P(RowsToNchwArgs), _vp], _int),
+        "cmt_img_stem_args_size": ([], _i64),
+        "cmt_img_conv_args_size": ([], _i64),
+        "cmt_img_concat_args_size": ([], _i64),
+        "cmt_img_gate_args_size": ([], _i64),
+        "cmt_img_apply_args_size": ([], _i64),
+        "cmt_img_pool_args_size": ([], _i64),
+        "cmt_img_concat_tile_rows": ([], _int),
+        "cmt_img_stem": ([P(ImgStemArgs), _vp], _int),
+        "cmt_img_conv3x3": ([P(ImgConvArgs), _vp], _int),
+        "cmt_img_concat1x1": ([P(ImgConcatArgs), _vp], _int),
+        "cmt_img_ese_gate": ([P(ImgGateArgs), _vp], _int),
+        "cmt_img_ese_apply": ([P(ImgApplyArgs), _vp], _int),
+        "cmt_img_maxpool": ([P(ImgPoolArgs), _vp], _int),
         "cmt_adamw_step": ([P(AdamwArgs), _vp], _int),
     }
     for name, (args, res) in sig.items():

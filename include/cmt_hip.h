@@ -982,6 +982,118 @@ int64_t cmt_rows_to_nchw_args_size(void);
 int cmt_fpn_lateral(const cmt_fpn_lateral_args* args, void* stream);
 int cmt_rows_to_nchw(const cmt_rows_to_nchw_args* args, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Image backbone (additive to ABI 25): the launches of VoVNet-eSE (img_backbone, the
+ * non-depthwise specs), inference only, BN folded by the caller.  A map between layers
+ * is NHWC CMT_F16P pair rows [B*H*W][2 C] (leading dimensions in 16-bit words);
+ * arithmetic of the three GEMM-like kernels as the cmt_bev_* block: lo*Whi + hi*Wlo +
+ * hi*Whi on v_mfma_f32_32x32x16_f16, fp32 accumulation in fixed K order, one writer
+ * per element, no atomics on the data path, bitwise repeatable.  range_flag: a
+ * pre-activation value (stem: also a pixel; apply: the result) that is non-finite or
+ * |x| >= 65520 ORs 1 into the word (NULL: off).  No call synchronises with the host.
+ * No entry has a width limit; B*H*W < 2^31, byte offsets are 64-bit.
+ *
+ * cmt_img_stem: Y[(b, yo, xo)][n] = act(sum_{ky,kx,c} X[b][c][2 yo - 1 + ky][2 xo - 1 + kx]
+ *   * Wt[n][(ky*3 + kx) * Cin + c] + shift[n]): the 3 x 3 / stride 2 / pad 1 conv straight
+ *   from the fp32 NCHW image (channel stride H*W, batch stride x_bstride floats), every
+ *   pixel split in registers.  Wt: pair rows [Cout][2][32], K = 9 Cin zero-padded to 32.
+ *   Ho = (H - 1) / 2 + 1, Wo alike.  Requirements: 1 <= Cin <= 3, Cout % 32 == 0,
+ *   ldy >= 2 Cout, Wt 16-byte aligned.
+ *
+ * cmt_img_conv3x3: the contract of cmt_bev_conv3x3 (stride 1 or 2, pad 1, pair rows to
+ *   pair rows, Wt pair rows [Cout][2][9 Cin] tap-major) without its width limit and with
+ *   Cin % 32 == 0, Cout % 32 == 0, Cout <= 256; ldx, ldw % 8 == 0, X and Wt 16-byte
+ *   aligned.  A wave owns 32 output rows x 32 nb columns: all Cout (nb = Cout / 32) where the
+ *   row tiles alone fill the device, fewer on small maps; nb = 0 lets the entry choose
+ *   from the row count and the device's compute units.  The result does not depend on nb.
+ *
+ * cmt_img_concat1x1: Y[(b, p)][n] = act(sum_s sum_c X_s[(b, p)][c] * Wt[n][off_s + c]
+ *   + shift[n]), off_s = C_0 + ... + C_{s-1}: the 1 x 1 conv of a channel concatenation
+ *   that is never written.  Up to CMT_IMG_MAX_SRC sources, each pair rows [B*HW][2 C_s]
+ *   with its own leading dimension ldx_s >= 2 C_s (a source may be the 2 C_s-word column
+ *   slice of a wider row buffer; the words outside it are not read).
+ *   Wt: pair rows [Cout][2][K], K = sum C_s.  Tiles of cmt_img_concat_tile_rows() pixels
+ *   lie within one image.  part (or NULL): fp32 [B][tiles][Cout], tiles =
+ *   ceil(HW / tile rows): the sum over the tile's pixels of the values as stored
+ *   ((float)hi + (float)lo after the activation), summed in a fixed order.
+ *   Requirements: 1 <= nsrc <= 8, C_s % 32 == 0, Cout % 128 == 0, ldx_s, ldw % 8 == 0,
+ *   X_s and Wt 16-byte aligned.
+ *
+ * cmt_img_ese_gate: gate[b][o] = hsigmoid(sum_c Wfc[o][c] * (sum_t part[b][t][c]) / HW
+ *   + bias[o]), hsigmoid(t) = min(max(t + 3, 0), 6) / 6.  fp32 FMA, tiles summed in
+ *   ascending order.  Wfc: fp32 [C][C]; gate: fp32 [B][C].  C % 4 == 0, C <= 8192.
+ *
+ * cmt_img_ese_apply: Y[(b, p)][c] = pair(x * gate[b][c] (+ r)), x and r un-paired as
+ *   (float)hi + (float)lo; R NULL: no identity term.  Y may be X.  C % 8 == 0, leading
+ *   dimensions % 8, X, R and Y 16-byte aligned.
+ *
+ * cmt_img_maxpool: 3 x 3 / stride 2 / ceil-mode / no-pad max on pair rows: windows are
+ *   clipped at the bottom / right edge, Ho = (H - 2) / 2 + 1, Wo alike.  Values compare
+ *   as (float)hi + (float)lo (a NaN wins, as in torch); the winning pair is copied
+ *   unchanged, the first of equal maxima in window order.  H, W >= 2, C % 8 == 0. */
+#define CMT_IMG_MAX_SRC 8
+typedef struct cmt_img_stem_args {
+    int B, H, W, Cin, Cout, relu;
+    const float* X; int64_t x_bstride;
+    const void* Wt;                               /* [Cout][2][32] */
+    const float* shift;                           /* [Cout] */
+    void* Y; int64_t ldy;
+    int* range_flag;
+} cmt_img_stem_args;
+typedef struct cmt_img_conv_args {
+    int B, H, W, Cin, Cout, stride, relu;
+    int nb;                                       /* 32-column blocks per workgroup, a divisor of Cout / 32; 0: chosen */
+    const void* X; int64_t ldx;
+    const void* Wt; int64_t ldw;
+    const float* shift;                           /* [Cout] */
+    void* Y; int64_t ldy;
+    int* range_flag;
+} cmt_img_conv_args;
+typedef struct cmt_img_concat_args {
+    int B, HW, Cout, nsrc, relu, reserved;
+    int C[CMT_IMG_MAX_SRC];
+    const void* X[CMT_IMG_MAX_SRC];
+    int64_t ldx[CMT_IMG_MAX_SRC];
+    const void* Wt; int64_t ldw;
+    const float* shift;                           /* [Cout] */
+    void* Y; int64_t ldy;
+    float* part;                                  /* [B][tiles][Cout] or NULL */
+    int* range_flag;
+} cmt_img_concat_args;
+typedef struct cmt_img_gate_args {
+    int B, C, tiles, HW;
+    const float* part;                            /* [B][tiles][C] */
+    const float* Wfc;                             /* [C][C] */
+    const float* bias;                            /* [C] */
+    float* gate;                                  /* [B][C] */
+} cmt_img_gate_args;
+typedef struct cmt_img_apply_args {
+    int B, HW, C, reserved;
+    const void* X; int64_t ldx;
+    const float* gate;                            /* [B][C] */
+    const void* R; int64_t ldr;
+    void* Y; int64_t ldy;
+    int* range_flag;
+} cmt_img_apply_args;
+typedef struct cmt_img_pool_args {
+    int B, H, W, C;
+    const void* X; int64_t ldx;
+    void* Y; int64_t ldy;
+} cmt_img_pool_args;
+int64_t cmt_img_stem_args_size(void);
+int64_t cmt_img_conv_args_size(void);
+int64_t cmt_img_concat_args_size(void);
+int64_t cmt_img_gate_args_size(void);
+int64_t cmt_img_apply_args_size(void);
+int64_t cmt_img_pool_args_size(void);
+int cmt_img_concat_tile_rows(void);
+int cmt_img_stem(const cmt_img_stem_args* args, void* stream);
+int cmt_img_conv3x3(const cmt_img_conv_args* args, void* stream);
+int cmt_img_concat1x1(const cmt_img_concat_args* args, void* stream);
+int cmt_img_ese_gate(const cmt_img_gate_args* args, void* stream);
+int cmt_img_ese_apply(const cmt_img_apply_args* args, void* stream);
+int cmt_img_maxpool(const cmt_img_pool_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
