@@ -412,6 +412,8 @@ extern "C" int cmt_chain(const cmt_chain_args* ap, void* stream) {
         CMT_REQUIRE((a.X || a.xpart) && a.Wo && a.W1 && a.W2 && a.WS,
                     "cmt_chain: chain B1 needs X (or xpart), Wo, W1, W2, WS");
     CMT_REQUIRE(a.xpart == nullptr || a.dtype == CMT_F16P, "cmt_chain: xpart is a split-chain (CMT_F16P) input");
+    CMT_REQUIRE(a.Wh == nullptr || (a.kind == 2 && a.dtype == CMT_F16P),
+                "cmt_chain: Wh (head weights) is a split chain B2 (CMT_F16P) input");
     if (a.kind == 2) {
         CMT_REQUIRE(a.WS && a.OUT, "cmt_chain: chain B2 needs WS and OUT");
         CMT_REQUIRE(a.Wn == nullptr || (a.P && a.Q), "cmt_chain: chain B2 with Wn needs P and Q");

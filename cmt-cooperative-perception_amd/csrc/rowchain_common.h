@@ -1,7 +1,8 @@
 // What the row-block chains of rowchain.hip (f16 / bf16) and rowchain_x3.hip
 // (f16 pairs) share: the workgroup geometry, the parameter-block layout, the
 // lane -> column map, the fp32 row / partials-tile accessors, the workgroups
-// per row block, the row LayerNorm and the swizzled operand-image address.
+// per row block (chain_parts: B2's grows by the split chain's head parts), the
+// row LayerNorm and the swizzled operand-image address.
 // Included by those two files only.
 #pragma once
 #include "cmt_common.h"
@@ -26,8 +27,10 @@ constexpr int bo = 0, ln1_w = 256, ln1_b = 512, b1 = 768, b2 = 1792, ln2_w = 204
 static_assert(prm_a::bq + CE == PRM_A && prm_b::bn + 3 * CE == PRM_B, "parameter blocks end with bq / bn");
 
 // workgroups per row block: chain A 1, B1 4 (FFN quarters), B2 3 (Q | K | V blocks; 1 on the last layer)
-__host__ __device__ constexpr int chain_parts(int kind, bool has_next) {
-    return kind == 0 ? 1 : kind == 1 ? 4 : (has_next ? 3 : 1);
+// plus, split chain B2 with head weights (cmt_chain_args.Wh), one per 256 columns of the task heads'
+// first conv (head_parts = ceil(head_cols / 256))
+__host__ __device__ constexpr int chain_parts(int kind, bool has_next, int head_parts = 0) {
+    return kind == 0 ? 1 : kind == 1 ? 4 : (has_next ? 3 : 1) + head_parts;
 }
 
 // column of lane value r (4 consecutive per group r >> 2) in wave w's 32-column tile

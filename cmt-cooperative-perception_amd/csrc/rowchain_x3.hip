@@ -14,6 +14,10 @@
 //   kind 2, chain B2, 3 workgroups per row block (1 on the last layer; g = Q|K|V block):
 //       sum of the 4 partials -> norms[2] -> Y; g = 0: post_norm -> OUT (+ its pair copy OUT16)
 //       -> next layer's self-attn in_proj block g (Q|K read Y + pos, V reads Y), head-split pairs
+//     with head weights (Wh: the task heads' first conv of this layer, final_kernel = 1, no bias)
+//     HP = ceil(head_cols / 256) more workgroups per row block, g = base + hb: the same sum ->
+//     norms[2] -> post_norm (+ nan_to_num) as g = 0, its pairs (what OUT16 would hold) times head
+//     block hb -> fp32 H1[row][256 hb ..); they write nothing else, and OUT16 is then not needed
 //
 // Every GEMM operand is an f16 pair (cmt_hip.h CMT_F16P) and every product the
 // three f16 MFMA passes hi*hi + lo*hi + hi*lo with fp32 accumulation, as the
@@ -141,8 +145,11 @@ __global__ __launch_bounds__(NTC, 1) void chain_x3_kernel(cmt_chain_args a) {
     e.lh = e.lane >> 5;
     const bool has_next = a.Wn != nullptr;
     constexpr int NSUB = KIND == 0 ? 2 : KIND == 1 ? 3 : 1;
-    const int parts = chain_parts(KIND, has_next);
+    // B2 with head weights: head parts g >= base behind the Q|K|V parts (block hb = g - base of the heads)
+    const int base = chain_parts(KIND, has_next);
+    const int parts = KIND == 2 && a.Wh ? base + (a.head_cols + CE - 1) / CE : base;
     const int rb = blockIdx.x / parts, g = blockIdx.x - rb * parts;
+    const bool head = KIND == 2 && g >= base;
     const int m0 = rb * RB;
     const int row = min(m0 + e.lr, a.rows - 1);
     const bool row_ok = m0 + e.lr < a.rows;
@@ -164,11 +171,15 @@ __global__ __launch_bounds__(NTC, 1) void chain_x3_kernel(cmt_chain_args a) {
         wst.base[2] = frag_base(a.W2, g, e.wave, e.lane);   // fc2 K block g
         wst.lo_off[0] = (int64_t)CE * CE;
         wst.lo_off[1] = wst.lo_off[2] = (int64_t)4 * CE * CE;
+    } else if (head) {
+        // head block hb of the pack zero-padded to whole 256-row blocks (lo pack behind the padded hi pack)
+        wst.base[0] = frag_base(a.Wh, g - base, e.wave, e.lane);
+        wst.lo_off[0] = (int64_t)((a.head_cols + CE - 1) / CE) * CE * CE;
     } else {
         wst.base[0] = frag_base(has_next ? a.Wn : a.prm, g, e.wave, e.lane);   // next in_proj block g
         wst.lo_off[0] = (int64_t)3 * CE * CE;
     }
-    const bool gemm = KIND != 2 || has_next;
+    const bool gemm = KIND != 2 || has_next || head;
 
     // ---- prologue loads, in the order their values are needed (vmcnt counts in issue order: a
     // wait for a value loaded after the weight ring's first WRING steps would wait for those
@@ -402,7 +413,7 @@ __global__ __launch_bounds__(NTC, 1) void chain_x3_kernel(cmt_chain_args a) {
     float y[VPL];
 #pragma unroll
     for (int i = 0; i < VPL; ++i) y[i] = v[i];
-    if (g == 0) {
+    if (g == 0 || head) {   // a head part forms the layer output as g == 0 does (never with MAX_INTO)
         e.layernorm(v, prm_b::post_w, prm_b::post_b, eps);              // post_norm -> layer output
 #pragma unroll
         for (int i = 0; i < VPL; ++i) {
@@ -412,16 +423,34 @@ __global__ __launch_bounds__(NTC, 1) void chain_x3_kernel(cmt_chain_args a) {
             v[i] = x;
         }
     }
-    if (has_next) {
+    if (gemm) {
         float u[VPL];
 #pragma unroll
-        for (int i = 0; i < VPL; ++i) u[i] = y[i] + qp[i];              // qp = 0 for the V block
+        for (int i = 0; i < VPL; ++i) u[i] = head ? v[i] : y[i] + qp[i];   // qp = 0 for the V block
         STAMP(2, 4);
-        e.put_act(actA, u);                                             // (y + pos) (Q|K) / y (V) pairs
+        // (y + pos) (Q|K) / y (V) pairs; a head part: the layer output's pairs, the split store_pair4
+        // gives OUT16 -- the operand of the task heads' first conv
+        e.put_act(actA, u);
         barrier_mem();
         STAMP(2, 5);
         e.sub_gemm<0>(actA, wst, acc);
         STAMP(2, 6);
+    }
+    if (head) {
+        // The task heads' first grouped conv at final_kernel = 1 (a per-row linear map, no bias:
+        // SeparateTaskHead builds it with bias=False): fp32 rows H1[row][256 hb + col].  The padded
+        // tail block's waves past head_cols multiplied zero weights and store nothing; a head part
+        // writes neither Y, OUT, OUT16 nor Q.
+        const int c_blk = (g - base) * CE;
+#pragma unroll
+        for (int gg = 0; gg < 4; ++gg) {
+            const int c = c_blk + e.col(4 * gg);
+            if (row_ok && c < a.head_cols)
+                *(f32x4*)(a.H1 + (int64_t)row * a.head_cols + c) =
+                    f32x4{acc[4 * gg], acc[4 * gg + 1], acc[4 * gg + 2], acc[4 * gg + 3]};
+        }
+        STAMP(2, 7);
+        return;
     }
     if (row_ok) {
         if (g == 0) {
@@ -465,7 +494,14 @@ int cmt_chain_x3(const cmt_chain_args& a, hipStream_t s) {
     CMT_REQUIRE(a.xpart == nullptr || (a.kind == 1 && a.xsplits == XS && a.Nq > 0 && a.rows % a.Nq == 0 &&
                                        (uintptr_t)a.xpart % 16 == 0),
                 "cmt_chain: xpart (split partials) feeds chain B1 with xsplits == 8, rows = B * Nq, 16-byte aligned");
-    const unsigned grid = (unsigned)(cdiv(a.rows, RB) * chain_parts(a.kind, a.Wn != nullptr));
+    CMT_REQUIRE(a.Wh == nullptr || (a.kind == 2 && a.H1 && a.head_cols > 0 && a.head_cols <= 1024 &&
+                                    a.head_cols % 64 == 0 && ((uintptr_t)a.Wh | (uintptr_t)a.H1) % 16 == 0),
+                "cmt_chain: Wh (head weights) feeds chain B2 with H1, head_cols a multiple of 64 in (0, 1024], "
+                "16-byte aligned");
+    // the cooperative heads max-fuse OUT over the agents before the task heads read it
+    CMT_REQUIRE(a.Wh == nullptr || !(a.out_flags & CMT_LN_MAX_INTO), "cmt_chain: Wh cannot go with CMT_LN_MAX_INTO");
+    const unsigned grid =
+        (unsigned)(cdiv(a.rows, RB) * chain_parts(a.kind, a.Wn != nullptr, a.Wh ? cdiv(a.head_cols, CE) : 0));
     if (a.kind == 0) chain_x3_kernel<0, WRING_DEFAULT><<<grid, NTC, 0, s>>>(a);
     else if (a.kind == 1 && a.xpart) chain_x3_kernel<1, WRING_DEFAULT, true><<<grid, NTC, 0, s>>>(a);
     else if (a.kind == 1) chain_x3_kernel<1, WRING_DEFAULT><<<grid, NTC, 0, s>>>(a);

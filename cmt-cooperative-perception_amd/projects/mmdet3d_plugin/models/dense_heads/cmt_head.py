@@ -135,9 +135,15 @@ class SeparateTaskHead(nn.Module):
                 if n == "height":
                     height_col = start
                 start += o
+            w1p = to_dtype(torch.cat(w1, 1), prec.gemm)
+            # final_kernel = 1 at the split policy: per decoder layer the conv's pair weight as chain
+            # B2's head pack (cmt_chain_args.Wh; engine._heads_in_chain), built with the other packs
+            w1_chain = None
+            if is_split(w1p) and k == 1 and C == 256:
+                w1_chain = [native.pack_chain_heads(w1p[l]) for l in range(G)]
             return dict(names=names, head_out=outs, out_total=start, k=k, center_col=center_col,
                         height_col=height_col,
-                        w1=to_dtype(torch.cat(w1, 1), prec.gemm),
+                        w1=w1p, w1_chain=w1_chain,
                         gw=torch.cat(gw, 1).detach().float().contiguous(),
                         gb=torch.cat(gb, 1).detach().float().contiguous(),
                         w2=torch.cat(w2, 1).detach().float().contiguous(),
@@ -282,6 +288,7 @@ def gt_from_metas(img_metas):
 class CmtHead(HeadTrainMixin, HeadEngineMixin, nn.Module):
     """cmt_head.py:206-919 (fusion head: BEV + multi-view image memory)."""
     variant = "fusion"
+    chain_heads_ok = True   # one agent: the task head's first conv may run inside chain B2 (engine._heads_in_chain)
 
     def __init__(self, in_channels, num_query=900, hidden_dim=128, depth_num=64, norm_bbox=True,
                  downsample_scale=8, scalar=10, noise_scale=1.0, noise_trans=0.0, dn_weight=1.0, split=0.75,
@@ -342,6 +349,17 @@ class CmtHead(HeadTrainMixin, HeadEngineMixin, nn.Module):
         L = self.transformer.decoder.num_layers
         outs = torch.empty((L, B * self.num_query, self.hidden_dim), dtype=torch.float32,
                            device=self.reference_points.weight.device)
+        if self.chain_heads_ok and len(agents) == 1 and shard is None and self._heads_in_chain(prec):
+            # one agent, nothing max-fused: the task plan is made ahead of the decoder, whose chain B2
+            # runs the task head's first conv layer by layer into the plan's H1 (no pair copy of the
+            # outputs, no GEMM launch behind the last layer)
+            self._h2d_seq = 0
+            plan = self._task_plan(outs, B, prec, heads_in_chain=True)
+            x, x_img, metas = agents[0]
+            self._decode_agent(x, x_img, metas, B, outs, native.LN_NAN_TO_NUM, self.variant, prec,
+                               heads=plan["heads"])
+            self._task_run(plan, 0, L)
+            return plan["ret"]
         outs16 = None
         if prec.gemm != torch.float32:
             outs16 = op_empty(B * self.num_query, self.hidden_dim, prec.gemm, outs.device, lead=(L,))

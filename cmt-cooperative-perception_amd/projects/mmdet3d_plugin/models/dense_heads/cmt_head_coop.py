@@ -43,6 +43,9 @@ def get_vehicle_image_metas(img_metas):
 class CmtHeadCoop(CmtHead):
     """cmt_head_coop.py:72-809 (fusion: LiDAR BEV + camera per agent)."""
     variant = "fusion"
+    # the agents' outputs are max-fused before the task heads read them: their first conv stays a
+    # GEMM over the fused outputs, never a part of one agent's chain B2 (engine._heads_in_chain)
+    chain_heads_ok = False
 
     def forward_single(self, x_vehicle, x_infrastructure, x_img_vehicle, x_img_infrastructure, img_metas):
         B = len(img_metas)

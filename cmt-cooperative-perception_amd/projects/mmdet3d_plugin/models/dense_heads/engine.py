@@ -19,7 +19,9 @@ fixed sequence of gfx950 kernels over HBM-resident buffers:
   coop max        fused into the post_norm kernel (cmt_head_coop.py:383-389)
   task heads      grouped Conv1d as one batched (implicit conv1d) GEMM over the
                   decoder layers, then GroupLayerNorm1d+ReLU, conv #2 and the
-                  box epilogue (cmt_head.py:136-203, 501-513)
+                  box epilogue (cmt_head.py:136-203, 501-513); at the reference's
+                  numerics with final_kernel = 1 and one agent the first conv runs
+                  inside the decoder's chain B2 instead (_heads_in_chain)
 
 The reference computes the BEV positional encoding, the coordinate encodings
 and every layer's K/V projection again on each forward; so does this engine
@@ -422,12 +424,13 @@ class HeadEngineMixin:
         return qpos, first_ops is not None
 
     # ------------------------------------------------------------------ per agent
-    def _decode_agent(self, x, x_img, metas, B, out, post_flags, variant, prec, out16=None):
+    def _decode_agent(self, x, x_img, metas, B, out, post_flags, variant, prec, out16=None, heads=None):
         """One get_outs_dec (cmt_head_coop.py:341-360) / the decoder part of
         forward_single (cmt_head.py:481-499); writes post-normed, nan_to_num'ed
         decoder outputs [L, B*Nq, C] into ``out`` (max-merged when post_flags
         has LN_MAX_INTO); ``out16`` receives the same values in the compute
-        dtype (f16/bf16 policy)."""
+        dtype (f16/bf16 policy).  ``heads`` (_heads_in_chain): the task head's
+        first conv handed down to the decoder's chain B2 (run_rows)."""
         pk = self._engine_pack(prec)
         C = self.hidden_dim
         dev = self.reference_points.weight.device
@@ -544,7 +547,8 @@ class HeadEngineMixin:
         if side is None:
             qpos, _ = self._query_pos(B, metas, use_img, pk, cams=cams)
         dec.run_rows(mem, pos, qpos, B=B, Nk=Nk, Nq=Nq, out=out, post_flags=post_flags, prec=prec,
-                     kv_operands=(mem, pos) if lowp else None, out16=out16 if lowp else None, state=state)
+                     kv_operands=(mem, pos) if lowp else None, out16=out16 if lowp else None, state=state,
+                     **(dict(heads=heads) if heads is not None else {}))
         return out
 
     def _side_stream(self, dev):
@@ -566,9 +570,25 @@ class HeadEngineMixin:
         self._task_run(plan, 0, outs_dec.shape[0])
         return plan["ret"]
 
-    def _task_plan(self, outs_dec, B, prec, outs16=None):
+    def _heads_in_chain(self, prec):
+        """Whether the task head's first conv runs inside the decoder's chain B2
+        (OPTIONS.chain_heads): the split ('ref') chains, exactly one task head and
+        final_kernel = 1, where the conv is a per-row linear map.  The caller adds
+        the condition it alone knows: one agent, so nothing is max-fused into the
+        outputs after a chain wrote them."""
+        dec = self.transformer.decoder
+        if not (OPTIONS.chain_heads and prec.gemm == SPLIT and dec.fused_supported() and dec._use_chain(prec)
+                and len(self.task_heads) == 1 and self.task_heads[0].final_kernel == 1):
+            return False
+        tp = self.task_heads[0].packed(prec)
+        return tp["w1_chain"] is not None and len(tp["names"]) * 64 <= 1024
+
+    def _task_plan(self, outs_dec, B, prec, outs16=None, heads_in_chain=False):
         """Output buffers of the task heads (allocated on the current stream)
-        and the per-task packed weights; _task_run fills layers [l0, l1)."""
+        and the per-task packed weights; _task_run fills layers [l0, l1).
+        ``heads_in_chain``: the plan is made ahead of the decoder, which fills
+        H1 itself (plan["heads"] goes to run_rows); _task_run then runs the tail
+        only."""
         L = outs_dec.shape[0]
         Nq = self.num_query
         ref = self.reference_points.weight.detach()
@@ -586,21 +606,31 @@ class HeadEngineMixin:
                 outs[name] = OUT[..., start:start + n]
                 start += n
             ret.append(outs)
+        if heads_in_chain:
+            # (the reference points are expanded by _task_run, behind the decoder as before)
+            tp, _, H1, _ = tasks[0]
+            return dict(tasks=tasks, ret=ret, refB=None, B=B, ref=ref,
+                        heads=dict(Wh=tp["w1_chain"], H1=H1, head_cols=H1.shape[-1]))
         refB = ref.unsqueeze(0).expand(B, Nq, 3).contiguous()
         return dict(tasks=tasks, ret=ret, refB=refB, B=B)
 
     def _task_run(self, plan, l0, l1):
         """Task heads of decoder layers [l0, l1): the grouped conv as one GEMM
         batched over the layers, then GroupLayerNorm1d + ReLU, conv #2 and the
-        box epilogue (cmt_head.py:136-203, 501-513)."""
+        box epilogue (cmt_head.py:136-203, 501-513).  A plan made with
+        heads_in_chain has its H1 from the decoder's chain B2: no GEMM here."""
         B, Nq, C, n = plan["B"], self.num_query, self.hidden_dim, l1 - l0
+        if plan["refB"] is None:
+            plan["refB"] = plan["ref"].unsqueeze(0).expand(B, Nq, 3).contiguous()
         for tp, A, H1, OUT in plan["tasks"]:
             nh, k = len(tp["names"]), tp["k"]
             width = nh * 64
-            # the grouped conv's groups are the decoder layers: weights of groups [l0, l1)
-            native.gemm(A[l0:l1], tp["w1"][l0:l1], H1[l0:l1], M=B * Nq, N=width, K=k * C, lda=C, ldw=k * C, ldc=width,
-                        batch=n, a_bstride=B * Nq * C, w_bstride=width * k * C, c_bstride=B * Nq * width,
-                        a_mode=native.A_CONV1D3 if k == 3 else native.A_ROWS, seg_len=Nq)
+            if "heads" not in plan:   # else chain B2 of every decoder layer wrote H1
+                # the grouped conv's groups are the decoder layers: weights of groups [l0, l1)
+                native.gemm(A[l0:l1], tp["w1"][l0:l1], H1[l0:l1], M=B * Nq, N=width, K=k * C, lda=C, ldw=k * C,
+                            ldc=width, batch=n, a_bstride=B * Nq * C, w_bstride=width * k * C,
+                            c_bstride=B * Nq * width, a_mode=native.A_CONV1D3 if k == 3 else native.A_ROWS,
+                            seg_len=Nq)
             # box_epilogue = False (diagnostics / parity at the logit level): center and height
             # come out as the raw task-head logits, before + inverse_sigmoid(ref) and sigmoid
             epi = getattr(self, "box_epilogue", True)

@@ -618,20 +618,27 @@ class PETRTransformerDecoder(nn.Module):
         return self._pack.get("decoder", params, prec.name, build)
 
     def run_rows(self, mem, pos, qpos, *, B, Nk, Nq, out=None, post_flags=native.LN_NAN_TO_NUM, prec=None,
-                 tgt0=None, kv_operands=None, out16=None, state=None):
+                 tgt0=None, kv_operands=None, out16=None, state=None, heads=None):
         """Fused decoder.  mem/pos: [B*Nk, C] fp32 batch-major rows, qpos:
         [B*Nq, C] fp32.  Writes the post-normed layer outputs to
         out [L, B*Nq, C] (fp32) with ``post_flags`` (nan_to_num / max-into).
         Under an f16/bf16 policy the producers may hand over the K/V GEMM
         operands already in the compute dtype: kv_operands = (lowp(mem),
         lowp(mem + pos)); mem/pos are then unused.  ``out16`` (f16/bf16 policy
-        only): a compute-dtype copy of ``out`` for the task-head GEMM."""
+        only): a compute-dtype copy of ``out`` for the task-head GEMM.
+        ``heads`` (split chains only; the engine's _heads_in_chain): dict(Wh =
+        per-layer head packs (native.pack_chain_heads), H1 = fp32 [L, B*Nq,
+        head_cols], head_cols) -- chain B2 of layer l then also computes the task
+        head's first conv of that layer into H1[l] (cmt_chain_args.Wh), and no
+        ``out16`` is needed."""
         if not self.fused_supported():
             raise NotImplementedError("fused decoder supports the CMT post-norm layout (C=256, 8x32 heads)")
         prec = get_precision(prec)
+        if heads is not None and not (prec.gemm == SPLIT and self._use_chain(prec)):
+            raise RuntimeError("run_rows: heads (the task head's first conv in chain B2) needs the split chains")
         if prec.gemm != torch.float32:
             return self._run_rows_lowp(mem, pos, qpos, B=B, Nk=Nk, Nq=Nq, out=out, post_flags=post_flags, prec=prec,
-                                       tgt0=tgt0, kv_operands=kv_operands, out16=out16, state=state)
+                                       tgt0=tgt0, kv_operands=kv_operands, out16=out16, state=state, heads=heads)
         pk = self.packed(prec)
         L, C, H = self.num_layers, self.embed_dims, self.embed_dims // 32
         dev = mem.device
@@ -823,7 +830,7 @@ class PETRTransformerDecoder(nn.Module):
                                     kmax_ld=ent["ld"], kmax_plane0=ent["p0"], keep_partials=keep)
 
     def _run_rows_lowp(self, mem, pos, qpos, *, B, Nk, Nq, out, post_flags, prec, tgt0, kv_operands, out16=None,
-                       state=None):
+                       state=None, heads=None):
         """run_rows under an f16/bf16/split policy: every GEMM operand is
         produced in the compute format by the kernel before it (LayerNorm
         writes lowp(y) and lowp(y + query_pos) beside the fp32 residual stream,
@@ -863,9 +870,9 @@ class PETRTransformerDecoder(nn.Module):
             r0.copy_(tgt0)
             native.add_cast(r0, rows=rows, C=C, Yl=st["tl"], Yp=st["tp"], P=qpos)
         return self._layers(st, qpos, kv, kvl, r0, B=B, Nk=Nk, Nq=Nq, out=out, post_flags=post_flags, prec=prec,
-                            out16=out16)
+                            out16=out16, heads=heads)
 
-    def _layers(self, st, qpos, kv, kvl, r0, *, B, Nk, Nq, out, post_flags, prec, out16):
+    def _layers(self, st, qpos, kv, kvl, r0, *, B, Nk, Nq, out, post_flags, prec, out16, heads=None):
         """The layer walk of both lowp paths (row-block chains, or separate
         launches: CMT_CHAIN=0 / shapes the chains do not take): per layer the
         self block, then the cross block.  ``r0``: layer 0's residual (None: the
@@ -874,7 +881,7 @@ class PETRTransformerDecoder(nn.Module):
             if l > 0 or not st["layer0_done"]:
                 self._self_block(st, l, qpos, r0 if l == 0 else st["tgt"], B=B, Nq=Nq, prec=prec)
             self._cross_block(st, l, qpos, kv, kvl[l], B=B, Nk=Nk, Nq=Nq, out=out, post_flags=post_flags, prec=prec,
-                              out16=out16)
+                              out16=out16, heads=heads)
         if out16 is not None and not st["chain"]:   # chain B2 writes out16 itself
             if prec.gemm == SPLIT:
                 native.split_rows(out.view(-1, self.embed_dims), out16.view(-1, 2, self.embed_dims))
@@ -899,13 +906,14 @@ class PETRTransformerDecoder(nn.Module):
         else:
             self._self_out_q(st, lw, qpos, R, rows=rows, Nq=Nq, C=C)
 
-    def _cross_block(self, st, l, qpos, kv, ent, *, B, Nk, Nq, out, post_flags, prec, out16):
+    def _cross_block(self, st, l, qpos, kv, ent, *, B, Nk, Nq, out, post_flags, prec, out16, heads=None):
         """Cross block of layer l: the cross-attention core (q = qc; K/V from
         _project_kv), out_proj + t1n + norms[1], the FFN + norms[2] -> tgt (the
         next query) and post_norm -> out[l].  Chain path: chain B1 (out_proj +
         norms[1] + one FFN quarter per workgroup -> fp32 partials), chain B2
         (partials -> norms[2] + post_norm + the next layer's in_proj) -- see
-        rowchain.hip; else the separate GEMM / layernorm_ex launches."""
+        rowchain.hip; else the separate GEMM / layernorm_ex launches.  ``heads``
+        (run_rows): chain B2 also runs the task head's first conv into H1[l]."""
         pk = self.packed(prec)
         lw = pk["layers"][l]
         L, C, rows = self.num_layers, self.embed_dims, B * Nq
@@ -919,7 +927,8 @@ class PETRTransformerDecoder(nn.Module):
                          R=t1n, W2=lw["f2_wp"], WS=st["cws"], **self._xpart(ws, xs, prec))
             native.chain(2, None, qpos if nxt is not None else None, prm, None, None, tgt, rows=rows,
                          Nq=Nq, eps=eps, Wn=nxt, OUT=out, out_offset=l * rows * C, out_flags=post_flags,
-                         Q=st["qkv"] if nxt is not None else None, WS=st["cws"], OUT16=out16)
+                         Q=st["qkv"] if nxt is not None else None, WS=st["cws"], OUT16=out16,
+                         **self._head_part(heads, l))
             return
         tl, tp, hf, t1, o, ksp = (st[k] for k in ("tl", "tp", "hf", "t1", "o", "ksp"))
         FF = hf.shape[-1]
@@ -938,6 +947,12 @@ class PETRTransformerDecoder(nn.Module):
         native.layernorm_ex(t1, w2, b2, rows=rows, C=C, ldx=C, eps=e2, Y=tgt, ldy=C, Yl=tl, Yp=tp, P=qpos,
                             W2=pw, B2=pb, Y2=out, ldy2=C, flags2=post_flags, y2_offset=l * rows * C,
                             nparts=ksp)
+
+    @staticmethod
+    def _head_part(heads, l):
+        if heads is None:
+            return {}
+        return dict(Wh=heads["Wh"][l], H1=heads["H1"][l], head_cols=heads["head_cols"])
 
     @staticmethod
     def _keep_partials(prec):

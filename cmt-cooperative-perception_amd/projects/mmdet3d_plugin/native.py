@@ -71,7 +71,8 @@ class ChainArgs(ctypes.Structure):
                 ("Wo", _vp), ("W1", _vp), ("W2", _vp), ("Wn", _vp),
                 ("Y", _vp), ("OUT", _vp), ("out_flags", _int), ("Q", _vp), ("WS", _vp),
                 ("OUT16", _vp), ("wo_frag", _int),
-                ("xpart", _vp), ("xsplits", _int), ("xround", _int)]
+                ("xpart", _vp), ("xsplits", _int), ("xround", _int),
+                ("Wh", _vp), ("H1", _vp), ("head_cols", _int)]
 
 
 class LnArgs(ctypes.Structure):
@@ -860,8 +861,22 @@ def pack_chain_fc2_pair(W2p):
     return torch.cat([pack_chain_fc2(h[:, 0].contiguous()), pack_chain_fc2(h[:, 1].contiguous())]).view(torch.uint16)
 
 
+def pack_chain_heads(Wp):
+    """Split-f16 weight of the task heads' first conv for one decoder layer
+    ([head_cols, 2, 256], final_kernel = 1) -> chain B2's head pack
+    (cmt_hip.h cmt_chain_args.Wh): zero rows up to a multiple of 256, then
+    pack_chain_pair."""
+    if Wp.dtype != torch.uint16 or Wp.dim() != 3 or Wp.shape[1:] != (2, 256) or Wp.shape[0] % 64:
+        raise RuntimeError("pack_chain_heads: weight must be split-f16 rows [64 n, 2, 256]")
+    pad = -Wp.shape[0] % 256
+    if pad:
+        Wp = torch.cat([Wp, torch.zeros((pad, 2, 256), dtype=Wp.dtype, device=Wp.device)])
+    return pack_chain_pair(Wp)
+
+
 def chain(kind, X, P, prm, Wo, W1, Y, *, rows, Nq, eps, R=None, W2=None, Wn=None, OUT=None, out_offset=0,
-          out_flags=0, Q=None, WS=None, OUT16=None, xpart=None, xsplits=0, xround=False):
+          out_flags=0, Q=None, WS=None, OUT16=None, xpart=None, xsplits=0, xround=False, Wh=None, H1=None,
+          head_cols=0):
     """One row-block chain of a decoder layer's query side (cmt_chain): kind 0
     after self-attention; kinds 1 then 2 after cross-attention (cmt_hip.h).
     Split-f16 operands (torch.uint16: the 'ref' policy) select the split chains:
@@ -869,9 +884,28 @@ def chain(kind, X, P, prm, Wo, W1, Y, *, rows, Nq, eps, R=None, W2=None, Wn=None
     (pack_chain_pair / pack_chain_fc2_pair; chain B1's W1 is fc1's), chain A's
     Q f16 head-split, chain B2's Q head-split pairs.  xpart (ABI 19, split chain
     B1): the cross-attention workspace a keep_partials attention() left its
-    ``xsplits`` partials in, combined inside the chain (X is then not read)."""
-    _dev(X, P, prm, Wo, W1, Y, R, W2, Wn, OUT, Q, WS, OUT16, xpart)
-    split = any(t is not None and t.dtype == torch.uint16 for t in (X, Wo, W1, W2, Wn, Q, OUT16))
+    ``xsplits`` partials in, combined inside the chain (X is then not read).
+    Wh / H1 / head_cols (split chain B2): the task heads' first conv of this
+    layer (pack_chain_heads of its [head_cols, 2, 256] pair weight) computed by
+    extra workgroups of the chain into fp32 H1 [rows, head_cols] -- what gemm()
+    gives on OUT16, which is then not needed."""
+    if Wh is not None:   # the argument rules of cmt_chain_x3, ahead of any device work
+        if kind != 2:
+            raise RuntimeError("cmt_chain: Wh (head weights) feeds chain B2 (kind 2) only")
+        if out_flags & LN_MAX_INTO:
+            raise RuntimeError("cmt_chain: Wh cannot go with LN_MAX_INTO (the fused maximum is complete only "
+                               "after the last agent)")
+        if head_cols <= 0 or head_cols > 1024 or head_cols % 64:
+            raise RuntimeError("cmt_chain: head_cols must be a multiple of 64 in (0, 1024]")
+        if Wh.dtype != torch.uint16 or Wh.dim() != 1 or Wh.numel() != 2 * (-(-head_cols // 256) * 256) * 256:
+            raise RuntimeError("cmt_chain: Wh must be pack_chain_heads of the [head_cols, 2, 256] pair weight")
+        if (H1 is None or H1.dtype != torch.float32 or not H1.is_contiguous() or H1.numel() != rows * head_cols
+                or H1.data_ptr() % 16):
+            raise RuntimeError("cmt_chain: H1 must be contiguous fp32 [rows, head_cols], 16-byte aligned")
+    elif H1 is not None or head_cols:
+        raise RuntimeError("cmt_chain: H1 / head_cols go with Wh")
+    _dev(X, P, prm, Wo, W1, Y, R, W2, Wn, OUT, Q, WS, OUT16, xpart, Wh, H1)
+    split = any(t is not None and t.dtype == torch.uint16 for t in (X, Wo, W1, W2, Wn, Q, OUT16, Wh))
     pw = 2 if split else 1   # a pair pack holds the hi pack, then the lo pack
     if Wn is not None and (Wn.dim() != 1 or Wn.numel() != pw * 768 * 256):
         raise RuntimeError("cmt_chain: Wn must be fragment-major (pack_chain_wn / pack_chain_pair)")
@@ -928,6 +962,8 @@ def chain(kind, X, P, prm, Wo, W1, Y, *, rows, Nq, eps, R=None, W2=None, Wn=None
         if kind != 1 or not split:
             raise RuntimeError("cmt_chain: xpart feeds the split chain B1 only")
         a.xpart, a.xsplits, a.xround = xpart.data_ptr(), xsplits, int(bool(xround))
+    if Wh is not None:
+        a.Wh, a.H1, a.head_cols = Wh.data_ptr(), H1.data_ptr(), head_cols
     _check(lib().cmt_chain(ctypes.byref(a), _stream()), "cmt_chain")
 
 

@@ -126,6 +126,9 @@ class Options:
     mlp_fused: bool        # CMT_MLP_FUSED=0: split rv_embedding as two GEMMs (hidden pair rows via HBM)
     chain_combine: bool    # CMT_CHAIN_COMBINE=0: split cross-attention combined by its own launch (pair rows
                            # via HBM) instead of inside chain B1
+    chain_heads: bool      # CMT_CHAIN_HEADS=0: the task heads' first conv as its own GEMM over the decoder
+                           # outputs' pair copy instead of inside chain B2 ('ref' chains, one task head,
+                           # final_kernel = 1, no max-fusion over agents; every other case takes the GEMM)
     rv_geo: bool           # CMT_RV_GEO=0: the camera rows' frustum coordinates and layout pass as launches of
                            # their own instead of inside the one-launch RV position MLP
     rv_affine: bool        # CMT_RV_AFFINE=0: the camera rows' rv_embedding[0] as coordinates + fc1 GEMM instead
@@ -151,6 +154,7 @@ def _env_on(name):
 OPTIONS = Options(side_stream=_env_on("CMT_SIDE_STREAM"), chain=_env_on("CMT_CHAIN"),
                   bev_pos_cache=_env_on("CMT_BEV_POS_CACHE"), conv_halo=_env_on("CMT_CONV_HALO"),
                   mlp_fused=_env_on("CMT_MLP_FUSED"), chain_combine=_env_on("CMT_CHAIN_COMBINE"),
+                  chain_heads=_env_on("CMT_CHAIN_HEADS"),
                   rv_geo=_env_on("CMT_RV_GEO"), rv_affine=_env_on("CMT_RV_AFFINE"),
                   train_graph=os.environ.get("CMT_TRAIN_GRAPH", "0") == "1",
                   device_assign=os.environ.get("CMT_DEVICE_ASSIGN", "0") == "1")

@@ -373,6 +373,7 @@ int cmt_gemm_ln(const cmt_gemm_args* gemm, const cmt_ln_args* ln, void* stream);
  *     OUT = post_norm(Y) (+ CMT_LN_NAN_TO_NUM / CMT_LN_MAX_INTO per out_flags)
  *     if Wn: Q = [lowp(Y + P) | lowp(Y + P) | lowp(Y)] Wn^T + bn  (next layer's
  *            self-attn in_proj, head split [B][24][Nq][32])
+ *     if Wh (CMT_F16P only): H1 = pairs(OUT) Wh^T, ceil(head_cols / 256) more workgroups per 32 rows
  * prm: packed fp32 parameter block, layout (floats)
  *   A (1024): bo | norms[0].weight | norms[0].bias | bq
  *   B (3840, the same block for B1 and B2): bo | norms[1].w | norms[1].b | b1 (1024) | b2 |
@@ -413,6 +414,15 @@ typedef struct cmt_chain_args {
      * Each workgroup combines its 32 rows itself (attn_combine_kernel's arithmetic, rounded to f16
      * when xround, as CMT_ATTN_ROUND_OUTPUT does) and X is not read. */
     const float* xpart; int xsplits; int xround;
+    /* B2 with dtype CMT_F16P (optional, NULL = off; additive to ABI 25, cmt_chain_args_size tells a
+     * stale mirror): the task heads' first grouped conv of this layer at final_kernel = 1, a per-row
+     * linear map without bias.  Wh = its pair weight [head_cols][256], zero-padded to a multiple of
+     * 256 rows and packed FRAGMENT-MAJOR like Wn (hi pack, then lo pack); H1 = fp32 [rows][head_cols]
+     * = pairs(OUT) Wh^T, the product cmt_gemm gives on OUT16 with the same weight, bit for bit.
+     * ceil(head_cols / 256) more workgroups per 32 rows compute it; OUT16 is then not needed.
+     * head_cols % 64 == 0, 0 < head_cols <= 1024; not with CMT_LN_MAX_INTO (the fused maximum is
+     * only complete after the last agent). */
+    const void* Wh; float* H1; int head_cols;
 } cmt_chain_args;
 int cmt_chain(const cmt_chain_args* args, void* stream);
 /* bytes of the B1 -> B2 partials workspace WS for `rows` query rows */
