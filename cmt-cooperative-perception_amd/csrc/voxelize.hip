@@ -20,11 +20,15 @@
 //             rows into the zero-padded [max_points, F] block and writes the
 //             fp32 mean of the kept rows (slot order / count -- HardSimpleVFE).
 //
-// Workspace contract: every word starts and ends all-ones ("clean"): the
-// table slots a call dirties are reset by the call itself (dropped voxels in
-// launch 2, kept voxels in launch 3, the look-back words and the ticket in
-// launch 3).  cmt_voxelize_workspace_init fills a new workspace once; after
-// that any number of calls with N <= its capacity reuse it on one stream.
+// Workspace contract: the hash table (tkey, tfirst, thead), the look-back
+// words and the ticket and error words start and end every call all-ones
+// ("clean"): the table slots a call dirties are reset by the call itself
+// (dropped voxels in launch 2, kept voxels in launch 3, the look-back words and
+// the ticket in launch 3).  pslot, pnext and vslot are per-call scratch: each
+// call writes the entries it reads ([0, N) resp. [0, M)) before reading them
+// and leaves them dirty.  cmt_voxelize_workspace_init fills a new workspace
+// once; after that any number of calls with N <= its capacity reuse it on one
+// stream.
 #include "cmt_common.h"
 
 namespace {
@@ -84,8 +88,11 @@ __global__ __launch_bounds__(BIN_PTS) void vox_bin_kernel(const float* __restric
         bool in = true;
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
-            c[j] = (int)floorf((p[j] - g.rmin[j]) / g.vsize[j]);
-            in = in && c[j] >= 0 && c[j] < g.grid[j];
+            // kept iff the fp32 quotient itself is in [0, grid): NaN, +-inf and |v| >= 2^31 are dropped
+            // before the conversion (which would turn NaN into cell 0); same set as 0 <= floor(v) < grid
+            const float v = (p[j] - g.rmin[j]) / g.vsize[j];
+            in = in && v >= 0.f && v < (float)g.grid[j];
+            c[j] = (int)floorf(v);
         }
         if (in) {
             key = (uint32_t)((c[2] * g.grid[1] + c[1]) * g.grid[0] + c[0]);

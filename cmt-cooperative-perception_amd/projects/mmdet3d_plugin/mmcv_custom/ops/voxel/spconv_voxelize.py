@@ -6,7 +6,10 @@ Semantics (deterministic): voxels in first-appearance order of their points,
 the first ``max_num_points`` points of each voxel in input order, at most
 ``max_voxels[0]`` (train) / ``max_voxels[1]`` (eval) voxels, coordinates z, y, x,
 zero-padded point slots -- spconv's CPU point2voxel order (its CUDA hash
-order is nondeterministic).  ``forward_mean`` additionally returns the
+order is nondeterministic).  A point is kept only if the fp32 quotient
+``v = (p - range_min) / voxel_size`` satisfies ``v >= 0 and v < grid`` on all
+three axes, tested before any conversion to int: points with a NaN, +-inf or
+|v| >= 2**31 coordinate are dropped, -0.0 lies in cell 0.  ``forward_mean`` additionally returns the
 HardSimpleVFE mean computed in the same kernel.
 
 The native voxelizer is three launches with no host synchronisation

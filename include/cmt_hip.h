@@ -519,13 +519,18 @@ int cmt_task_head_tail(const float* H1, int L, int B, int Nq, int nheads, int hc
  * HardSimpleVFE.  Deterministic CPU semantics: voxels in first-appearance
  * order of their points, each keeps its first max_points points in input
  * order, at most max_voxels voxels, coordinates z,y,x.
+ * A point is kept only if the fp32 quotient v = (p - range_min) / vsize
+ * satisfies v >= 0 && v < (float)grid on all three axes, tested before any
+ * conversion to int: NaN, +-inf and |v| >= 2^31 are dropped, -0.0 is cell 0.
  * points [N, F] fp32 (F >= nfeat_mean); outputs sized for max_voxels:
  *   voxels [max_voxels, max_points, F] (zero padded), coors [max_voxels, 3],
  *   num_points [max_voxels], means [max_voxels, nfeat_mean],
  *   num_voxels [1] (device int, M; -1 if the in-kernel scan gave up).
  * Three launches, no host synchronisation (graph-capturable).
  * Workspace (ABI 9): cmt_voxelize_workspace_bytes(N, .) bytes, filled once by
- * cmt_voxelize_workspace_init; every call leaves it clean again, so one
+ * cmt_voxelize_workspace_init; every call leaves its hash table, look-back
+ * words and ticket/error words all-ones again (the per-point and per-voxel
+ * scratch arrays are rewritten by each call before it reads them), so one
  * workspace serves any number of calls with N up to its capacity (the
  * largest power of two >= 1024 whose layout fits workspace_bytes), on one
  * stream at a time.

@@ -18,7 +18,12 @@
  * [0, grid) on any axis are dropped, a voxel id is assigned at the first point
  * that falls into a new voxel (first-appearance order) until max_voxels ids
  * exist, each voxel keeps its first max_points points in input order, voxels
- * are zero padded, coordinates are written z, y, x.  The CUDA hash voxelizer
+ * are zero padded, coordinates are written z, y, x.  "Outside" is decided on the
+ * fp32 quotient v = (p - range_min) / vsize itself, before any conversion to
+ * int: a point is kept only if v >= 0 && v < (float)grid on all three axes.
+ * NaN, +-inf and |v| >= 2^31 are therefore dropped without an undefined
+ * float -> int conversion; -0.0 is kept (cell 0).  For every finite v this is
+ * the same set as 0 <= floor(v) < grid.  The CUDA hash voxelizer
  * orders voxels/points by atomics (nondeterministic); this build defines the
  * CPU order as the contract.  Parity unpinned: the reference has no tests or
  * fixtures for this op.
@@ -72,8 +77,8 @@ int cmt_oracle_voxelize(const float* points, int N, int F, const float* voxel_si
         int ok = 1;
         for (int j = 0; j < 3; ++j) {
             float v = (p[j] - coors_range[j]) / voxel_size[j];
+            if (!(v >= 0.f && v < (float)grid[j])) { ok = 0; break; }   /* NaN fails both */
             c[j] = (int)floorf(v);
-            if (c[j] < 0 || c[j] >= grid[j]) { ok = 0; break; }
         }
         if (!ok) continue;
         int64_t key = ((int64_t)c[2] * grid[1] + c[1]) * grid[0] + c[0];
