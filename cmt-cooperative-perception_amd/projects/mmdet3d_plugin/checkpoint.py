@@ -6,6 +6,8 @@
   (``cmt.py`` / ``cmt_coop.py`` build the head as ``self.pts_bbox_head``);
   key names inside the prefix are the reference's, so they
   load unchanged.
+* ``load_detector_checkpoint``: the whole checkpoint into a ``CmtDetector`` /
+  ``CmtCoopDetector`` (``models/detectors``), key for key.
 * ``convert_agent_checkpoint`` / ``merge_coop_checkpoints``: the key rewrite
   of ``tools/model_converters/convert_cmtcoop_checkpoints.py`` that turns
   single-agent CmtDetector checkpoints into one CmtCoopDetector checkpoint:
@@ -22,7 +24,8 @@ import os
 
 import torch
 
-__all__ = ["read_state_dict", "load_head_checkpoint", "convert_agent_checkpoint", "merge_coop_checkpoints",
+__all__ = ["read_state_dict", "load_head_checkpoint", "load_detector_checkpoint", "convert_agent_checkpoint",
+           "merge_coop_checkpoints",
            "AGENTS", "HEAD_PREFIX"]
 
 HEAD_PREFIX = "pts_bbox_head."
@@ -50,6 +53,13 @@ def load_head_checkpoint(head, src, strict=True):
     if any(k.startswith(HEAD_PREFIX) for k in sd):
         sd = {k[len(HEAD_PREFIX):]: v for k, v in sd.items() if k.startswith(HEAD_PREFIX)}
     return head.load_state_dict(sd, strict=strict)
+
+
+def load_detector_checkpoint(model, src, strict=True):
+    """Load a whole detector checkpoint (mmcv-wrapped or a bare state dict, a path or a dict) into a
+    CmtDetector / CmtCoopDetector, whose keys are the reference's.  The output of ``merge_coop_checkpoints``
+    loads as it is: SparseConv takes its kernels in either layout.  Returns torch's (missing, unexpected)."""
+    return model.load_state_dict(read_state_dict(src), strict=strict)
 
 
 def convert_agent_checkpoint(sd, agent, prefix=None, wo_trans=False):

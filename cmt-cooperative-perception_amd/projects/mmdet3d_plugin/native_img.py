@@ -5,6 +5,7 @@ host.  The packing reuses native_bev's float64 BN fold and f16 hi / lo split.
 """
 import ctypes
 
+import numpy as np
 import torch
 
 from . import native as N
@@ -13,11 +14,114 @@ from .native_bev import _flag, _pair_rows, _shift, fold_bn, out_hw, split_pair
 from .native_fpn import pack_conv1x1
 
 __all__ = ["STEM_K", "CONCAT_TM", "MAX_SRC", "pack_stem", "pack_concat", "pool_hw", "concat_tiles", "stem", "conv3x3",
-           "conv3x3_gemm", "concat1x1", "ese_gate", "ese_apply", "maxpool"]
+           "conv3x3_gemm", "concat1x1", "ese_gate", "ese_apply", "maxpool", "IMG_MEAN", "IMG_STD", "norm_constants",
+           "test_crop", "crop_lidar2img", "prepare_images"]
 
 STEM_K = 32        # the stem's K = 9 Cin <= 27, zero-padded (cmt_hip.h)
 CONCAT_TM = 128    # pixels per tile of cmt_img_concat1x1 (cmt_img_concat_tile_rows())
 MAX_SRC = N.IMG_MAX_SRC
+
+
+# img_norm_cfg of the reference's VoVNet configs (BGR order as cv2 loads, to_rgb=False)
+IMG_MEAN = (103.530, 116.280, 123.675)
+IMG_STD = (57.375, 57.120, 58.395)
+
+
+def norm_constants(mean, std):
+    """(mean32, inv32) as the pipeline holds them: mean32 = float32(mean), inv32 = float32(1 / float64(float32(std)))
+    (mmcv's imnormalize_ subtracts the float32 mean and multiplies by the reciprocal of the float32 std)"""
+    mean32 = np.asarray(mean, dtype=np.float32).reshape(-1)
+    std32 = np.asarray(std, dtype=np.float32).reshape(-1)
+    if mean32.shape != (3,) or std32.shape != (3,):
+        raise ValueError("mean and std must have 3 entries")
+    if not (np.all(np.isfinite(mean32)) and np.all(np.isfinite(std32)) and np.all(std32 != 0)):
+        raise ValueError("mean must be finite and std finite and non-zero")
+    return mean32, (1.0 / std32.astype(np.float64)).astype(np.float32)
+
+
+def test_crop(src_hw, final_dim, bot_pct_lim=(0.0, 0.0)):
+    """The test branch of ResizeCropFlipImage._sample_augmentation (transform_3d.py:446-455) for a source of
+    ``src_hw = (H, W)`` and ``final_dim = (fH, fW)`` -> (resize, crop) with crop = (x0, y0, x1, y1) in source
+    pixels.  Only resize == 1 (a pure integer crop) is built: anything else needs interpolation."""
+    H, W = (int(v) for v in src_hw)
+    fH, fW = (int(v) for v in final_dim)
+    if min(H, W, fH, fW) <= 0:
+        raise ValueError(f"positive sizes required, got src_hw {tuple(src_hw)}, final_dim {tuple(final_dim)}")
+    resize = max(fH / H, fW / W)
+    if resize != 1.0:
+        raise NotImplementedError(f"test_crop: {(H, W)} -> {(fH, fW)} needs a resize by {resize:.6g}; only the "
+                                  "integer crop (resize 1) has a native path, interpolation is not built")
+    new_w, new_h = int(W * resize), int(H * resize)
+    crop_h = int((1 - float(np.mean(bot_pct_lim))) * new_h) - fH
+    crop_w = int(max(0, new_w - fW) / 2)
+    return resize, (crop_w, crop_h, crop_w + fW, crop_h + fH)
+
+
+test_crop.__test__ = False   # a host helper, not a test, whatever collects names starting with test_
+
+
+def crop_lidar2img(cam_intrinsic, lidar2cam, crop):
+    """lidar2img of the cropped image, in float64: the intrinsic's principal point moves by (-x0, -y0)
+    (transform_3d.py:373-378 and 420-431 with resize 1, no flip, no rotation), then intrinsic @ lidar2cam.
+    ``cam_intrinsic`` is 3 x 3 or 4 x 4, ``lidar2cam`` 4 x 4; the inputs are not modified."""
+    K = np.array(cam_intrinsic, dtype=np.float64)
+    E = np.array(lidar2cam, dtype=np.float64)
+    if K.shape == (3, 3):
+        K4 = np.eye(4)
+        K4[:3, :3] = K
+        K = K4
+    if K.shape != (4, 4) or E.shape != (4, 4):
+        raise ValueError(f"cam_intrinsic must be 3 x 3 or 4 x 4 and lidar2cam 4 x 4, got {K.shape} and {E.shape}")
+    K[0, 2] -= float(crop[0])
+    K[1, 2] -= float(crop[1])
+    return K @ E
+
+
+def prepare_images(frames, crop=None, mean=IMG_MEAN, std=IMG_STD, to_rgb=False, size_divisor=32, out=None, size=None):
+    """cmt_img_prepare: uint8 frames [N, Hs, Ws, 3] (interleaved, as cv2 loads them) -> the backbone's input fp32
+    [N, 3, Hp, Wp]: crop, normalise, zero-pad, HWC -> CHW in one kernel.  ``crop`` = (x0, y0, x1, y1) in source
+    pixels as test_crop returns it (None: the whole frame); crop pixels outside the source count as byte 0
+    before normalisation.  (Hp, Wp) is the crop size rounded up to ``size_divisor``, or the explicit
+    ``size = (Hp, Wp)``; the pad is 0 after normalisation.  ``mean`` / ``std`` are indexed by output channel,
+    which reads source channel 2 - c when ``to_rgb``."""
+    if not torch.is_tensor(frames) or frames.dtype != torch.uint8:
+        raise ValueError(f"frames must be a uint8 tensor, got {frames.dtype if torch.is_tensor(frames) else type(frames)}")
+    if frames.dim() != 4 or frames.shape[3] != 3 or min(frames.shape) <= 0:
+        raise ValueError(f"frames must be a non-empty [N, H, W, 3] tensor, got {tuple(frames.shape)}")
+    if not frames.is_contiguous():
+        raise ValueError("frames must be contiguous (interleaved HWC rows)")
+    if not frames.is_cuda:
+        raise ValueError("frames must live on a HIP device (no CPU path)")
+    n, Hs, Ws = (int(s) for s in frames.shape[:3])
+    x0, y0, x1, y1 = (0, 0, Ws, Hs) if crop is None else (int(v) for v in crop)
+    w, h = x1 - x0, y1 - y0
+    if w <= 0 or h <= 0:
+        raise ValueError(f"empty crop {(x0, y0, x1, y1)}")
+    if size is not None:
+        Hp, Wp = (int(v) for v in size)
+        if Hp < h or Wp < w:
+            raise ValueError(f"size {(Hp, Wp)} below the crop's {(h, w)}")
+    else:
+        d = int(size_divisor)
+        if d <= 0:
+            raise ValueError(f"size_divisor must be positive, got {size_divisor}")
+        Hp, Wp = (h + d - 1) // d * d, (w + d - 1) // d * d
+    if max(abs(x0), abs(y0), Hp, Wp) >= 2 ** 30 or n * Hp * ((Wp + 3) // 4) >= 2 ** 31:
+        raise ValueError("crop or output size beyond the kernel's index range")
+    mean32, inv32 = norm_constants(mean, std)
+    if out is not None:
+        _f32("out", out, (n, 3, Hp, Wp))
+        if out.device != frames.device:
+            raise ValueError("out must live on the frames' device")
+    Y = out if out is not None else torch.empty((n, 3, Hp, Wp), dtype=torch.float32, device=frames.device)
+    a = N.ImgPrepareArgs()
+    a.N, a.Hs, a.Ws, a.to_rgb = n, Hs, Ws, int(bool(to_rgb))
+    a.x0, a.y0, a.w, a.h, a.Hp, a.Wp = x0, y0, w, h, Hp, Wp
+    for c in range(3):
+        a.mean[c], a.inv_std[c] = float(mean32[c]), float(inv32[c])
+    a.src, a.dst = _p(frames), _p(Y)
+    _check(lib().cmt_img_prepare(ctypes.byref(a), _stream()), "cmt_img_prepare")
+    return Y
 
 
 def pack_stem(w, bn):

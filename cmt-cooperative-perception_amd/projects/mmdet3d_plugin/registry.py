@@ -16,7 +16,8 @@ import inspect
 __all__ = ["Registry", "build_from_cfg", "HEADS", "TRANSFORMER", "ATTENTION", "TRANSFORMER_LAYER",
            "TRANSFORMER_LAYER_SEQUENCE", "FEEDFORWARD_NETWORK", "BBOX_CODERS", "VOXEL_LAYERS",
            "NORM_LAYERS", "MIDDLE_ENCODERS", "BACKBONES", "NECKS", "build_head", "build_transformer",
-           "build_bbox_coder", "build_middle_encoder", "build_backbone", "build_neck"]
+           "build_bbox_coder", "build_middle_encoder", "build_backbone", "build_neck", "DETECTORS", "VOXEL_ENCODERS",
+           "build_voxel_encoder", "build_detector", "build_model"]
 
 
 class Registry:
@@ -86,6 +87,8 @@ NORM_LAYERS = Registry("norm layer", parent=MODELS)
 MIDDLE_ENCODERS = Registry("middle_encoder", parent=MODELS)
 BACKBONES = Registry("backbone", parent=MODELS)
 NECKS = Registry("neck", parent=MODELS)
+VOXEL_ENCODERS = Registry("voxel_encoder", parent=MODELS)
+DETECTORS = Registry("detector", parent=MODELS)
 BBOX_CODERS = Registry("bbox_coder")
 VOXEL_LAYERS = Registry("voxel_layer")
 
@@ -112,3 +115,19 @@ def build_backbone(cfg, **kw):
 
 def build_neck(cfg, **kw):
     return build_from_cfg(cfg, NECKS, kw or None)
+
+
+def build_voxel_encoder(cfg, **kw):
+    return build_from_cfg(cfg, VOXEL_ENCODERS, kw or None)
+
+
+def build_detector(cfg, train_cfg=None, test_cfg=None):
+    """mmdet3d's build_detector / build_model: train_cfg / test_cfg go either in the model dict or here"""
+    if (train_cfg is not None and cfg.get("train_cfg") is not None) or \
+            (test_cfg is not None and cfg.get("test_cfg") is not None):
+        raise ValueError("train_cfg / test_cfg given both in the model dict and as an argument")
+    extra = {k: v for k, v in (("train_cfg", train_cfg), ("test_cfg", test_cfg)) if v is not None}
+    return build_from_cfg(cfg, DETECTORS, extra or None)
+
+
+build_model = build_detector   # cmt_coop.py:46-49 builds its agents with builder.build_model

@@ -23,7 +23,8 @@ from .config import load_config
 from .registry import build_head
 
 __all__ = ["CONFIG_DIR", "make_head_cfg", "build_synthetic_head", "camera_lidar2img", "synthetic_metas",
-           "synthetic_bev", "synthetic_img", "synthetic_points", "head_state_dict", "CONFIGS"]
+           "synthetic_bev", "synthetic_img", "synthetic_points", "head_state_dict", "CONFIGS", "make_detector_cfg",
+           "synthetic_frames"]
 
 CONFIG_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "configs")
 CONFIGS = ("cmt_lidar_nus", "cmt_fusion_nus", "cmtcoop_fusion_tumtraf", "cmtcoop_lidar_tumtraf")
@@ -59,6 +60,64 @@ def make_head_cfg(name, num_query=900, num_layers=None, grid_size=None, head_typ
                       nms_type=None, max_num=200),
     )
     return head, c
+
+
+def make_detector_cfg(name, num_query=900, num_layers=None, grid_size=None, spec_name="V-99-eSE"):
+    """The whole ``model`` dict of a package config: the head of ``make_head_cfg`` under the feature-extractor
+    blocks of the reference configs (e.g. CMT_Nuscenes/fusion/cmt_voxel0075_vov_1600x640_cbgs.py:160-200,
+    CMTCoop_TUMTraf/fusion/coop/...py:216-273).  ``grid_size=[X, Y, 40]`` shrinks the scene around the origin
+    at the config's voxel size: x, y in +-X vx / 2, +-Y vy / 2, ``sparse_shape = [41, Y, X]``; the voxel layer,
+    the middle encoder, the head's ``pc_range`` and ``test_cfg`` then agree.  ``spec_name``: the VoVNet spec.
+    One key is not the reference's: the SparseEncoder gets ``capacity_factor=8``, the worst case, because
+    ``synthetic_points`` are uniform and isolated, so the strided stages grow the active set where a LiDAR
+    sweep shrinks it; the factor sizes buffers only and changes no value."""
+    head, c = make_head_cfg(name, num_query=num_query, num_layers=num_layers, grid_size=grid_size)
+    vx, vy, _ = c["voxel_size"]
+    pcr = list(c["point_cloud_range"])
+    grid = list(c["grid_size"])
+    if grid_size is not None:
+        grid = [int(g) for g in grid_size]
+        if len(grid) != 3 or grid[2] != c["grid_size"][2]:
+            raise ValueError(f"grid_size must be [X, Y, {c['grid_size'][2]}], got {list(grid_size)}")
+        pcr = [-grid[0] * vx / 2, -grid[1] * vy / 2, pcr[2], grid[0] * vx / 2, grid[1] * vy / 2, pcr[5]]
+    head["bbox_coder"]["pc_range"] = pcr
+    test_cfg = head.pop("test_cfg")
+    test_cfg.update(grid_size=grid, pc_range=pcr)
+    head.pop("train_cfg")
+    fusion = "fusion" in name
+    body = dict(type="CmtDetector", use_grid_mask=True)
+    if fusion:
+        body.update(
+            img_backbone=dict(type="VoVNet", spec_name=spec_name, norm_eval=True, frozen_stages=-1, input_ch=3,
+                              out_features=("stage4", "stage5")),
+            img_neck=dict(type="CPFPN", in_channels=[768, 1024], out_channels=256, num_outs=2))
+    voxel_layer = dict(c["pts_voxel_layer"], point_cloud_range=pcr)
+    body.update(
+        pts_voxel_layer=voxel_layer,
+        pts_voxel_encoder=dict(type="HardSimpleVFE", num_features=5),
+        pts_middle_encoder=dict(type="SparseEncoder", in_channels=5, sparse_shape=[grid[2] + 1, grid[1], grid[0]],
+                                output_channels=128, order=("conv", "norm", "act"),
+                                encoder_channels=((16, 16, 32), (32, 32, 64), (64, 64, 128), (128, 128)),
+                                encoder_paddings=((0, 0, 1), (0, 0, 1), (0, 0, [0, 1, 1]), (0, 0)),
+                                block_type="basicblock", capacity_factor=8.0),
+        pts_backbone=dict(type="SECOND", in_channels=256, out_channels=[128, 256], layer_nums=[5, 5],
+                          layer_strides=[1, 2], norm_cfg=dict(type="BN", eps=0.001, momentum=0.01),
+                          conv_cfg=dict(type="Conv2d", bias=False)),
+        pts_neck=dict(type="SECONDFPN", in_channels=[128, 256], out_channels=[256, 256], upsample_strides=[1, 2],
+                      norm_cfg=dict(type="BN", eps=0.001, momentum=0.01),
+                      upsample_cfg=dict(type="deconv", bias=False), use_conv_for_no_stride=True))
+    tail = dict(pts_bbox_head=head, train_cfg=None, test_cfg=dict(pts=test_cfg))
+    if name.startswith("cmtcoop"):
+        return dict(type="CmtCoopDetector", vehicle_model=body, infrastructure_model=copy.deepcopy(body),
+                    coop_fusion_neck=None, **tail)
+    return dict(body, **tail)
+
+
+def synthetic_frames(n, h=900, w=1600, seed=0, device=None):
+    """camera frames as cv2 loads them: uint8 [n, h, w, 3], interleaved"""
+    g = torch.Generator().manual_seed(seed + 17)
+    x = torch.randint(0, 256, (n, h, w, 3), generator=g, dtype=torch.uint8)
+    return x.to(device) if device is not None else x
 
 
 def _jitter_(module, gen, scale=0.05):

@@ -21,6 +21,12 @@ the same "at least one of --out / --eval / --format-only" check and the same
   i % world) and rank 0 gathers the results (all_gather_object), as
   multi_gpu_test's result collection.
 
+``--detector`` runs the whole model instead of the head alone: synthetic points and synthetic uint8 camera
+frames (``--frame-size H W``, 900 x 1600 by default) go through ``build_detector(make_detector_cfg(...))``:
+``prepare_images`` with the crop of ``test_crop`` (the config's final_dim scaled to the frame width),
+``lidar2img`` from ``crop_lidar2img``, ``pad_shape`` in the metas, and a CHECKPOINT is read by
+``load_detector_checkpoint`` (every branch, not only ``pts_bbox_head.*``).
+
 Config 1 of BASELINE.json: ``python cmt-cooperative-perception_amd/tools/test.py
 cmt_lidar_nus --synthetic --num-query 32 --num-layers 1 --points 1000 --eval bbox``.
 The head runs on a HIP device only -- there is no CPU path; without a GPU the
@@ -55,6 +61,11 @@ def parse_args(argv=None):
     p.add_argument("--num-layers", type=int, default=None, help="override the decoder depth (config 1: 1)")
     p.add_argument("--grid", type=int, nargs=2, default=None, metavar=("H", "W"),
                    help="BEV feature map size (default 180 180)")
+    p.add_argument("--detector", action="store_true",
+                   help="run CmtDetector / CmtCoopDetector on raw points and uint8 camera frames, not the head on "
+                        "synthetic feature maps")
+    p.add_argument("--frame-size", type=int, nargs=2, default=(900, 1600), metavar=("H", "W"),
+                   help="camera frame size as loaded, for --detector (default 900 1600)")
     p.add_argument("--points", type=int, default=1000, help="synthetic points per frame and agent")
     p.add_argument("--precision", default="bf16", choices=["bf16", "fp16", "ref"], help="compute policy")
     p.add_argument("--bbox-classes", nargs="+", type=int, default=None, help="keep these labels (OpenLABEL)")
@@ -147,6 +158,60 @@ def frame_inputs(name, meta, frame, args, device):
     return feats, metas, points
 
 
+def build_detector_model(args, name, device):
+    from projects.mmdet3d_plugin import synthetic as S
+    from projects.mmdet3d_plugin.registry import build_detector
+    from projects.mmdet3d_plugin.checkpoint import load_detector_checkpoint
+    import torch
+    nq = args.num_query if args.num_query is not None else 900
+    grid = [8 * args.grid[1], 8 * args.grid[0], 40] if args.grid else None
+    cfg = S.make_detector_cfg(name, num_query=nq, num_layers=args.num_layers, grid_size=grid)
+    apply_cfg_options(cfg["pts_bbox_head"], args.cfg_options)
+    torch.manual_seed(args.seed)
+    model = build_detector(cfg)
+    model.init_weights()
+    if args.checkpoint:
+        load_detector_checkpoint(model, args.checkpoint)
+    model.eval().to(device)
+    return model, cfg
+
+
+def detector_frame_inputs(name, cfg, meta, frame, args, device):
+    """One synthetic frame for the detector -> (forward_test keyword arguments, per-agent point clouds)."""
+    import numpy as np
+    from projects.mmdet3d_plugin import native_img as NI
+    from projects.mmdet3d_plugin import synthetic as S
+    seed = args.seed + 1000 * frame
+    coop = name.startswith("cmtcoop")
+    fusion = "fusion" in name
+    body = cfg["vehicle_model"] if coop else cfg
+    pcr = body["pts_voxel_layer"]["point_cloud_range"]
+    Hf, Wf = args.frame_size
+    fH, fW = meta.get("final_dim", (640, 1600))
+    final_dim = (int(round(fH * Wf / fW)), Wf)   # the config's final_dim at this frame width
+    if coop:
+        agents = [("vehicle_", S.VEHICLE_YAWS), ("infrastructure_", S.INFRA_YAWS)]
+    else:
+        agents = [("", S.NUS_YAWS)]
+    metas, kw, points = dict(), dict(), []
+    for i, (prefix, yaws) in enumerate(agents):
+        pts = S.synthetic_points(args.points, pcr, seed=seed + 10 * i, device=device)
+        points.append(pts)
+        kw[prefix + "points"] = [[pts]]
+        if not fusion:
+            continue
+        _, crop = NI.test_crop((Hf, Wf), final_dim)
+        frames = S.synthetic_frames(len(yaws), Hf, Wf, seed=seed + 2 + 10 * i, device=device)
+        img = NI.prepare_images(frames, crop=crop)
+        K = np.array([[1266.0 * Wf / 1600.0, 0.0, Wf / 2.0], [0.0, 1266.0 * Wf / 1600.0, Hf / 2.0], [0.0, 0.0, 1.0]])
+        metas[prefix + "lidar2img"] = [NI.crop_lidar2img(K, S.camera_lidar2img(y, f=1.0, cx=0.0, cy=0.0), crop)
+                                       for y in yaws]
+        metas[prefix + "pad_shape"] = [tuple(img.shape[2:]) + (3,)] * len(yaws)
+        kw[prefix + "img"] = [img[None]]
+    kw["img_metas"] = [[metas]]
+    return kw, points
+
+
 def run_frame(head, name, feats, metas):
     if name.startswith("cmtcoop"):
         (xv, iv), (xi_, ii) = feats
@@ -191,8 +256,15 @@ def _run(args, name, device, rank, world, distributed):
     from projects.mmdet3d_plugin.mmcv_custom.ops.voxel import SPConvVoxelization
     from projects.mmdet3d_plugin.mmcv_custom.ops.voxel.spconv_voxelize import voxelize_batch
 
-    head, cfg, meta = build_head(args, name, device)
-    vcfg = dict(meta["pts_voxel_layer"])
+    if args.detector:
+        from projects.mmdet3d_plugin import synthetic as S
+        model, dcfg = build_detector_model(args, name, device)
+        meta = S.make_head_cfg(name)[1]
+        cfg = dcfg["pts_bbox_head"]
+        vcfg = dict((dcfg["vehicle_model"] if name.startswith("cmtcoop") else dcfg)["pts_voxel_layer"])
+    else:
+        head, cfg, meta = build_head(args, name, device)
+        vcfg = dict(meta["pts_voxel_layer"])
     vox = SPConvVoxelization(voxel_size=vcfg["voxel_size"], point_cloud_range=vcfg["point_cloud_range"],
                              max_num_points=vcfg["max_num_points"], max_voxels=vcfg["max_voxels"],
                              num_point_features=vcfg["num_point_features"]).eval()
@@ -201,13 +273,20 @@ def _run(args, name, device, rank, world, distributed):
     t0 = time.perf_counter()
     with torch.no_grad():
         for f in range(rank, args.frames, world):
-            feats, metas, points = frame_inputs(name, meta, f, args, device)
+            if args.detector:
+                kw, points = detector_frame_inputs(name, dcfg, meta, f, args, device)
+            else:
+                feats, metas, points = frame_inputs(name, meta, f, args, device)
             # the voxel layer of the detector (cmt.py:88-113 + HardSimpleVFE), per agent
             vox_stats = []
             for pts in points:
                 mean, nums, coors = voxelize_batch(vox, [pts], num_features=vcfg["num_point_features"])
                 vox_stats.append(dict(voxels=int(mean.shape[0]), points_kept=int(nums.sum().item())))
-            boxes, scores, labels = run_frame(head, name, feats, metas)
+            if args.detector:
+                res = model(return_loss=False, **kw)[0]["pts_bbox"]
+                boxes, scores, labels = res["boxes_3d"], res["scores_3d"], res["labels_3d"]
+            else:
+                boxes, scores, labels = run_frame(head, name, feats, metas)
             results.append(dict(frame=f, voxels=vox_stats,
                                 boxes_3d=boxes.float().cpu().tolist(), scores_3d=scores.float().cpu().tolist(),
                                 labels_3d=labels.cpu().tolist(),

@@ -1,0 +1,224 @@
+"""Per-stage times of the whole detector at full size: uint8 camera frames and raw points to boxes.
+
+Two frames, each through ``build_detector(make_detector_cfg(...))`` with VoVNet V-99-eSE:
+  * fusion (cmt_fusion_nus): 6 frames 900 x 1600 and one cloud of --points points;
+  * coop (cmtcoop_fusion_tumtraf): 1 vehicle + 3 infrastructure frames 900 x 1600, one cloud per agent.
+Stages: prepare (cmt_img_prepare), image backbone, image neck, voxelize (+ fused mean), middle encoder, BEV
+backbone + neck, head + decode (boxes copied to the host).  One pass fills every stage's inputs; then each stage
+is timed alone on those inputs with device events around one call: the median of --repeats calls after --warmup,
+with min .. max.  A stage's host reads (the voxel count, the sparse encoder's row counts) are inside its time.
+For the coop frame a stage's time is the sum over the two agents.  The end-to-end frame time is a host clock
+around prepare + ``simple_test`` ending in a device synchronise.
+
+cmt_img_prepare is also timed against the same operation written with torch ops on the device (slice, permute,
+float, sub, mul, F.pad), in alternating windows of --iters calls, and its bytes per second over the bytes it
+must move (source crop once, destination once).
+
+    python dev/detector_probe.py [--points 300000] [--repeats 20] [--warmup 3] [--iters 20] [--seed 0] [--out FILE]
+
+Needs a HIP device and the built library; there is no CPU path.
+"""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+import torch
+import torch.nn.functional as F
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (os.path.join(ROOT, "cmt-cooperative-perception_amd"), ROOT):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+STAGES = ("prepare", "image backbone", "image neck", "voxelize", "middle encoder", "BEV backbone + neck",
+          "head + decode")
+FRAME = (900, 1600)
+
+
+def event_ms(fn):
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0.record()
+    fn()
+    t1.record()
+    torch.cuda.synchronize()
+    return t0.elapsed_time(t1)
+
+
+def med(ts):
+    return statistics.median(ts), min(ts), max(ts)
+
+
+def fmt(t):
+    return f"{t[0]:9.3f} ({t[1]:.3f} .. {t[2]:.3f})"
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--points", type=int, default=300000)
+    ap.add_argument("--repeats", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("detector_probe needs a HIP device (timings are never taken on the CPU)")
+    from projects.mmdet3d_plugin import build_detector
+    from projects.mmdet3d_plugin import native_img as NI
+    from projects.mmdet3d_plugin import synthetic as S
+    from projects.mmdet3d_plugin.models.detectors import bbox3d2result
+    dev = torch.device("cuda:0")
+    lines = []
+
+    def say(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    say(f"device {torch.cuda.get_device_name(0)}; seed {args.seed}; frames {FRAME[0]} x {FRAME[1]} uint8, "
+        f"{args.points} points per cloud; per stage: median of {args.repeats} single calls after {args.warmup} "
+        "warm-up (min .. max), device events, ms")
+    _, crop = NI.test_crop(FRAME, (640, 1600))
+
+    def build(name):
+        torch.manual_seed(args.seed)
+        model = build_detector(S.make_detector_cfg(name))
+        model.init_weights()
+        S._jitter_(model, torch.Generator().manual_seed(args.seed + 1))
+        return model.eval().to(dev)
+
+    def frame(name):
+        model = build(name)
+        coop = name.startswith("cmtcoop")
+        if coop:
+            agents = [("vehicle_", model.vehicle_model, S.VEHICLE_YAWS), ("infrastructure_", model.infrastructure_model,
+                                                                          S.INFRA_YAWS)]
+        else:
+            agents = [("", model, S.NUS_YAWS)]
+        head = model.pts_bbox_head
+        meta = dict()
+        inputs = []
+        for i, (prefix, det, yaws) in enumerate(agents):
+            pcr = det.pts_voxel_layer.point_cloud_range.tolist()
+            inputs.append((S.synthetic_frames(len(yaws), *FRAME, seed=args.seed + i, device=dev),
+                           [S.synthetic_points(args.points, pcr, seed=args.seed + 10 + i, device=dev)]))
+            meta.update(S.synthetic_metas(1, yaws=yaws, prefix=prefix, seed=args.seed + 20 + i)[0])
+        metas = [meta]
+        st = [dict() for _ in agents]
+
+        def prepare(i):
+            st[i]["img"] = NI.prepare_images(inputs[i][0], crop=crop)
+
+        def backbone(i):
+            st[i]["bb"] = list(agents[i][1].img_backbone(st[i]["img"]).values())
+
+        def neck(i):
+            st[i]["imf"] = agents[i][1].img_neck(st[i]["bb"])
+
+        def voxelize(i):
+            st[i]["vox"] = agents[i][1].voxelize(inputs[i][1])
+
+        def middle(i):
+            feats, _, coors = st[i]["vox"]
+            st[i]["mid"] = agents[i][1].pts_middle_encoder(feats, coors, 1)
+
+        def bev(i):
+            st[i]["bev"] = agents[i][1].pts_neck(agents[i][1].pts_backbone(st[i]["mid"]))
+
+        def head_decode(_=None):
+            if coop:
+                outs = head(st[0]["bev"], st[1]["bev"], st[0]["imf"], st[1]["imf"], metas)
+            else:
+                outs = head(st[0]["bev"], st[0]["imf"], metas)
+            st[0]["res"] = [bbox3d2result(b, s, l) for b, s, l in head.get_bboxes(outs, metas)]
+
+        per_agent = [prepare, backbone, neck, voxelize, middle, bev]
+
+        def end_to_end():
+            imgs = [NI.prepare_images(inputs[i][0], crop=crop)[None] for i in range(len(agents))]
+            if coop:
+                return model.simple_test(inputs[0][1], inputs[1][1], metas, vehicle_img=imgs[0],
+                                         infrastructure_img=imgs[1])
+            return model.simple_test(inputs[0][1], metas, img=imgs[0])
+
+        with torch.no_grad():
+            for fn in per_agent:
+                for i in range(len(agents)):
+                    fn(i)
+            head_decode()
+            torch.cuda.synchronize()
+            model.check_input_range()
+            vox = [int(s["vox"][0].shape[0]) for s in st]
+            say(f"--- {name}: {type(model).__name__}, cameras {[len(a[2]) for a in agents]}, voxels {vox}, "
+                f"boxes {int(st[0]['res'][0]['scores_3d'].shape[0])}")
+            total = 0.0
+            for label, fn in zip(STAGES, per_agent + [head_decode]):
+                n = 1 if fn is head_decode else len(agents)
+                for _ in range(args.warmup):
+                    for i in range(n):
+                        fn(i)
+                torch.cuda.synchronize()
+                ts = [sum(event_ms(lambda i=i: fn(i)) for i in range(n)) for _ in range(args.repeats)]
+                t = med(ts)
+                total += t[0]
+                say(f"{label:>22} {fmt(t)}")
+            say(f"{'sum of the medians':>22} {total:9.3f}")
+            for _ in range(args.warmup):
+                end_to_end()
+            torch.cuda.synchronize()
+            ts = []
+            for _ in range(args.repeats):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                res = end_to_end()
+                torch.cuda.synchronize()
+                ts.append((time.perf_counter() - t0) * 1e3)
+            assert torch.equal(res[0]["pts_bbox"]["scores_3d"], st[0]["res"][0]["scores_3d"])
+            say(f"{'end to end, host clock':>22} {fmt(med(ts))}   (uint8 frames + points -> boxes on the host; equals "
+                "the staged pass bit for bit)")
+            model.check_input_range()
+        return inputs[0][0]
+
+    frames = frame("cmt_fusion_nus")
+    frame("cmtcoop_fusion_tumtraf")
+
+    # cmt_img_prepare against the torch chain, at the fusion frame
+    mean32, inv32 = NI.norm_constants(NI.IMG_MEAN, NI.IMG_STD)
+    mean_t = torch.from_numpy(mean32).to(dev).view(1, 3, 1, 1)
+    inv_t = torch.from_numpy(inv32).to(dev).view(1, 3, 1, 1)
+    x0, y0, x1, y1 = crop
+    out = torch.empty((frames.shape[0], 3, 640, 1600), dtype=torch.float32, device=dev)
+
+    def native_fn():
+        NI.prepare_images(frames, crop=crop, out=out)
+
+    def torch_fn():
+        x = frames[:, y0:y1, x0:x1].permute(0, 3, 1, 2).float()
+        return F.pad(((x - mean_t) * inv_t).contiguous(), (0, 0, 0, 0))
+
+    same = torch.equal(torch_fn(), NI.prepare_images(frames, crop=crop))
+    for fn in (native_fn, torch_fn):
+        for _ in range(args.warmup):
+            fn()
+    torch.cuda.synchronize()
+    tn, tt = [], []
+    for _ in range(args.repeats):
+        tn.append(event_ms(lambda: [native_fn() for _ in range(args.iters)]) / args.iters)
+        tt.append(event_ms(lambda: [torch_fn() for _ in range(args.iters)]) / args.iters)
+    tn, tt = med(tn), med(tt)
+    nbytes = frames.shape[0] * 640 * 1600 * 3 * (1 + 4)
+    say(f"--- cmt_img_prepare [6, 900, 1600, 3] -> [6, 3, 640, 1600]: alternating windows of {args.iters} calls, "
+        f"median of {args.repeats} (min .. max), ms per call; the torch chain's result is "
+        f"{'bit-equal' if same else 'NOT bit-equal'}")
+    say(f"{'cmt_img_prepare':>22} {fmt(tn)}   {nbytes * 1e-6:.1f} MB moved -> {nbytes / (tn[0] * 1e-3) * 1e-12:.2f} TB/s")
+    say(f"{'torch ops':>22} {fmt(tt)}   native / torch {tn[0] / tt[0]:.2f}")
+    say(f"peak device memory {torch.cuda.max_memory_allocated() / 2 ** 20:.0f} MiB")
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -1109,6 +1109,29 @@ int cmt_img_ese_gate(const cmt_img_gate_args* args, void* stream);
 int cmt_img_ese_apply(const cmt_img_apply_args* args, void* stream);
 int cmt_img_maxpool(const cmt_img_pool_args* args, void* stream);
 
+/* ---- camera frames -> the image backbone's input (imgprep.hip; additive to ABI 25) ----------------
+ * cmt_img_prepare: the test-time image pipeline of the reference (integer crop of
+ * ResizeCropFlipImage at resize 1, NormalizeMultiviewImage, PadMultiViewImage) in one pass.
+ *   src: uint8 [N][Hs][Ws][3], contiguous and interleaved (any byte alignment).
+ *   dst: fp32 [N][3][Hp][Wp], contiguous, 4-byte aligned (16-byte stores when Wp % 4 == 0 and
+ *   dst is 16-byte aligned, scalar stores otherwise); every element is written.
+ *   For y < h and x < w, with b the byte of source pixel (y0 + y, x0 + x), channel
+ *   (to_rgb ? 2 - c : c), or 0 where that pixel lies outside the source:
+ *     dst[n][c][y][x] = fl32(fl32((float)b - mean[c]) * inv_std[c]);
+ *   dst[n][c][y][x] = 0 for y >= h or x >= w.  inv_std is the caller's float32 reciprocal of std.
+ *   Requirements: N, Hs, Ws, w, h > 0, Hp >= h, Wp >= w, |x0|, |y0|, Hp, Wp < 2^30,
+ *   N * Hp * ceil(Wp / 4) < 2^31 (element offsets are 64-bit); CMT_EINVAL otherwise. */
+typedef struct cmt_img_prepare_args {
+    int N, Hs, Ws, to_rgb;
+    int x0, y0, w, h;                             /* crop window in source pixels */
+    int Hp, Wp;
+    float mean[3], inv_std[3];                    /* by destination channel */
+    const void* src;
+    void* dst;
+} cmt_img_prepare_args;
+int64_t cmt_img_prepare_args_size(void);
+int cmt_img_prepare(const cmt_img_prepare_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
