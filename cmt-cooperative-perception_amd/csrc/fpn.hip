@@ -232,6 +232,48 @@ __global__ __launch_bounds__(256) void rows_to_nchw_kernel(cmt_rows_to_nchw_args
     }
 }
 
+// rows_to_nchw_kernel for plain fp16 rows [B*HW][C] (the image backbone's one-pass policy): the same tile,
+// one 16-byte load per lane, the value widened exactly.
+template <bool VEC>
+__global__ __launch_bounds__(256) void rows_to_nchw_f16_kernel(cmt_rows_to_nchw_args a) {
+    __shared__ float tile[64][65];
+    const int t = threadIdx.x;
+    const int p0 = blockIdx.x * 64, c0 = blockIdx.y * 64, b = blockIdx.z;
+    const int C = a.C, HW = a.HW;
+    {
+        const int cg = (t & 7) * 8, pl = t >> 3;
+#pragma unroll
+        for (int pass = 0; pass < 2; ++pass) {
+            const int pi = pass * 32 + pl;
+            if (p0 + pi < HW && c0 + cg < C) {
+                const pair8_t x = *(const pair8_t*)((const f16_t*)a.X + ((int64_t)b * HW + p0 + pi) * a.ldx + c0 + cg);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) tile[cg + j][pi] = (float)x[j];
+            }
+        }
+    }
+    __syncthreads();
+    float* Y = a.Y + (int64_t)b * C * HW;
+    if constexpr (VEC) {
+        const int q = (t & 15) * 4, cr = t >> 4;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int c = c0 + cr + 16 * k, p = p0 + q;
+            if (c < C && p < HW) {   // HW % 4 == 0: the four pixels are inside together
+                const float* s = &tile[cr + 16 * k][q];
+                *(f32x4*)(Y + (int64_t)c * HW + p) = f32x4{s[0], s[1], s[2], s[3]};
+            }
+        }
+    } else {
+        const int px = t & 63, cr = t >> 6;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            const int c = c0 + cr + 4 * k;
+            if (c < C && p0 + px < HW) Y[(int64_t)c * HW + p0 + px] = tile[cr + 4 * k][px];
+        }
+    }
+}
+
 template <typename T>
 bool fpn_aligned16(const T* p) { return (((uintptr_t)p) & 15) == 0; }
 
@@ -286,4 +328,22 @@ extern "C" int cmt_rows_to_nchw(const cmt_rows_to_nchw_args* a, void* stream) {
     else
         rows_to_nchw_kernel<false><<<grid, 256, 0, (hipStream_t)stream>>>(*a);
     return cmt_check_launch("cmt_rows_to_nchw");
+}
+
+extern "C" int cmt_rows_to_nchw_f16(const cmt_rows_to_nchw_args* a, void* stream) {
+    CMT_REQUIRE(a != nullptr, "cmt_rows_to_nchw_f16: null argument struct");
+    CMT_REQUIRE(a->X && a->Y, "cmt_rows_to_nchw_f16: X and Y must be non-null");
+    CMT_REQUIRE(a->B > 0 && a->HW > 0, "cmt_rows_to_nchw_f16: B and HW must be positive");
+    CMT_REQUIRE(a->C > 0 && a->C % 8 == 0, "cmt_rows_to_nchw_f16: C must be a positive multiple of 8");
+    CMT_REQUIRE(a->B <= 65535 && a->C <= 65535 * 64, "cmt_rows_to_nchw_f16: B or C beyond the grid");
+    CMT_REQUIRE((int64_t)a->B * a->HW < ((int64_t)1 << 31), "cmt_rows_to_nchw_f16: B*HW must be below 2^31");
+    CMT_REQUIRE(a->ldx >= (int64_t)a->C && a->ldx % 8 == 0 && fpn_aligned16(a->X),
+                "cmt_rows_to_nchw_f16: ldx >= C, % 8 (16-bit words), and a 16-byte aligned X required");
+    CMT_REQUIRE((((uintptr_t)a->Y) & 3) == 0, "cmt_rows_to_nchw_f16: Y must be 4-byte aligned");
+    dim3 grid((unsigned)cdiv(a->HW, 64), (unsigned)cdiv(a->C, 64), (unsigned)a->B);
+    if (a->HW % 4 == 0 && fpn_aligned16(a->Y))
+        rows_to_nchw_f16_kernel<true><<<grid, 256, 0, (hipStream_t)stream>>>(*a);
+    else
+        rows_to_nchw_f16_kernel<false><<<grid, 256, 0, (hipStream_t)stream>>>(*a);
+    return cmt_check_launch("cmt_rows_to_nchw_f16");
 }

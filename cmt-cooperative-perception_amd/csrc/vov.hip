@@ -13,7 +13,8 @@
 // block.  W goes through LDS in chunks of 32 k, staged once for the four waves, double-buffered, one
 // barrier per chunk.  Three f16 MFMA passes lo*Whi + hi*Wlo + hi*Whi per step with fp32 accumulation
 // in fixed K order.  No atomics on the data path (one writer per element), no call synchronises with
-// the host.
+// the host.  The second half of the file holds the opt-in one-pass fp16 policy of the same launches
+// (cmt_img_*_f16: plain fp16 rows, one MFMA per step).
 #include "cmt_common.h"
 
 namespace {
@@ -599,4 +600,496 @@ extern "C" int cmt_img_maxpool(const cmt_img_pool_args* a, void* stream) {
     CMT_REQUIRE(blocks < ((int64_t)1 << 31), "cmt_img_maxpool: grid too large");
     img_pool_kernel<<<dim3((unsigned)blocks), 256, 0, (hipStream_t)stream>>>(*a, Ho, Wo, total);
     return cmt_check_launch("cmt_img_maxpool");
+}
+
+// ---- the one-pass fp16 policy (cmt_img_*_f16) -------------------------------------------------------------------
+// The same launches on plain fp16 rows [B*H*W][C] with W rounded once to fp16: one MFMA per 16-k step instead
+// of three, 2 bytes per activation between layers instead of 4.  The tile (128 rows per workgroup, 32 per wave,
+// NB accumulators of 32 columns), the LDS row of 128 bytes with its XOR swizzle (w_store above, unchanged) and
+// the double buffer are those of the three-pass kernels; a staged chunk holds 64 k instead of hi | lo of 32, so
+// a chunk carries four MFMA steps per accumulator and the barrier, staging and gather cost per MFMA stays at
+// 3/4 of the three-pass kernel's instead of tripling.  A channel count with C % 64 == 32 ends in a half chunk
+// (32 k: pieces 4 .. 7 of the LDS row are neither loaded nor read).  K order: tap-major (source-major), channels
+// ascending, as above.
+namespace {
+
+constexpr int IMG_KC16 = 64;    // k per staged chunk of fp16 W (four 16-k steps)
+
+// A W chunk of plain fp16 rows: rows [n0, n0 + 32 NB) x 64 k from k offset kb of [N][ldw].  Piece i of thread
+// t: row (t >> 3) + 32 i, 16 bytes sub = t & 7 of the row's 128; a half chunk has pieces 0 .. 3 only (the
+// others would lie in the next tap or past the row's end) and leaves the registers as they are.
+template <int NB>
+__device__ __forceinline__ void w_load16(pair8_t (&q)[NB], const f16_t* Wt, int64_t ldw, int n0, int kb, bool half, int t) {
+    const int sub = t & 7;
+    if (half && sub >= 4) return;
+    const f16_t* src = Wt + (int64_t)(n0 + (t >> 3)) * ldw + kb + 8 * sub;
+#pragma unroll
+    for (int i = 0; i < NB; ++i) q[i] = *(const pair8_t*)(src + (int64_t)(32 * i) * ldw);
+}
+
+// 64 k (a half chunk: 32) of the wave's 32 rows against the staged chunk: step j is k = 16 j + 8 h .. + 7,
+// piece 2 j + h of the row
+template <int NB>
+__device__ __forceinline__ void mma_chunk16(const f16_t* buf, const pair8_t (&a)[4], f32x16 (&acc)[NB], bool half, int r, int h) {
+    const int swz = (r >> 1) & 7;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if (j >= 2 && half) break;   // workgroup-uniform
+#pragma unroll
+        for (int f = 0; f < NB; ++f) {
+            const pair8_t b = *(const pair8_t*)(buf + (32 * f + r) * IMG_WROW + (((2 * j + h) ^ swz) * 8));
+            acc[f] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[j], b, acc[f], 0, 0, 0);
+        }
+    }
+}
+
+// 64 (a half chunk: 32) channels from c of an fp16 row (xr already at the lane's 8 h): zero where the row is padding
+__device__ __forceinline__ void a_load16(const f16_t* xr, bool ok, int c, bool half, pair8_t (&a)[4]) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        a[j] = zero8();
+        if (ok && !(half && j >= 2)) a[j] = *(const pair8_t*)(xr + c + 16 * j);
+    }
+}
+
+// img_conv3x3_kernel on fp16 rows: ceil(Cin / 64) chunks per tap, the last a half chunk where Cin % 64 == 32.
+template <int NB>
+__global__ __launch_bounds__(256, NB >= 5 ? 2 : (NB >= 3 ? 3 : 4)) void img_conv3x3_f16_kernel(cmt_img_conv_args a, int Ho, int Wo, int M) {
+    __shared__ __attribute__((aligned(16))) f16_t s_w[2][NB * 32 * IMG_WROW];
+    const int t = threadIdx.x;
+    const int lane = t & 63, wave = t >> 6;
+    const int r = lane & 31, h = lane >> 5;
+    const int s = a.stride;
+    const int n0 = blockIdx.y * (32 * NB);
+    const int row0 = blockIdx.x * IMG_TM + wave * 32;
+    const int m = row0 + r;
+    const bool live = m < M;
+    int b = 0, yo = 0, xo = 0;
+    if (live) {
+        b = m / (Ho * Wo);
+        const int p = m - b * (Ho * Wo);
+        yo = p / Wo;
+        xo = p - yo * Wo;
+    }
+    const int Cin = a.Cin;
+    const int cpt = (Cin + IMG_KC16 - 1) / IMG_KC16, nchunks = 9 * cpt;
+    const bool odd = (Cin % IMG_KC16) != 0;   // the last chunk of every tap is a half chunk
+    const f16_t* X = (const f16_t*)a.X;
+    const f16_t* Wt = (const f16_t*)a.Wt;
+    auto tap_src = [&](int tap, bool& ok) -> const f16_t* {
+        const int yi = yo * s - 1 + tap / 3, xi = xo * s - 1 + tap % 3;
+        ok = live && (unsigned)yi < (unsigned)a.H && (unsigned)xi < (unsigned)a.W;
+        return X + ((int64_t)(b * a.H + (ok ? yi : 0)) * a.W + (ok ? xi : 0)) * a.ldx + 8 * h;
+    };
+    f32x16 acc[NB];
+#pragma unroll
+    for (int f = 0; f < NB; ++f)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[f][i] = 0.f;
+
+    pair8_t wq[NB], av[4], nv[4];
+#pragma unroll
+    for (int i = 0; i < NB; ++i) wq[i] = zero8();
+    bool half = odd && cpt == 1;
+    w_load16<NB>(wq, Wt, a.ldw, n0, 0, half, t);
+    w_store<NB>(s_w[0], wq, t);
+    int tap = 0, cc = 0;
+    bool ok;
+    const f16_t* xr = tap_src(0, ok);
+    bool any = __ballot(ok) != 0;
+    a_load16(xr, ok, 0, half, av);
+    __syncthreads();
+    for (int it = 0; it < nchunks; ++it) {
+        int ntap = tap, ncc = cc + 1;
+        if (ncc == cpt) {
+            ncc = 0;
+            ++ntap;
+        }
+        const bool more = it + 1 < nchunks;   // workgroup-uniform
+        const bool nhalf = odd && ncc == cpt - 1;
+        bool nok = ok, nany = any;
+        const f16_t* nxr = xr;
+        if (more) {
+            w_load16<NB>(wq, Wt, a.ldw, n0, ntap * Cin + IMG_KC16 * ncc, nhalf, t);
+            if (ncc == 0) {
+                nxr = tap_src(ntap, nok);
+                nany = __ballot(nok) != 0;
+            }
+            a_load16(nxr, nok, IMG_KC16 * ncc, nhalf, nv);
+        }
+        if (any) mma_chunk16<NB>(s_w[it & 1], av, acc, half, r, h);   // wave-uniform
+        // the other buffer was last read before the barrier that ended chunk it - 1
+        if (more) w_store<NB>(s_w[(it + 1) & 1], wq, t);
+        __syncthreads();
+        tap = ntap;
+        cc = ncc;
+        xr = nxr;
+        ok = nok;
+        any = nany;
+        half = nhalf;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) av[j] = nv[j];
+    }
+
+    f16_t* Y = (f16_t*)a.Y;
+    bool bad = false;
+#pragma unroll
+    for (int f = 0; f < NB; ++f) {
+        const int col = n0 + 32 * f + r;
+        const float sh = a.shift[col];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int row = row0 + acc_row(i, h);
+            if (row >= M) continue;
+            float v = acc[f][i] + sh;
+            bad |= f16_unrepresentable(v);
+            if (a.relu) v = fmaxf(v, 0.f);
+            Y[(int64_t)row * a.ldy + col] = (f16_t)v;
+        }
+    }
+    raise_range_flag(a.range_flag, bad);
+}
+
+// img_concat_kernel on fp16 rows: ceil(C_s / 64) chunks per source, the last a half chunk where C_s % 64 == 32.
+// part: the fp32 sums of the fp16 values as stored, in the order of the three-pass kernel.
+__global__ __launch_bounds__(256) void img_concat_f16_kernel(cmt_img_concat_args a, int tiles) {
+    constexpr int NB = IMG_CAT_NB;
+    __shared__ __attribute__((aligned(16))) f16_t s_w[2][NB * 32 * IMG_WROW];
+    __shared__ float s_part[4][32 * NB];
+    const int t = threadIdx.x;
+    const int lane = t & 63, wave = t >> 6;
+    const int r = lane & 31, h = lane >> 5;
+    const int b = blockIdx.z, n0 = blockIdx.y * (32 * NB);
+    const int p0 = blockIdx.x * IMG_TM + wave * 32;
+    const bool live = p0 + r < a.HW;
+    const bool any = p0 < a.HW;   // wave-uniform
+    const int64_t m = (int64_t)b * a.HW + (live ? p0 + r : 0);
+    const f16_t* Wt = (const f16_t*)a.Wt;
+    f32x16 acc[NB];
+#pragma unroll
+    for (int f = 0; f < NB; ++f)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[f][i] = 0.f;
+
+    pair8_t wq[NB], av[4], nv[4];
+#pragma unroll
+    for (int i = 0; i < NB; ++i) wq[i] = zero8();
+    int src = 0, cc = 0, off = 0, Cs = a.C[0];
+    bool half = Cs - IMG_KC16 * cc < IMG_KC16;
+    w_load16<NB>(wq, Wt, a.ldw, n0, 0, half, t);
+    w_store<NB>(s_w[0], wq, t);
+    const f16_t* xr = (const f16_t*)a.X[0] + m * a.ldx[0] + 8 * h;
+    a_load16(xr, live, 0, half, av);
+    __syncthreads();
+    for (int it = 0;; ++it) {
+        int nsrc = src, ncc = cc + 1, noff = off, nCs = Cs;
+        const f16_t* nxr = xr;
+        if (IMG_KC16 * ncc >= Cs) {
+            ncc = 0;
+            ++nsrc;
+            noff = off + Cs;
+        }
+        const bool more = nsrc < a.nsrc;   // workgroup-uniform
+        bool nhalf = false;
+        if (more) {
+            if (ncc == 0) {
+                nCs = a.C[nsrc];
+                nxr = (const f16_t*)a.X[nsrc] + m * a.ldx[nsrc] + 8 * h;
+            }
+            nhalf = nCs - IMG_KC16 * ncc < IMG_KC16;
+            w_load16<NB>(wq, Wt, a.ldw, n0, noff + IMG_KC16 * ncc, nhalf, t);
+            a_load16(nxr, live, IMG_KC16 * ncc, nhalf, nv);
+        }
+        if (any) mma_chunk16<NB>(s_w[it & 1], av, acc, half, r, h);
+        if (more) w_store<NB>(s_w[(it + 1) & 1], wq, t);
+        __syncthreads();
+        if (!more) break;
+        src = nsrc;
+        cc = ncc;
+        off = noff;
+        Cs = nCs;
+        xr = nxr;
+        half = nhalf;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) av[j] = nv[j];
+    }
+
+    f16_t* Y = (f16_t*)a.Y;
+    bool bad = false;
+#pragma unroll
+    for (int f = 0; f < NB; ++f) {
+        const int col = n0 + 32 * f + r;
+        const float sh = a.shift[col];
+        float sum = 0.f;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int p = p0 + acc_row(i, h);
+            if (p >= a.HW) continue;
+            float v = acc[f][i] + sh;
+            bad |= f16_unrepresentable(v);
+            if (a.relu) v = fmaxf(v, 0.f);
+            const f16_t y = (f16_t)v;
+            Y[((int64_t)b * a.HW + p) * a.ldy + col] = y;
+            sum += (float)y;
+        }
+        sum = pair_sum(sum);
+        if (h == 0) s_part[wave][32 * f + r] = sum;
+    }
+    raise_range_flag(a.range_flag, bad);
+    if (a.part != nullptr) {   // workgroup-uniform
+        __syncthreads();
+        if (t < 32 * NB)
+            a.part[((int64_t)b * tiles + blockIdx.x) * a.Cout + n0 + t] =
+                ((s_part[0][t] + s_part[1][t]) + s_part[2][t]) + s_part[3][t];
+    }
+}
+
+// img_stem_kernel with every pixel rounded once to fp16 and W fp16 [Cout][32]: one MFMA per step
+__global__ __launch_bounds__(256) void img_stem_f16_kernel(cmt_img_stem_args a, int Ho, int Wo, int M) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int r = lane & 31, h = lane >> 5;
+    const int row0 = blockIdx.x * IMG_TM + wave * 32;
+    if (row0 >= M) return;   // wave-uniform; the kernel has no barrier
+    const int m = row0 + r;
+    const bool live = m < M;
+    int b = 0, yo = 0, xo = 0;
+    if (live) {
+        b = m / (Ho * Wo);
+        const int p = m - b * (Ho * Wo);
+        yo = p / Wo;
+        xo = p - yo * Wo;
+    }
+    const int Cin = a.Cin, K = 9 * Cin;
+    const float* xb = a.X + (int64_t)b * a.x_bstride;
+    bool bad = false;
+    pair8_t av[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int jj = 0; jj < 8; ++jj) {
+            const int k = 16 * j + 8 * h + jj;
+            float v = 0.f;
+            if (live && k < K) {
+                const int tap = k / Cin, c = k - tap * Cin;
+                const int yi = 2 * yo - 1 + tap / 3, xi = 2 * xo - 1 + tap % 3;
+                if ((unsigned)yi < (unsigned)a.H && (unsigned)xi < (unsigned)a.W)
+                    v = xb[((int64_t)c * a.H + yi) * a.W + xi];
+            }
+            bad |= f16_unrepresentable(v);
+            av[j][jj] = (f16_t)v;
+        }
+    f16_t* Y = (f16_t*)a.Y;
+    for (int nb = 0; nb < a.Cout / 32; ++nb) {
+        const int col = 32 * nb + r;
+        const f16_t* wr = (const f16_t*)a.Wt + (int64_t)col * IMG_KC + 8 * h;
+        f32x16 acc;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(av[j], *(const pair8_t*)(wr + 16 * j), acc, 0, 0, 0);
+        const float sh = a.shift[col];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int row = row0 + acc_row(i, h);
+            if (row >= M) continue;
+            float v = acc[i] + sh;
+            bad |= f16_unrepresentable(v);
+            if (a.relu) v = fmaxf(v, 0.f);
+            Y[(int64_t)row * a.ldy + col] = (f16_t)v;
+        }
+    }
+    raise_range_flag(a.range_flag, bad);
+}
+
+// One thread: 8 channels of one pixel, fp32 multiply and add, one rounding.  Reads come before the writes of
+// the same elements, so Y may be X.
+__global__ __launch_bounds__(256) void img_apply_f16_kernel(cmt_img_apply_args a, int64_t total) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int groups = a.C / 8;
+    const int64_t row = idx / groups;
+    const int c = (int)(idx - row * groups) * 8;
+    const int b = (int)(row / a.HW);
+    const pair8_t x = *(const pair8_t*)((const f16_t*)a.X + row * a.ldx + c);
+    const float* g = a.gate + (int64_t)b * a.C + c;
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = (float)x[j] * g[j];
+    if (a.R != nullptr) {
+        const pair8_t rr = *(const pair8_t*)((const f16_t*)a.R + row * a.ldr + c);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] += (float)rr[j];
+    }
+    bool bad = false;
+    pair8_t y;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        bad |= f16_unrepresentable(v[j]);
+        y[j] = (f16_t)v[j];
+    }
+    *(pair8_t*)((f16_t*)a.Y + row * a.ldy + c) = y;
+    raise_range_flag(a.range_flag, bad);
+}
+
+// One thread: 8 channels of one output pixel; img_pool_kernel's window on fp16 values, copied unchanged.
+__global__ __launch_bounds__(256) void img_pool_f16_kernel(cmt_img_pool_args a, int Ho, int Wo, int64_t total) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int groups = a.C / 8;
+    const int64_t m = idx / groups;
+    const int c = (int)(idx - m * groups) * 8;
+    const int b = (int)(m / ((int64_t)Ho * Wo));
+    const int p = (int)(m - (int64_t)b * Ho * Wo);
+    const int yo = p / Wo, xo = p - yo * Wo;
+    const f16_t* X = (const f16_t*)a.X;
+    pair8_t best = *(const pair8_t*)(X + ((int64_t)(b * a.H + 2 * yo) * a.W + 2 * xo) * a.ldx + c);
+#pragma unroll
+    for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+        for (int dx = 0; dx < 3; ++dx) {
+            const int yi = 2 * yo + dy, xi = 2 * xo + dx;
+            if ((dy == 0 && dx == 0) || yi >= a.H || xi >= a.W) continue;
+            const pair8_t x = *(const pair8_t*)(X + ((int64_t)(b * a.H + yi) * a.W + xi) * a.ldx + c);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const float v = (float)x[j];
+                if (v > (float)best[j] || v != v) best[j] = x[j];
+            }
+        }
+    *(pair8_t*)((f16_t*)a.Y + m * a.ldy + c) = best;
+}
+
+template <int NB>
+void img_conv_f16_launch(const cmt_img_conv_args* a, int Ho, int Wo, int64_t M, hipStream_t s) {
+    img_conv3x3_f16_kernel<NB><<<dim3((unsigned)cdiv64(M, IMG_TM), (unsigned)(a->Cout / (32 * NB))), 256, 0, s>>>(*a, Ho, Wo, (int)M);
+}
+
+}  // namespace
+
+extern "C" int cmt_img_stem_f16(const cmt_img_stem_args* a, void* stream) {
+    CMT_REQUIRE(a != nullptr, "cmt_img_stem_f16: null argument struct");
+    CMT_REQUIRE(a->X && a->Wt && a->shift && a->Y, "cmt_img_stem_f16: X, Wt, shift and Y must be non-null");
+    CMT_REQUIRE(a->B > 0 && a->H > 0 && a->W > 0, "cmt_img_stem_f16: B, H and W must be positive");
+    CMT_REQUIRE(a->Cin >= 1 && a->Cin <= 3, "cmt_img_stem_f16: Cin must be 1, 2 or 3");
+    CMT_REQUIRE(a->Cout > 0 && a->Cout % 32 == 0, "cmt_img_stem_f16: Cout must be a positive multiple of 32");
+    CMT_REQUIRE((int64_t)a->B * a->H * a->W < ((int64_t)1 << 31), "cmt_img_stem_f16: B*H*W must be below 2^31");
+    CMT_REQUIRE(a->x_bstride >= (int64_t)a->Cin * a->H * a->W, "cmt_img_stem_f16: x_bstride below Cin*H*W");
+    CMT_REQUIRE(a->ldy >= (int64_t)a->Cout && a->ldy % 8 == 0, "cmt_img_stem_f16: ldy >= Cout and % 8 (16-bit words) required");
+    CMT_REQUIRE(img_aligned16(a->Wt) && (((uintptr_t)a->X) & 3) == 0 && (((uintptr_t)a->Y) & 1) == 0,
+                "cmt_img_stem_f16: Wt must be 16-byte, X 4-byte and Y 2-byte aligned");
+    const int Ho = (a->H - 1) / 2 + 1, Wo = (a->W - 1) / 2 + 1;
+    const int64_t M = (int64_t)a->B * Ho * Wo;
+    img_stem_f16_kernel<<<dim3((unsigned)cdiv64(M, IMG_TM)), 256, 0, (hipStream_t)stream>>>(*a, Ho, Wo, (int)M);
+    return cmt_check_launch("cmt_img_stem_f16");
+}
+
+extern "C" int cmt_img_conv3x3_f16(const cmt_img_conv_args* a, void* stream) {
+    CMT_REQUIRE(a != nullptr, "cmt_img_conv3x3_f16: null argument struct");
+    CMT_REQUIRE(a->X && a->Wt && a->shift && a->Y, "cmt_img_conv3x3_f16: X, Wt, shift and Y must be non-null");
+    CMT_REQUIRE(a->B > 0 && a->H > 0 && a->W > 0, "cmt_img_conv3x3_f16: B, H and W must be positive");
+    CMT_REQUIRE(a->stride == 1 || a->stride == 2, "cmt_img_conv3x3_f16: stride must be 1 or 2");
+    CMT_REQUIRE(a->Cin > 0 && a->Cin % 32 == 0, "cmt_img_conv3x3_f16: Cin must be a positive multiple of 32");
+    CMT_REQUIRE(a->Cout > 0 && a->Cout % 32 == 0 && a->Cout <= 256,
+                "cmt_img_conv3x3_f16: Cout must be a positive multiple of 32, at most 256");
+    CMT_REQUIRE((int64_t)a->B * a->H * a->W < ((int64_t)1 << 31), "cmt_img_conv3x3_f16: B*H*W must be below 2^31");
+    CMT_REQUIRE(a->ldx >= (int64_t)a->Cin && a->ldx % 8 == 0 && a->ldw >= 9 * (int64_t)a->Cin && a->ldw % 8 == 0 &&
+                    a->ldy >= (int64_t)a->Cout && a->ldy % 8 == 0,
+                "cmt_img_conv3x3_f16: ldx >= Cin, ldw >= 9 Cin and ldy >= Cout (all % 8, 16-bit words) required");
+    CMT_REQUIRE(img_aligned16(a->X) && img_aligned16(a->Wt) && (((uintptr_t)a->Y) & 1) == 0,
+                "cmt_img_conv3x3_f16: X and Wt must be 16-byte aligned");
+    const int s = a->stride;
+    const int Ho = (a->H - 1) / s + 1, Wo = (a->W - 1) / s + 1;
+    const int64_t M = (int64_t)a->B * Ho * Wo;
+    hipStream_t st = (hipStream_t)stream;
+    const int blocks = a->Cout / 32;
+    int nb = a->nb;
+    CMT_REQUIRE(nb >= 0 && (nb == 0 || blocks % nb == 0), "cmt_img_conv3x3_f16: nb must be 0 or a divisor of Cout / 32");
+    if (nb == 0) {
+        // as cmt_img_conv3x3: all columns per workgroup unless the row tiles alone leave compute units idle
+        const int64_t tiles = cdiv64(M, IMG_TM), cus = cmt_cu_count();
+        nb = blocks;
+        if (tiles < cus) {
+            nb = 1;
+            for (int d = blocks; d > 1; --d)
+                if (blocks % d == 0 && tiles * (blocks / d) >= cus) {
+                    nb = d;
+                    break;
+                }
+        }
+    }
+    switch (nb) {
+        case 1: img_conv_f16_launch<1>(a, Ho, Wo, M, st); break;
+        case 2: img_conv_f16_launch<2>(a, Ho, Wo, M, st); break;
+        case 3: img_conv_f16_launch<3>(a, Ho, Wo, M, st); break;
+        case 4: img_conv_f16_launch<4>(a, Ho, Wo, M, st); break;
+        case 5: img_conv_f16_launch<5>(a, Ho, Wo, M, st); break;
+        case 6: img_conv_f16_launch<6>(a, Ho, Wo, M, st); break;
+        case 7: img_conv_f16_launch<7>(a, Ho, Wo, M, st); break;
+        default: img_conv_f16_launch<8>(a, Ho, Wo, M, st); break;
+    }
+    return cmt_check_launch("cmt_img_conv3x3_f16");
+}
+
+extern "C" int cmt_img_concat1x1_f16(const cmt_img_concat_args* a, void* stream) {
+    CMT_REQUIRE(a != nullptr, "cmt_img_concat1x1_f16: null argument struct");
+    CMT_REQUIRE(a->Wt && a->shift && a->Y, "cmt_img_concat1x1_f16: Wt, shift and Y must be non-null");
+    CMT_REQUIRE(a->B > 0 && a->HW > 0, "cmt_img_concat1x1_f16: B and HW must be positive");
+    CMT_REQUIRE(a->B <= 65535, "cmt_img_concat1x1_f16: B beyond the grid");
+    CMT_REQUIRE(a->nsrc >= 1 && a->nsrc <= CMT_IMG_MAX_SRC, "cmt_img_concat1x1_f16: 1 to 8 sources required");
+    CMT_REQUIRE(a->Cout > 0 && a->Cout % (32 * IMG_CAT_NB) == 0, "cmt_img_concat1x1_f16: Cout must be a positive multiple of 128");
+    CMT_REQUIRE((int64_t)a->B * a->HW < ((int64_t)1 << 31), "cmt_img_concat1x1_f16: B*HW must be below 2^31");
+    int64_t K = 0;
+    for (int s = 0; s < a->nsrc; ++s) {
+        CMT_REQUIRE(a->X[s] != nullptr && img_aligned16(a->X[s]), "cmt_img_concat1x1_f16: every source must be non-null and 16-byte aligned");
+        CMT_REQUIRE(a->C[s] > 0 && a->C[s] % 32 == 0, "cmt_img_concat1x1_f16: every source width must be a positive multiple of 32");
+        CMT_REQUIRE(a->ldx[s] >= (int64_t)a->C[s] && a->ldx[s] % 8 == 0, "cmt_img_concat1x1_f16: ldx >= C and % 8 (16-bit words) required");
+        K += a->C[s];
+    }
+    CMT_REQUIRE(K < ((int64_t)1 << 24), "cmt_img_concat1x1_f16: K too large");
+    CMT_REQUIRE(a->ldw >= K && a->ldw % 8 == 0 && a->ldy >= (int64_t)a->Cout && a->ldy % 8 == 0,
+                "cmt_img_concat1x1_f16: ldw >= K and ldy >= Cout (both % 8, 16-bit words) required");
+    CMT_REQUIRE(img_aligned16(a->Wt) && (((uintptr_t)a->Y) & 1) == 0 && (((uintptr_t)a->part) & 3) == 0,
+                "cmt_img_concat1x1_f16: Wt must be 16-byte aligned, part 4-byte");
+    const int tiles = cdiv(a->HW, IMG_TM);
+    dim3 grid((unsigned)tiles, (unsigned)(a->Cout / (32 * IMG_CAT_NB)), (unsigned)a->B);
+    img_concat_f16_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(*a, tiles);
+    return cmt_check_launch("cmt_img_concat1x1_f16");
+}
+
+extern "C" int cmt_img_ese_apply_f16(const cmt_img_apply_args* a, void* stream) {
+    CMT_REQUIRE(a != nullptr, "cmt_img_ese_apply_f16: null argument struct");
+    CMT_REQUIRE(a->X && a->gate && a->Y, "cmt_img_ese_apply_f16: X, gate and Y must be non-null");
+    CMT_REQUIRE(a->B > 0 && a->HW > 0, "cmt_img_ese_apply_f16: B and HW must be positive");
+    CMT_REQUIRE(a->C > 0 && a->C % 8 == 0, "cmt_img_ese_apply_f16: C must be a positive multiple of 8");
+    CMT_REQUIRE((int64_t)a->B * a->HW < ((int64_t)1 << 31), "cmt_img_ese_apply_f16: B*HW must be below 2^31");
+    CMT_REQUIRE(a->ldx >= (int64_t)a->C && a->ldx % 8 == 0 && a->ldy >= (int64_t)a->C && a->ldy % 8 == 0,
+                "cmt_img_ese_apply_f16: ldx, ldy >= C and % 8 (16-bit words) required");
+    CMT_REQUIRE(img_aligned16(a->X) && img_aligned16(a->Y) && img_aligned16(a->gate),
+                "cmt_img_ese_apply_f16: X, Y and gate must be 16-byte aligned");
+    if (a->R != nullptr)
+        CMT_REQUIRE(a->ldr >= (int64_t)a->C && a->ldr % 8 == 0 && img_aligned16(a->R),
+                    "cmt_img_ese_apply_f16: ldr >= C, % 8, and a 16-byte aligned R required");
+    const int64_t total = (int64_t)a->B * a->HW * (a->C / 8);
+    const int64_t blocks = cdiv64(total, 256);
+    CMT_REQUIRE(blocks < ((int64_t)1 << 31), "cmt_img_ese_apply_f16: grid too large");
+    img_apply_f16_kernel<<<dim3((unsigned)blocks), 256, 0, (hipStream_t)stream>>>(*a, total);
+    return cmt_check_launch("cmt_img_ese_apply_f16");
+}
+
+extern "C" int cmt_img_maxpool_f16(const cmt_img_pool_args* a, void* stream) {
+    CMT_REQUIRE(a != nullptr, "cmt_img_maxpool_f16: null argument struct");
+    CMT_REQUIRE(a->X && a->Y, "cmt_img_maxpool_f16: X and Y must be non-null");
+    CMT_REQUIRE(a->B > 0 && a->H >= 2 && a->W >= 2, "cmt_img_maxpool_f16: B positive and H, W >= 2 required");
+    CMT_REQUIRE(a->C > 0 && a->C % 8 == 0, "cmt_img_maxpool_f16: C must be a positive multiple of 8");
+    CMT_REQUIRE((int64_t)a->B * a->H * a->W < ((int64_t)1 << 31), "cmt_img_maxpool_f16: B*H*W must be below 2^31");
+    CMT_REQUIRE(a->ldx >= (int64_t)a->C && a->ldx % 8 == 0 && a->ldy >= (int64_t)a->C && a->ldy % 8 == 0,
+                "cmt_img_maxpool_f16: ldx, ldy >= C and % 8 (16-bit words) required");
+    CMT_REQUIRE(img_aligned16(a->X) && img_aligned16(a->Y), "cmt_img_maxpool_f16: X and Y must be 16-byte aligned");
+    const int Ho = (a->H - 2) / 2 + 1, Wo = (a->W - 2) / 2 + 1;
+    const int64_t total = (int64_t)a->B * Ho * Wo * (a->C / 8);
+    const int64_t blocks = cdiv64(total, 256);
+    CMT_REQUIRE(blocks < ((int64_t)1 << 31), "cmt_img_maxpool_f16: grid too large");
+    img_pool_f16_kernel<<<dim3((unsigned)blocks), 256, 0, (hipStream_t)stream>>>(*a, Ho, Wo, total);
+    return cmt_check_launch("cmt_img_maxpool_f16");
 }

@@ -23,6 +23,12 @@ sources without a concatenated map, its epilogue leaving the pool's per-tile sum
 ``cmt_img_ese_apply`` scales (and adds the identity) in place; ``cmt_img_maxpool`` between stages.  The
 selected maps leave through ``cmt_rows_to_nchw`` as contiguous fp32 NCHW, what ``CPFPN`` reads.
 
+Arithmetic.  ``native_img.set_img_precision('ref' | 'fp16')`` (env ``CMT_IMG_PRECISION``, default ``'ref'``),
+read per forward: ``'ref'`` is the routing above, three-pass split-f16 on pair rows; ``'fp16'`` runs the same
+launches on ``cmt_img_*_f16`` -- plain fp16 rows between launches, weights folded in float64 and rounded once to
+fp16, one MFMA per step with fp32 accumulation -- and leaves through ``cmt_rows_to_nchw_f16``; nothing is routed
+to ``cmt_gemm`` there.  The gate stays fp32 (``cmt_img_ese_gate``).  Packs are cached per arithmetic.
+
 state_dict keys carry the ``/`` of the reference's module names: ``stem.stem_1/conv.weight``,
 ``stem.stem_1/norm.{weight, bias, running_mean, running_var, num_batches_tracked}``,
 ``stage3.OSA3_2.layers.4.OSA3_2_4/conv.weight``, ``stage2.OSA2_1.concat.OSA2_1_concat/conv.weight``,
@@ -153,21 +159,25 @@ class VoVNet(nn.Module, RangeFlagMixin):
         """weights come from a checkpoint (or the caller); nothing to initialise"""
 
     # ---- packs -------------------------------------------------------------------------------------------
-    def _packed(self, key, seq, pack):
+    def _packed(self, key, seq, pack, fp16=False):
         conv, bn = _pair_of(seq)
-        return self._pack.get(key, [conv.weight] + bn_tensors(bn), bn.eps,
+        return self._pack.get(key + ("fp16",) if fp16 else key, [conv.weight] + bn_tensors(bn), bn.eps,
                               lambda: pack(conv.weight, bn_tensors(bn) + [bn.eps]))
 
-    def packed_stem(self, i):
-        """(pair rows, shift) of stem conv ``i`` (0: [64, 2, 32] for cmt_img_stem; 1, 2: [Cout, 2, 9 Cin])"""
+    def packed_stem(self, i, fp16=False):
+        """(pair rows, shift) of stem conv ``i`` (0: [64, 2, 32] for cmt_img_stem; 1, 2: [Cout, 2, 9 Cin]);
+        ``fp16``: (fp16 rows [64, 32] or [Cout, 9 Cin], shift) of the one-pass policy, cached apart"""
         seq = self.stem[3 * i:3 * i + 2]
+        if fp16:
+            return self._packed(("stem", i), seq, NI.pack_stem_f16 if i == 0 else NI.pack_conv3x3_f16, True)
         return self._packed(("stem", i), seq, NI.pack_stem if i == 0 else NB.pack_conv3x3)
 
-    def packed_layer(self, blk_name, blk, i):
-        """(pair rows, shift) of 3 x 3 layer ``i`` of an OSA block, or of its aggregation (``i='concat'``)"""
+    def packed_layer(self, blk_name, blk, i, fp16=False):
+        """(pair rows, shift) of 3 x 3 layer ``i`` of an OSA block, or of its aggregation (``i='concat'``);
+        ``fp16``: the one-pass policy's fp16 rows, cached apart"""
         if i == "concat":
-            return self._packed((blk_name, i), blk.concat, NI.pack_concat)
-        return self._packed((blk_name, i), blk.layers[i], NB.pack_conv3x3)
+            return self._packed((blk_name, i), blk.concat, NI.pack_concat_f16 if fp16 else NI.pack_concat, fp16)
+        return self._packed((blk_name, i), blk.layers[i], NI.pack_conv3x3_f16 if fp16 else NB.pack_conv3x3, fp16)
 
     def packed_fc(self, blk_name, blk):
         """(fp32 [C, C], fp32 [C]) of the gate's fc"""
@@ -194,8 +204,50 @@ class VoVNet(nn.Module, RangeFlagMixin):
         return NI.ese_apply(y, gate, B=B, HW=H * W, C=blk.concat_ch, identity=x if blk.identity else None, out=y,
                             range_flag=flag)
 
+    def _osa_f16(self, name, blk, x, B, H, W, flag):
+        srcs, cur, cin = [x], x, blk.in_ch
+        for i in range(len(blk.layers)):
+            w16, shift = self.packed_layer(name, blk, i, fp16=True)
+            cur = NI.conv3x3_f16(cur, w16, shift, B=B, H=H, W=W, Cin=cin, Cout=blk.stage_ch, stride=1, range_flag=flag)
+            srcs.append(cur)
+            cin = blk.stage_ch
+        w16, shift = self.packed_layer(name, blk, "concat", fp16=True)
+        y, part = NI.concat1x1_f16(srcs, w16, shift, B=B, HW=H * W, Cout=blk.concat_ch, part=True, range_flag=flag)
+        fw, fb = self.packed_fc(name, blk)
+        gate = NI.ese_gate(part, fw, fb, HW=H * W)
+        return NI.ese_apply_f16(y, gate, B=B, HW=H * W, C=blk.concat_ch, identity=x if blk.identity else None, out=y,
+                                range_flag=flag)
+
+    def _forward_f16(self, x, B, H, W, flag):
+        """forward's body on the one-pass fp16 kernels: fp16 rows [B*H*W, C] between launches"""
+        outs = OrderedDict()
+        s = [self.stem[3 * i].out_channels for i in range(3)]
+        w16, shift = self.packed_stem(0, fp16=True)
+        rows = NI.stem_f16(x, w16, shift, Cout=s[0], range_flag=flag)
+        H, W = NB.out_hw(H, W, 2)
+        w16, shift = self.packed_stem(1, fp16=True)
+        rows = NI.conv3x3_f16(rows, w16, shift, B=B, H=H, W=W, Cin=s[0], Cout=s[1], stride=1, range_flag=flag)
+        w16, shift = self.packed_stem(2, fp16=True)
+        rows = NI.conv3x3_f16(rows, w16, shift, B=B, H=H, W=W, Cin=s[1], Cout=s[2], stride=2, range_flag=flag)
+        H, W = NB.out_hw(H, W, 2)
+        C = s[2]
+        if "stem" in self._out_features:
+            outs["stem"] = NF.rows_to_nchw_f16(rows, (B, C, H, W))
+        for name in self.stage_names:
+            for blk_name, blk in getattr(self, name).named_children():
+                if isinstance(blk, _Pool):
+                    rows = NI.maxpool_f16(rows, B=B, H=H, W=W, C=C)
+                    H, W = NI.pool_hw(H, W)
+                else:
+                    rows = self._osa_f16(blk_name, blk, rows, B, H, W, flag)
+                    C = blk.concat_ch
+            if name in self._out_features:
+                outs[name] = NF.rows_to_nchw_f16(rows, (B, C, H, W))
+        return outs
+
     def forward(self, x):
-        """[B, input_ch, H, W] -> an ordered dict name -> contiguous fp32 NCHW map for ``out_features``"""
+        """[B, input_ch, H, W] -> an ordered dict name -> contiguous fp32 NCHW map for ``out_features``, in the
+        arithmetic of ``native_img.img_precision()`` at the time of the call"""
         inference_only(self)
         if not torch.is_tensor(x) or x.dim() != 4 or x.shape[1] != self.input_ch or not x.is_floating_point():
             raise ValueError(f"VoVNet takes a floating [B, {self.input_ch}, H, W] image, got "
@@ -212,6 +264,8 @@ class VoVNet(nn.Module, RangeFlagMixin):
         with torch.no_grad():
             flag = self._range_flag(x.device)
             x = x.float().contiguous()
+            if NI.img_precision() == "fp16":
+                return self._forward_f16(x, B, H, W, flag)
             s = [self.stem[3 * i].out_channels for i in range(3)]
             wp, shift = self.packed_stem(0)
             rows = NI.stem(x, wp, shift, Cout=s[0], range_flag=flag)

@@ -379,6 +379,12 @@ def _load():
         "cmt_img_ese_gate": ([P(ImgGateArgs), _vp], _int),
         "cmt_img_ese_apply": ([P(ImgApplyArgs), _vp], _int),
         "cmt_img_maxpool": ([P(ImgPoolArgs), _vp], _int),
+        "cmt_img_stem_f16": ([P(ImgStemArgs), _vp], _int),
+        "cmt_img_conv3x3_f16": ([P(ImgConvArgs), _vp], _int),
+        "cmt_img_concat1x1_f16": ([P(ImgConcatArgs), _vp], _int),
+        "cmt_img_ese_apply_f16": ([P(ImgApplyArgs), _vp], _int),
+        "cmt_img_maxpool_f16": ([P(ImgPoolArgs), _vp], _int),
+        "cmt_rows_to_nchw_f16": ([P(RowsToNchwArgs), _vp], _int),
         "cmt_img_prepare_args_size": ([], _i64),
         "cmt_img_prepare": ([P(ImgPrepareArgs), _vp], _int),
         "cmt_adamw_step": ([P(AdamwArgs), _vp], _int),

@@ -11,7 +11,7 @@ from . import native as N
 from .native import _check, _dev, _p, _stream, lib
 from .native_bev import RowMap, _flag, _pair_rows, _shift, fold_bn, pack_conv3x3, split_pair
 
-__all__ = ["lateral", "rows_to_nchw", "pack_conv1x1", "pack_conv3x3_bias", "nearest_index"]
+__all__ = ["lateral", "rows_to_nchw", "rows_to_nchw_f16", "pack_conv1x1", "pack_conv3x3_bias", "nearest_index"]
 
 
 def _is_bn(bias_or_bn):
@@ -108,4 +108,25 @@ def rows_to_nchw(rows, shape, out=None):
     a.B, a.C, a.HW, a.reserved = B, C, H * W, 0
     a.X, a.ldx, a.Y = _p(rows), 2 * C, _p(Y)
     _check(lib().cmt_rows_to_nchw(ctypes.byref(a), _stream()), "cmt_rows_to_nchw")
+    return Y
+
+
+def rows_to_nchw_f16(rows, shape, out=None):
+    """cmt_rows_to_nchw_f16: fp16 rows [B*H*W, C] of the map ``shape`` = (B, C, H, W) (the image backbone's one-pass
+    policy) -> contiguous fp32 NCHW, every value widened exactly"""
+    B, C, H, W = (int(s) for s in shape)
+    if min(B, H, W) <= 0 or C <= 0 or C % 8:
+        raise ValueError(f"a non-empty map with C % 8 == 0 required, got {(B, C, H, W)}")
+    if not torch.is_tensor(rows) or rows.dtype != torch.float16 or rows.dim() != 2 or rows.shape[1] != C or \
+            rows.shape[0] < B * H * W or not rows.is_contiguous():
+        raise ValueError(f"rows must be contiguous fp16 rows [>= {B * H * W}, {C}], got "
+                         f"{(rows.dtype, tuple(rows.shape)) if torch.is_tensor(rows) else type(rows)}")
+    if out is not None and (out.dtype != torch.float32 or tuple(out.shape) != (B, C, H, W) or not out.is_contiguous()):
+        raise ValueError(f"out must be contiguous fp32 {(B, C, H, W)}, got {out.dtype} {tuple(out.shape)}")
+    _dev(rows, out)
+    Y = out if out is not None else torch.empty((B, C, H, W), dtype=torch.float32, device=rows.device)
+    a = N.RowsToNchwArgs()
+    a.B, a.C, a.HW, a.reserved = B, C, H * W, 0
+    a.X, a.ldx, a.Y = _p(rows), C, _p(Y)
+    _check(lib().cmt_rows_to_nchw_f16(ctypes.byref(a), _stream()), "cmt_rows_to_nchw_f16")
     return Y

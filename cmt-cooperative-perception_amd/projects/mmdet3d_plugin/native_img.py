@@ -4,6 +4,7 @@ device check, tensors must live on a HIP device, there is no CPU fallback, no wr
 host.  The packing reuses native_bev's float64 BN fold and f16 hi / lo split.
 """
 import ctypes
+import os
 
 import numpy as np
 import torch
@@ -15,7 +16,9 @@ from .native_fpn import pack_conv1x1
 
 __all__ = ["STEM_K", "CONCAT_TM", "MAX_SRC", "pack_stem", "pack_concat", "pool_hw", "concat_tiles", "stem", "conv3x3",
            "conv3x3_gemm", "concat1x1", "ese_gate", "ese_apply", "maxpool", "IMG_MEAN", "IMG_STD", "norm_constants",
-           "test_crop", "crop_lidar2img", "prepare_images"]
+           "test_crop", "crop_lidar2img", "prepare_images", "set_img_precision", "img_precision", "round_f16",
+           "pack_stem_f16", "pack_conv3x3_f16", "pack_concat_f16", "stem_f16", "conv3x3_f16", "concat1x1_f16",
+           "ese_apply_f16", "maxpool_f16"]
 
 STEM_K = 32        # the stem's K = 9 Cin <= 27, zero-padded (cmt_hip.h)
 CONCAT_TM = 128    # pixels per tile of cmt_img_concat1x1 (cmt_img_concat_tile_rows())
@@ -369,4 +372,246 @@ def maxpool(X, *, B, H, W, C, out=None):
     a.B, a.H, a.W, a.C = B, H, W, C
     a.X, a.ldx, a.Y, a.ldy = _p(X), 2 * C, _p(Y), 2 * C
     _check(lib().cmt_img_maxpool(ctypes.byref(a), _stream()), "cmt_img_maxpool")
+    return Y
+
+
+# ---- the one-pass fp16 policy -------------------------------------------------------------------------------------
+# Arithmetic of VoVNet (models/backbones/vovnet.py): "ref" (the three-pass split-f16 kernels above on pair rows,
+# fp32-accurate) or "fp16" (cmt_img_*_f16: plain fp16 rows [B*H*W, C] between launches, weights folded in float64
+# and rounded once to fp16, one MFMA per 16-k step with fp32 accumulation).  Independent of runtime.set_precision
+# (the head's policy).  The initial mode is the environment variable CMT_IMG_PRECISION, read once here.
+_IMG_PRECISIONS = ("ref", "fp16")
+
+
+def _img_precision_name(mode, what):
+    if mode not in _IMG_PRECISIONS:
+        raise ValueError(f"{what} must be one of {list(_IMG_PRECISIONS)}, got {mode!r}")
+    return mode
+
+
+_img_precision = _img_precision_name(os.environ.get("CMT_IMG_PRECISION") or "ref", "CMT_IMG_PRECISION")
+
+
+def set_img_precision(mode):
+    """Select the arithmetic of the image backbone ("ref" or "fp16"); returns the previous mode."""
+    global _img_precision
+    old, _img_precision = _img_precision, _img_precision_name(mode, "img precision")
+    return old
+
+
+def img_precision():
+    """the current mode of set_img_precision"""
+    return _img_precision
+
+
+def round_f16(w64):
+    """float64 rows [N, K] -> contiguous fp16 [N, K], rounded once (RNE); a value that is non-finite or beyond
+    fp16's largest finite 65504 raises"""
+    if w64.numel() and not bool(torch.isfinite(w64).all()):
+        raise ValueError("non-finite folded weights cannot take the fp16 format")
+    if w64.numel() and w64.abs().max().item() > 65504.0:
+        raise ValueError("folded weights beyond the f16 range (65504) cannot take the fp16 format")
+    return w64.half().contiguous()
+
+
+def pack_stem_f16(w, bn):
+    """pack_stem for cmt_img_stem_f16 -> (fp16 [Cout, 32], fp32 shift [Cout])"""
+    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or not 1 <= w.shape[1] <= 3:
+        raise ValueError(f"expected a (Cout, Cin <= 3, 3, 3) conv weight, got {tuple(w.shape)}")
+    scale, shift = fold_bn(*bn)
+    w64 = (w.detach().double() * scale[:, None, None, None]).permute(0, 2, 3, 1).reshape(w.shape[0], -1)
+    rows = torch.zeros((w.shape[0], STEM_K), dtype=torch.float64, device=w.device)
+    rows[:, :w64.shape[1]] = w64
+    return round_f16(rows), shift.float().contiguous()
+
+
+def pack_conv3x3_f16(w, bn):
+    """native_bev.pack_conv3x3 for cmt_img_conv3x3_f16 -> (fp16 [Cout, 9 Cin] with k = (ky*3 + kx) * Cin + c,
+    fp32 shift [Cout])"""
+    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3):
+        raise ValueError(f"expected a (Cout, Cin, 3, 3) conv weight, got {tuple(w.shape)}")
+    scale, shift = fold_bn(*bn)
+    w64 = w.detach().double() * scale[:, None, None, None]
+    return round_f16(w64.permute(0, 2, 3, 1).reshape(w.shape[0], -1)), shift.float().contiguous()
+
+
+def pack_concat_f16(w, bn):
+    """pack_concat for cmt_img_concat1x1_f16 -> (fp16 [Cout, K] in the concatenation's channel order, fp32 shift)"""
+    if not isinstance(bn, (list, tuple)) or len(bn) != 5:
+        raise ValueError("bn must be (weight, bias, running_mean, running_var, eps)")
+    if w.dim() != 4 or tuple(w.shape[2:]) != (1, 1):
+        raise ValueError(f"expected a (Cout, Cin, 1, 1) conv weight, got {tuple(w.shape)}")
+    scale, shift = fold_bn(*bn)
+    w64 = w.detach().double().reshape(w.shape[0], w.shape[1]) * scale[:, None]
+    return round_f16(w64), shift.float().contiguous()
+
+
+def _rows16(name, t, rows, C):
+    if t.dtype != torch.float16 or t.dim() != 2 or t.shape[1] != C or t.shape[0] < rows or not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous fp16 rows [>= {rows}, {C}], got {t.dtype} {tuple(t.shape)}")
+
+
+def stem_f16(x, W16, shift, *, Cout, relu=True, out=None, range_flag=None):
+    """cmt_img_stem_f16: the 3 x 3 / stride 2 / pad 1 conv of the fp32 NCHW image [B, Cin <= 3, H, W] (a strided
+    batch axis is taken as it is) -> fp16 rows [B*Ho*Wo, Cout] (rows beyond stay untouched)"""
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise ValueError("x must be an fp32 [B, C, H, W] image")
+    B, Cin, H, W = (int(s) for s in x.shape)
+    if min(B, H, W) <= 0 or not 1 <= Cin <= 3 or Cout <= 0 or Cout % 32:
+        raise ValueError(f"a non-empty image with 1 <= Cin <= 3 and Cout % 32 == 0 required, got {tuple(x.shape)} "
+                         f"and Cout {Cout}")
+    bstride = int(x.stride(0)) if B > 1 else Cin * H * W
+    if tuple(x.stride()[1:]) != (H * W, W, 1) or bstride < Cin * H * W:
+        raise ValueError("every image of x must be contiguous [C, H, W] at a batch stride >= C*H*W")
+    if B * H * W >= 2 ** 31:
+        raise ValueError("B*H*W must be below 2^31")
+    Ho, Wo = out_hw(H, W, 2)
+    _rows16("W16", W16, Cout, STEM_K)
+    if W16.shape[0] != Cout:
+        raise ValueError(f"W16 must hold {Cout} rows, got {W16.shape[0]}")
+    _shift(shift, Cout)
+    _flag(range_flag)
+    if out is not None:
+        _rows16("out", out, B * Ho * Wo, Cout)
+    _dev(x, W16, shift, out, range_flag)
+    Y = out if out is not None else torch.empty((B * Ho * Wo, Cout), dtype=torch.float16, device=x.device)
+    a = N.ImgStemArgs()
+    a.B, a.H, a.W, a.Cin, a.Cout, a.relu = B, H, W, Cin, Cout, int(bool(relu))
+    a.X, a.x_bstride, a.Wt, a.shift = _p(x), bstride, _p(W16), _p(shift)
+    a.Y, a.ldy, a.range_flag = _p(Y), Cout, _p(range_flag)
+    _check(lib().cmt_img_stem_f16(ctypes.byref(a), _stream()), "cmt_img_stem_f16")
+    return Y
+
+
+def _ld16(name, t, rows, C):
+    """fp16 rows [>= rows, C], possibly a column slice of a wider row buffer -> the leading dimension"""
+    if t.dtype != torch.float16 or t.dim() != 2 or t.shape[1] != C or t.shape[0] < rows:
+        raise ValueError(f"{name} must be fp16 rows [>= {rows}, {C}], got {t.dtype} {tuple(t.shape)}")
+    ld = int(t.stride(0)) if t.shape[0] > 1 else max(int(t.stride(0)), C)
+    if t.stride(1) != 1 or ld < C or ld % 8:
+        raise ValueError(f"{name}: a row must be C contiguous words at a leading dimension >= C, % 8; got strides "
+                         f"{tuple(t.stride())}")
+    return ld
+
+
+def conv3x3_f16(X, W16, shift, *, B, H, W, Cin, Cout, stride, relu=True, out=None, range_flag=None, nb=0):
+    """cmt_img_conv3x3_f16: fp16 rows [B*H*W, Cin] -> fp16 rows [B*Ho*Wo, Cout] (rows beyond stay untouched);
+    Cin % 32 == 0, Cout % 32 == 0, Cout <= 256, any width.  X and out may be column slices of wider row buffers
+    (leading dimension % 8).  ``nb`` as in conv3x3: the result does not depend on it."""
+    if nb < 0 or (nb and Cout > 0 and (Cout // 32) % nb):
+        raise ValueError(f"nb must be 0 or a divisor of Cout / 32 = {Cout // 32}, got {nb}")
+    if min(B, H, W) <= 0:
+        raise ValueError(f"B, H and W must be positive, got {(B, H, W)}")
+    if stride not in (1, 2):
+        raise ValueError(f"stride must be 1 or 2, got {stride}")
+    if Cin <= 0 or Cin % 32 or Cout <= 0 or Cout % 32 or Cout > 256:
+        raise ValueError(f"Cin and Cout must be multiples of 32, Cout at most 256, got {Cin} and {Cout}")
+    if B * H * W >= 2 ** 31:
+        raise ValueError("B*H*W must be below 2^31")
+    Ho, Wo = out_hw(H, W, stride)
+    ldx = _ld16("X", X, B * H * W, Cin)
+    _rows16("W16", W16, Cout, 9 * Cin)
+    if W16.shape[0] != Cout:
+        raise ValueError(f"W16 must hold {Cout} rows, got {W16.shape[0]}")
+    _shift(shift, Cout)
+    _flag(range_flag)
+    ldy = Cout if out is None else _ld16("out", out, B * Ho * Wo, Cout)
+    _dev(X, W16, shift, out, range_flag)
+    Y = out if out is not None else torch.empty((B * Ho * Wo, Cout), dtype=torch.float16, device=X.device)
+    a = N.ImgConvArgs()
+    a.B, a.H, a.W, a.Cin, a.Cout, a.stride, a.relu, a.nb = B, H, W, Cin, Cout, stride, int(bool(relu)), nb
+    a.X, a.ldx, a.Wt, a.ldw, a.shift = _p(X), ldx, _p(W16), 9 * Cin, _p(shift)
+    a.Y, a.ldy, a.range_flag = _p(Y), ldy, _p(range_flag)
+    _check(lib().cmt_img_conv3x3_f16(ctypes.byref(a), _stream()), "cmt_img_conv3x3_f16")
+    return Y
+
+
+def concat1x1_f16(sources, W16, shift, *, B, HW, Cout, relu=True, out=None, part=None, range_flag=None):
+    """cmt_img_concat1x1_f16: the 1 x 1 conv of the channel concatenation of up to 8 fp16 ``sources`` ([B*HW, C_s]
+    each, possibly a column slice of a wider row buffer) -> fp16 rows [B*HW, Cout].  ``part`` as in concat1x1: the
+    fp32 per-tile column sums of the fp16 values as stored.  Returns (rows, part)."""
+    sources = list(sources)
+    if not 1 <= len(sources) <= MAX_SRC:
+        raise ValueError(f"1 to {MAX_SRC} sources required, got {len(sources)}")
+    _positive(B=B, HW=HW)
+    if Cout <= 0 or Cout % 128:
+        raise ValueError(f"Cout must be a positive multiple of 128, got {Cout}")
+    if B * HW >= 2 ** 31 or B > 65535:
+        raise ValueError("B*HW must be below 2^31 and B at most 65535")
+    dims = []
+    for i, t in enumerate(sources):
+        C = int(t.shape[1]) if torch.is_tensor(t) and t.dim() == 2 else 0
+        if C <= 0 or C % 32:
+            raise ValueError(f"source {i} must be fp16 rows [>= {B * HW}, C] with C a positive multiple of 32, got "
+                             f"{tuple(t.shape) if torch.is_tensor(t) else type(t)}")
+        dims.append((C, _ld16(f"source {i}", t, B * HW, C)))
+    K = sum(c for c, _ in dims)
+    _rows16("W16", W16, Cout, K)
+    if W16.shape[0] != Cout:
+        raise ValueError(f"W16 must hold {Cout} rows, got {W16.shape[0]}")
+    _shift(shift, Cout)
+    _flag(range_flag)
+    if out is not None:
+        _rows16("out", out, B * HW, Cout)
+    tiles = concat_tiles(HW)
+    if part is not None and part is not True:
+        _f32("part", part, (B, tiles, Cout))
+    _dev(*sources, W16, shift, out, None if part is True else part, range_flag)
+    dev = sources[0].device
+    Y = out if out is not None else torch.empty((B * HW, Cout), dtype=torch.float16, device=dev)
+    if part is True:
+        part = torch.empty((B, tiles, Cout), dtype=torch.float32, device=dev)
+    a = N.ImgConcatArgs()
+    a.B, a.HW, a.Cout, a.nsrc, a.relu = B, HW, Cout, len(sources), int(bool(relu))
+    for i, (t, (c, ld)) in enumerate(zip(sources, dims)):
+        a.C[i], a.X[i], a.ldx[i] = c, t.data_ptr(), ld
+    a.Wt, a.ldw, a.shift = _p(W16), K, _p(shift)
+    a.Y, a.ldy, a.part, a.range_flag = _p(Y), Cout, _p(part), _p(range_flag)
+    _check(lib().cmt_img_concat1x1_f16(ctypes.byref(a), _stream()), "cmt_img_concat1x1_f16")
+    return Y, part
+
+
+def ese_apply_f16(X, gate, *, B, HW, C, identity=None, out=None, range_flag=None):
+    """cmt_img_ese_apply_f16: fp16 rows x [B*HW, C] times gate [B, C] (plus the fp16 rows ``identity``), in fp32,
+    rounded once -> fp16 rows; ``out`` may be X (in place)"""
+    _positive(B=B, HW=HW)
+    if C <= 0 or C % 8:
+        raise ValueError(f"C must be a positive multiple of 8, got {C}")
+    if B * HW >= 2 ** 31:
+        raise ValueError("B*HW must be below 2^31")
+    _rows16("X", X, B * HW, C)
+    _f32("gate", gate, (B, C))
+    if identity is not None:
+        _rows16("identity", identity, B * HW, C)
+    if out is not None:
+        _rows16("out", out, B * HW, C)
+    _flag(range_flag)
+    _dev(X, gate, identity, out, range_flag)
+    Y = out if out is not None else torch.empty((B * HW, C), dtype=torch.float16, device=X.device)
+    a = N.ImgApplyArgs()
+    a.B, a.HW, a.C = B, HW, C
+    a.X, a.ldx, a.gate, a.R, a.ldr = _p(X), C, _p(gate), _p(identity), C
+    a.Y, a.ldy, a.range_flag = _p(Y), C, _p(range_flag)
+    _check(lib().cmt_img_ese_apply_f16(ctypes.byref(a), _stream()), "cmt_img_ese_apply_f16")
+    return Y
+
+
+def maxpool_f16(X, *, B, H, W, C, out=None):
+    """cmt_img_maxpool_f16: 3 x 3 / stride 2 / ceil-mode / no-pad max, fp16 rows [B*H*W, C] -> [B*Ho*Wo, C] with
+    (Ho, Wo) = pool_hw(H, W)"""
+    _positive(B=B)
+    Ho, Wo = pool_hw(H, W)
+    if C <= 0 or C % 8:
+        raise ValueError(f"C must be a positive multiple of 8, got {C}")
+    if B * H * W >= 2 ** 31:
+        raise ValueError("B*H*W must be below 2^31")
+    _rows16("X", X, B * H * W, C)
+    if out is not None:
+        _rows16("out", out, B * Ho * Wo, C)
+    _dev(X, out)
+    Y = out if out is not None else torch.empty((B * Ho * Wo, C), dtype=torch.float16, device=X.device)
+    a = N.ImgPoolArgs()
+    a.B, a.H, a.W, a.C = B, H, W, C
+    a.X, a.ldx, a.Y, a.ldy = _p(X), C, _p(Y), C
+    _check(lib().cmt_img_maxpool_f16(ctypes.byref(a), _stream()), "cmt_img_maxpool_f16")
     return Y

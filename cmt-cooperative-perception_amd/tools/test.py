@@ -68,6 +68,9 @@ def parse_args(argv=None):
                    help="camera frame size as loaded, for --detector (default 900 1600)")
     p.add_argument("--points", type=int, default=1000, help="synthetic points per frame and agent")
     p.add_argument("--precision", default="bf16", choices=["bf16", "fp16", "ref"], help="compute policy")
+    p.add_argument("--img-precision", default=None, choices=["ref", "fp16"],
+                   help="arithmetic of the image backbone (--detector): three-pass split-f16 or one-pass fp16; "
+                        "default: the process setting (CMT_IMG_PRECISION, else ref)")
     p.add_argument("--bbox-classes", nargs="+", type=int, default=None, help="keep these labels (OpenLABEL)")
     p.add_argument("--bbox-score", type=float, default=None, help="minimum score (OpenLABEL)")
     p.add_argument("--seed", type=int, default=0, help="random seed")
@@ -243,12 +246,17 @@ def main(argv=None):
     else:
         device = torch.device("cuda", args.gpu_id)
     torch.cuda.set_device(device)
+    from projects.mmdet3d_plugin import native_img
     prev = get_precision()
     set_precision(args.precision)
+    prev_img = native_img.img_precision()
+    if args.img_precision is not None:
+        native_img.set_img_precision(args.img_precision)
     try:
         return _run(args, name, device, rank, world, distributed)
     finally:
         set_precision(prev)   # the CLI may run inside another process (tests)
+        native_img.set_img_precision(prev_img)
 
 
 def _run(args, name, device, rank, world, distributed):

@@ -14,7 +14,11 @@ cmt_img_prepare is also timed against the same operation written with torch ops 
 float, sub, mul, F.pad), in alternating windows of --iters calls, and its bytes per second over the bytes it
 must move (source crop once, destination once).
 
-    python dev/detector_probe.py [--points 300000] [--repeats 20] [--warmup 3] [--iters 20] [--seed 0] [--out FILE]
+``--img-precision`` (default ``ref``) is the image backbone's arithmetic (native_img.set_img_precision): ``fp16``
+runs VoVNet on the one-pass fp16 kernels; everything else is unchanged.
+
+    python dev/detector_probe.py [--img-precision ref|fp16] [--points 300000] [--repeats 20] [--warmup 3]
+                                 [--iters 20] [--seed 0] [--out FILE]
 
 Needs a HIP device and the built library; there is no CPU path.
 """
@@ -61,6 +65,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--img-precision", choices=("ref", "fp16"), default="ref")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -76,7 +81,8 @@ def main():
         print(s, flush=True)
         lines.append(s)
 
-    say(f"device {torch.cuda.get_device_name(0)}; seed {args.seed}; frames {FRAME[0]} x {FRAME[1]} uint8, "
+    NI.set_img_precision(args.img_precision)
+    say(f"device {torch.cuda.get_device_name(0)}; seed {args.seed}; image backbone precision {args.img_precision!r}; frames {FRAME[0]} x {FRAME[1]} uint8, "
         f"{args.points} points per cloud; per stage: median of {args.repeats} single calls after {args.warmup} "
         "warm-up (min .. max), device events, ms")
     _, crop = NI.test_crop(FRAME, (640, 1600))

@@ -16,7 +16,13 @@ Steps (``--step``; run each under its own time limit, e.g. ``timeout -k 10 600 p
             tests/test_gpu_vov.py's, against float64)
 MIOpen picks its algorithms on first use, so every torch step is warmed before it is timed.
 
-    python dev/img_backbone_probe.py --step forward [--iters 2] [--warmup 2] [--repeats 5] [--seed 0] [--out FILE]
+``--precision`` (default ``ref``): the backbone's arithmetic (native_img.set_img_precision).  ``fp16`` runs ``kinds``
+under the one-pass policy; ``both`` makes ``forward`` alternate windows of 'ref', 'fp16' and torch in one session, and
+``layers`` time cmt_img_conv3x3_f16 (the library's nb and every divisor) beside the three-pass kernel on the same
+values rounded to fp16.
+
+    python dev/img_backbone_probe.py --step forward [--precision both] [--iters 2] [--warmup 2] [--repeats 5]
+                                     [--seed 0] [--out FILE]
 
 ``--out`` appends.  Needs a HIP device and the built library; there is no CPU path.
 """
@@ -137,6 +143,7 @@ def ms(t):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--step", choices=("kinds", "layers", "forward"), required=True)
+    ap.add_argument("--precision", choices=("ref", "fp16", "both"), default="ref")
     ap.add_argument("--iters", type=int, default=2)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--repeats", type=int, default=5)
@@ -160,12 +167,18 @@ def main():
 
     m = seed(build_backbone(CFG), args.seed).eval().to(dev)
     x = torch.randn(SHAPE, generator=torch.Generator().manual_seed(args.seed + 1)).to(dev)
-    say(f"[{args.step}] device {torch.cuda.get_device_name(0)}; V-99-eSE, seed {args.seed}; input {SHAPE}; median of "
+    if args.step == "kinds" and args.precision == "both":
+        raise SystemExit("--step kinds takes one arithmetic per run: --precision ref or fp16")
+    say(f"[{args.step}, precision {args.precision}] device {torch.cuda.get_device_name(0)}; V-99-eSE, seed {args.seed}; input {SHAPE}; median of "
         f"{args.repeats} windows of {args.iters} after {args.warmup} warm-up (min .. max), device events")
 
     if args.step == "kinds":
-        names = dict(stem=NI, conv3x3=NI, conv3x3_gemm=NI, concat1x1=NI, ese_gate=NI, ese_apply=NI, maxpool=NI,
-                     rows_to_nchw=NF)
+        f16 = args.precision == "fp16"
+        NI.set_img_precision(args.precision)
+        names = dict(stem_f16=NI, conv3x3_f16=NI, concat1x1_f16=NI, ese_gate=NI, ese_apply_f16=NI, maxpool_f16=NI,
+                     rows_to_nchw_f16=NF) if f16 else \
+            dict(stem=NI, conv3x3=NI, conv3x3_gemm=NI, concat1x1=NI, ese_gate=NI, ese_apply=NI, maxpool=NI, rows_to_nchw=NF)
+        osa_name = "_osa_f16" if f16 else "_osa"
         real = {k: getattr(mod, k) for k, mod in names.items()}
         events, stage = [], ["stem"]
 
@@ -176,18 +189,18 @@ def main():
                 y = real[kind](*a, **kw)
                 t1.record()
                 shape = (kw["Cin"], kw["Cout"], kw.get("stride", 1), kw["B"], kw["H"], kw["W"]) \
-                    if kind in ("conv3x3", "conv3x3_gemm") else None
+                    if kind in ("conv3x3", "conv3x3_gemm", "conv3x3_f16") else None
                 events.append((kind, stage[0], shape, t0, t1))
                 return y
             return f
 
-        real_osa = m._osa
+        real_osa = getattr(m, osa_name)
 
         def osa(name, *a, **kw):
             stage[0] = "stage" + name[3]
             return real_osa(name, *a, **kw)
 
-        m._osa = osa
+        setattr(m, osa_name, osa)
         for k, mod in names.items():
             setattr(mod, k, rec(k))
         runs = []
@@ -202,7 +215,7 @@ def main():
         finally:
             for k, mod in names.items():
                 setattr(mod, k, real[k])
-            m._osa = real_osa
+            setattr(m, osa_name, real_osa)
         m.check_input_range()
 
         def med(select):
@@ -256,6 +269,29 @@ def main():
 
             # the library's own choice of column blocks per workgroup (nb = 0) beside every divisor of Cout / 32
             divs = [d for d in range(1, cout // 32 + 1) if (cout // 32) % d == 0]
+            if args.precision != "ref":
+                # the one-pass kernel on the same values rounded to fp16, in the same alternating windows as the
+                # three-pass kernel
+                one = torch.ones(cout, dtype=torch.float64, device=dev)
+                w16, shift16 = NI.pack_conv3x3_f16(w, [one, bias.double(), torch.zeros_like(one), one, 0.0])
+                rows16 = xs.permute(0, 2, 3, 1).reshape(-1, cin).half().contiguous()
+                out16 = torch.empty((B * ho * wo, cout), dtype=torch.float16, device=dev)
+
+                def run16(nb=0):
+                    return NI.conv3x3_f16(rows16, w16, shift16, B=B, H=H, W=W, Cin=cin, Cout=cout, stride=stride,
+                                          out=out16, nb=nb)
+
+                with torch.no_grad():
+                    res = timed([run, run16] + [lambda d=d: run16(d) for d in divs], args.iters, args.warmup, args.repeats)
+                    ref = F.relu(F.conv2d(xs, w, bias, stride, 1))
+                d16 = (NF.rows_to_nchw_f16(out16, (B, cout, ho, wo)) - ref).abs().max().item() / ref.abs().max().item()
+                flop = 2.0 * B * ho * wo * 9 * cin * cout
+                say(f"  {str((cin, cout, stride, H, W)):>40} {flop * 1e-9:7.1f} three-pass {ms(res[0])} ms {flop / res[0][0] * 1e-12:6.1f} "
+                    f"TFLOP/s | one-pass {ms(res[1])} ms {flop / res[1][0] * 1e-12:6.1f} TFLOP/s | one/three "
+                    f"{res[1][0] / res[0][0]:.2f} (rel. difference to torch fp32 {d16:.1e}; one-pass by nb: " +
+                    ", ".join(f"{q} {t[0] * 1e3:.3f}" for q, t in zip(divs, res[2:])) + ")")
+                del xs, rows, out, ref, rows16, out16
+                continue
             # cmt_gemm's CMT_A_CONV3X3 pair-row path takes the stride-1 layers with Cout % 64 == 0
             gemm_ok = stride == 1 and cout % 64 == 0 and cin % 64 == 0
             out_g = torch.empty_like(out) if gemm_ok else None
@@ -278,7 +314,23 @@ def main():
 
     else:
         chain = TorchChain(m)
-        tn, tt = timed([lambda: m(x), lambda: chain(x)], args.iters, args.warmup, args.repeats)
+
+        def under(mode):
+            def f():
+                NI.set_img_precision(mode)
+                return m(x)
+            return f
+
+        if args.precision == "both":
+            tr, tn, tt = timed([under("ref"), under("fp16"), lambda: chain(x)], args.iters, args.warmup, args.repeats)
+            say(f"whole forward (launches and allocations included), alternating windows: 'ref' {ms(tr)} ms, 'fp16' "
+                f"{ms(tn)} ms, torch fp32 {ms(tt)} ms; fp16/ref {tn[0] / tr[0]:.3f}, ref/torch {tr[0] / tt[0]:.2f}, "
+                f"fp16/torch {tn[0] / tt[0]:.2f}; windows apart: {tn[2] < tr[1]}")
+            say("below: 'fp16' against the torch fp32 chain")
+            NI.set_img_precision("fp16")
+        else:
+            NI.set_img_precision(args.precision)
+            tn, tt = timed([lambda: m(x), lambda: chain(x)], args.iters, args.warmup, args.repeats)
         say(f"whole forward (launches and allocations included): native {ms(tn)} ms, torch fp32 {ms(tt)} ms, "
             f"native/torch {tn[0] / tt[0]:.2f}")
         outs, ref = m(x), chain(x)

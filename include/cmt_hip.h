@@ -1109,6 +1109,55 @@ int cmt_img_ese_gate(const cmt_img_gate_args* args, void* stream);
 int cmt_img_ese_apply(const cmt_img_apply_args* args, void* stream);
 int cmt_img_maxpool(const cmt_img_pool_args* args, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Image backbone, the one-pass fp16 policy (additive to ABI 25): the launches above on
+ * plain fp16 rows.  A map between layers is NHWC [B*H*W][C] of IEEE fp16 (leading
+ * dimensions in 16-bit words, half of the pair rows'); weights are BN-folded and rounded
+ * once to fp16 by the caller, the shift stays fp32.  Every 16-k step is one
+ * v_mfma_f32_32x32x16_f16 with fp32 accumulation in fixed K order (the K order of the
+ * entries above); the epilogue adds the shift, applies the activation and rounds once to
+ * fp16 (RNE; |x| >= 65520 stores an infinity and raises range_flag).  fp16 subnormal
+ * operands are kept by the MFMA, not flushed.  One writer per element, no atomics on
+ * the data path, bitwise repeatable, no scratch, no call synchronises with the host.
+ * The argument structs are those above with the leading dimensions halved; range_flag as
+ * above.  cmt_img_ese_gate is shared: it reads fp32 partial sums either way.
+ *
+ * cmt_img_stem_f16: cmt_img_stem with every pixel rounded to fp16 on load and
+ *   Wt: fp16 [Cout][32], K = 9 Cin zero-padded to 32.  Requirements: 1 <= Cin <= 3,
+ *   Cout % 32 == 0, ldy >= Cout and % 8, Wt 16-byte aligned.
+ *
+ * cmt_img_conv3x3_f16: cmt_img_conv3x3 on fp16 rows; Wt: fp16 [Cout][9 Cin] tap-major
+ *   (k = (ky*3 + kx) * Cin + c).  Cin % 32 == 0, Cout % 32 == 0, Cout <= 256, stride 1 or
+ *   2, pad 1; ldx >= Cin, ldw >= 9 Cin, ldy >= Cout, all % 8; X and Wt 16-byte aligned.
+ *   W is staged 64 k per chunk; Cin % 64 == 32 ends every tap in a half chunk.  nb as in
+ *   cmt_img_conv3x3: 0 lets the entry choose, the result does not depend on it.
+ *
+ * cmt_img_concat1x1_f16: cmt_img_concat1x1 on up to CMT_IMG_MAX_SRC fp16 sources
+ *   [B*HW][C_s] with ldx_s >= C_s (a source may be a C_s-word column slice of a wider
+ *   row buffer); Wt: fp16 [Cout][K], K = sum C_s.  part (or NULL): fp32 [B][tiles][Cout],
+ *   the fp32 sums over the tile's pixels of the fp16 values as stored, in the fixed
+ *   order of cmt_img_concat1x1.  Requirements: 1 <= nsrc <= 8, C_s % 32 == 0,
+ *   Cout % 128 == 0, ldx_s >= C_s, ldw >= K, ldy >= Cout, all % 8; X_s and Wt 16-byte
+ *   aligned.
+ *
+ * cmt_img_ese_apply_f16: Y[(b, p)][c] = f16(x * gate[b][c] (+ r)), computed in fp32 and
+ *   rounded once; R NULL: no identity term.  Y may be X.  C % 8 == 0, ldx, ldr, ldy >= C
+ *   and % 8, X, R, Y and gate 16-byte aligned.
+ *
+ * cmt_img_maxpool_f16: cmt_img_maxpool's windows on fp16 values: the winning element is
+ *   copied unchanged, the first of equal maxima in window order, a NaN wins.  H, W >= 2,
+ *   C % 8 == 0, ldx, ldy >= C and % 8, X and Y 16-byte aligned.
+ *
+ * cmt_rows_to_nchw_f16 (fpn.hip): Y[b][c][p] = (float)X[b*HW + p][c], fp16 rows to
+ *   contiguous fp32 [B][C][HW] through the LDS transpose of cmt_rows_to_nchw.
+ *   C % 8 == 0, ldx >= C and % 8, X 16-byte aligned, HW arbitrary. */
+int cmt_img_stem_f16(const cmt_img_stem_args* args, void* stream);
+int cmt_img_conv3x3_f16(const cmt_img_conv_args* args, void* stream);
+int cmt_img_concat1x1_f16(const cmt_img_concat_args* args, void* stream);
+int cmt_img_ese_apply_f16(const cmt_img_apply_args* args, void* stream);
+int cmt_img_maxpool_f16(const cmt_img_pool_args* args, void* stream);
+int cmt_rows_to_nchw_f16(const cmt_rows_to_nchw_args* args, void* stream);
+
 /* ---- camera frames -> the image backbone's input (imgprep.hip; additive to ABI 25) ----------------
  * cmt_img_prepare: the test-time image pipeline of the reference (integer crop of
  * ResizeCropFlipImage at resize 1, NormalizeMultiviewImage, PadMultiViewImage) in one pass.
