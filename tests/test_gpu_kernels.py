@@ -476,6 +476,10 @@ def test_layernorm_fused_post(N, dev):
     assert (Y.cpu()[ok] - r1[ok]).abs().max().item() < 1e-4
     assert torch.isfinite(Y2.cpu()).all()
     assert (Y2.cpu()[ok] - r2[ok]).abs().max().item() < 1e-4
+    # the poisoned row: both LayerNorms are NaN, nan_to_num makes the second 0, then the maximum
+    assert not ok[7] and ok.sum() == rows - 1 and torch.isnan(Y.cpu()[7]).all()
+    assert torch.equal(Y2.cpu()[7], torch.maximum(torch.zeros(C), prev[7]))
+    assert torch.equal(Y2.cpu()[7], r2[7])
 
 
 @pytest.mark.parametrize("lp", [torch.float16, torch.bfloat16])
@@ -671,7 +675,13 @@ def test_chain_a(N, dev, dt, B, Nq, with_r):
         assert ey <= 2e-5 * y.abs().max().item(), ey
         assert eq <= 2 ** -10 * qref.abs().max().item(), eq
         return   # the split chains have the fragment-major (register) form only
-    assert ey < 2e-3
+    # Y is fp32 and upstream of any in-chain rounding: test_chain_b's measured rule -- 4 x the error of
+    # the same formula in float32 torch, never below 2e-5 of the scale
+    f = lambda t: t.float()
+    y32 = _ln64(f(val(X)) @ f(val(Wo)).T + f(bo) + (f(R) if R is not None else 0), f(lw), f(lb))
+    bound = max(4 * (y32.double() - y).abs().max().item(), 2e-5 * y.abs().max().item())
+    print(f"chain A ({B} x {Nq}) {dt}: Y err {ey:.2e} (bound {bound:.2e})")
+    assert ey <= bound, (ey, bound)
     rel = eq / qref.abs().max().item()
     assert rel < 1.5e-2, rel
     # fragment-major Wo (wo_frag: register-streamed out_proj, no LDS weight ring): the same
