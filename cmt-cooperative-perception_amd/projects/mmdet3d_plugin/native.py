@@ -254,6 +254,12 @@ class ImgPrepareArgs(ctypes.Structure):
                 ("mean", _flt * 3), ("inv_std", _flt * 3), ("src", _vp), ("dst", _vp)]
 
 
+class ImgResizeArgs(ctypes.Structure):
+    _fields_ = [("N", _int), ("Hs", _int), ("Ws", _int), ("to_rgb", _int), ("Hr", _int), ("Wr", _int),
+                ("x0", _int), ("y0", _int), ("w", _int), ("h", _int), ("Hp", _int), ("Wp", _int),
+                ("mean", _flt * 3), ("inv_std", _flt * 3), ("src", _vp), ("dst", _vp)]
+
+
 STRUCTS = {"gemm": GemmArgs, "attn": AttnArgs, "ln": LnArgs, "chain": ChainArgs, "gemm_ex": GemmExArgs,
            "attn_train": AttnTrainArgs, "ln_train": LnTrainArgs, "bn": BnArgs, "det_loss": DetLossArgs,
            "match_cost": MatchCostArgs, "adamw": AdamwArgs, "mlp2": Mlp2Args, "mlp2_affine": Mlp2AffineArgs, "lsap": LsapArgs,
@@ -261,7 +267,8 @@ STRUCTS = {"gemm": GemmArgs, "attn": AttnArgs, "ln": LnArgs, "chain": ChainArgs,
            "sparse_dense": SparseDenseArgs, "bev_conv": BevConvArgs, "bev_deblock": BevDeblockArgs,
            "fpn_lateral": FpnLateralArgs, "rows_to_nchw": RowsToNchwArgs,
            "img_stem": ImgStemArgs, "img_conv": ImgConvArgs, "img_concat": ImgConcatArgs, "img_gate": ImgGateArgs,
-           "img_apply": ImgApplyArgs, "img_pool": ImgPoolArgs, "img_prepare": ImgPrepareArgs}
+           "img_apply": ImgApplyArgs, "img_pool": ImgPoolArgs, "img_prepare": ImgPrepareArgs,
+           "img_resize": ImgResizeArgs}
 
 _LIB = None
 
@@ -387,6 +394,8 @@ def _load():
         "cmt_rows_to_nchw_f16": ([P(RowsToNchwArgs), _vp], _int),
         "cmt_img_prepare_args_size": ([], _i64),
         "cmt_img_prepare": ([P(ImgPrepareArgs), _vp], _int),
+        "cmt_img_resize_args_size": ([], _i64),
+        "cmt_img_resize_prepare": ([P(ImgResizeArgs), _vp], _int),
         "cmt_adamw_step": ([P(AdamwArgs), _vp], _int),
     }
     for name, (args, res) in sig.items():

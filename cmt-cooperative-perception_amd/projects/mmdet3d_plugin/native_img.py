@@ -16,7 +16,8 @@ from .native_fpn import pack_conv1x1
 
 __all__ = ["STEM_K", "CONCAT_TM", "MAX_SRC", "pack_stem", "pack_concat", "pool_hw", "concat_tiles", "stem", "conv3x3",
            "conv3x3_gemm", "concat1x1", "ese_gate", "ese_apply", "maxpool", "IMG_MEAN", "IMG_STD", "norm_constants",
-           "test_crop", "crop_lidar2img", "prepare_images", "set_img_precision", "img_precision", "round_f16",
+           "test_crop", "crop_lidar2img", "prepare_images", "resize_crop_plan", "resize_crop_lidar2img",
+           "image_plan_from_config", "set_img_precision", "img_precision", "round_f16",
            "pack_stem_f16", "pack_conv3x3_f16", "pack_concat_f16", "stem_f16", "conv3x3_f16", "concat1x1_f16",
            "ese_apply_f16", "maxpool_f16"]
 
@@ -42,31 +43,31 @@ def norm_constants(mean, std):
     return mean32, (1.0 / std32.astype(np.float64)).astype(np.float32)
 
 
-def test_crop(src_hw, final_dim, bot_pct_lim=(0.0, 0.0)):
-    """The test branch of ResizeCropFlipImage._sample_augmentation (transform_3d.py:446-455) for a source of
-    ``src_hw = (H, W)`` and ``final_dim = (fH, fW)`` -> (resize, crop) with crop = (x0, y0, x1, y1) in source
-    pixels.  Only resize == 1 (a pure integer crop) is built: anything else needs interpolation."""
-    H, W = (int(v) for v in src_hw)
+def resize_crop_plan(aug_hw, final_dim, bot_pct_lim=(0.0, 0.0)):
+    """The whole test branch of ResizeCropFlipImage[Coop]._sample_augmentation (transform_3d.py:449-455) for
+    ``aug_hw = (H, W)`` of the config's ida_aug_conf and ``final_dim = (fH, fW)`` -> (resize, (newW, newH), crop):
+    the frame is resized to (newW, newH), whatever its own size, and ``crop = (x0, y0, x1, y1)`` is in pixels of the
+    resized frame.  int() truncates as there.  H and W are the config's, not the frame's: a 1200 x 1920 TUMTraf
+    frame under H = 900, W = 1600 gets resize 1.0 and is still resampled to 1600 x 900."""
+    H, W = (int(v) for v in aug_hw)
     fH, fW = (int(v) for v in final_dim)
     if min(H, W, fH, fW) <= 0:
-        raise ValueError(f"positive sizes required, got src_hw {tuple(src_hw)}, final_dim {tuple(final_dim)}")
+        raise ValueError(f"positive sizes required, got aug_hw {tuple(aug_hw)}, final_dim {tuple(final_dim)}")
     resize = max(fH / H, fW / W)
-    if resize != 1.0:
-        raise NotImplementedError(f"test_crop: {(H, W)} -> {(fH, fW)} needs a resize by {resize:.6g}; only the "
-                                  "integer crop (resize 1) has a native path, interpolation is not built")
     new_w, new_h = int(W * resize), int(H * resize)
     crop_h = int((1 - float(np.mean(bot_pct_lim))) * new_h) - fH
     crop_w = int(max(0, new_w - fW) / 2)
-    return resize, (crop_w, crop_h, crop_w + fW, crop_h + fH)
+    return resize, (new_w, new_h), (crop_w, crop_h, crop_w + fW, crop_h + fH)
 
 
-test_crop.__test__ = False   # a host helper, not a test, whatever collects names starting with test_
-
-
-def crop_lidar2img(cam_intrinsic, lidar2cam, crop):
-    """lidar2img of the cropped image, in float64: the intrinsic's principal point moves by (-x0, -y0)
-    (transform_3d.py:373-378 and 420-431 with resize 1, no flip, no rotation), then intrinsic @ lidar2cam.
-    ``cam_intrinsic`` is 3 x 3 or 4 x 4, ``lidar2cam`` 4 x 4; the inputs are not modified."""
+def resize_crop_lidar2img(cam_intrinsic, lidar2cam, resize, crop):
+    """lidar2img of the resized and cropped image, in float64: rows 0-1 of the intrinsic are multiplied by
+    ``resize``, the principal point then moves by (-x0, -y0) (transform_3d.py:373-378 and 420-431, no flip, no
+    rotation), then intrinsic @ lidar2cam.  ``cam_intrinsic`` is 3 x 3 or 4 x 4, ``lidar2cam`` 4 x 4; the inputs are
+    not modified.  ``resize`` is the scalar of resize_crop_plan, as in the reference, also where the pixels were
+    scaled by other, anisotropic factors because the frame is not the config's H x W (TUMTraf: pixels x (0.8333,
+    0.75), intrinsics x 1.0).  That is the reference's behaviour, kept so that its checkpoints see the projection
+    they were trained with."""
     K = np.array(cam_intrinsic, dtype=np.float64)
     E = np.array(lidar2cam, dtype=np.float64)
     if K.shape == (3, 3):
@@ -75,28 +76,94 @@ def crop_lidar2img(cam_intrinsic, lidar2cam, crop):
         K = K4
     if K.shape != (4, 4) or E.shape != (4, 4):
         raise ValueError(f"cam_intrinsic must be 3 x 3 or 4 x 4 and lidar2cam 4 x 4, got {K.shape} and {E.shape}")
+    K[:2] *= float(resize)
     K[0, 2] -= float(crop[0])
     K[1, 2] -= float(crop[1])
     return K @ E
 
 
-def prepare_images(frames, crop=None, mean=IMG_MEAN, std=IMG_STD, to_rgb=False, size_divisor=32, out=None, size=None):
+def test_crop(src_hw, final_dim, bot_pct_lim=(0.0, 0.0)):
+    """resize_crop_plan for a frame that already has the config's size ``src_hw = (H, W)`` -> (resize, crop) with
+    crop = (x0, y0, x1, y1) in source pixels.  Only resize == 1 (a pure integer crop) is accepted here;
+    resize_crop_plan and prepare_images(resize_dims=...) cover every other case."""
+    resize, _, crop = resize_crop_plan(src_hw, final_dim, bot_pct_lim)
+    if resize != 1.0:
+        raise NotImplementedError(f"test_crop: {tuple(src_hw)} -> {tuple(final_dim)} needs a resize by {resize:.6g}: use "
+                                  "resize_crop_plan and prepare_images(resize_dims=...)")
+    return resize, crop
+
+
+test_crop.__test__ = False   # a host helper, not a test, whatever collects names starting with test_
+
+
+def crop_lidar2img(cam_intrinsic, lidar2cam, crop):
+    """resize_crop_lidar2img at resize 1: the principal point moves by (-x0, -y0), then intrinsic @ lidar2cam"""
+    return resize_crop_lidar2img(cam_intrinsic, lidar2cam, 1.0, crop)
+
+
+def _pipeline_steps(steps):
+    for st in steps or []:
+        if isinstance(st, dict):
+            yield st
+            yield from _pipeline_steps(st.get("transforms"))
+
+
+def image_plan_from_config(cfg):
+    """The image preparation of a config dict (config.load_config): the ResizeCropFlipImage[Coop]
+    (training=False), NormalizeMultiviewImage[Coop] and PadMultiViewImage[Coop] steps of ``data.test.pipeline``,
+    looked for inside MultiScaleFlipAug3D's ``transforms`` too -> dict(resize, resize_dims, crop, mean, std, to_rgb,
+    size_divisor), the first three from resize_crop_plan; None for a pipeline without the resize step (LiDAR only)."""
+    steps = list(_pipeline_steps(cfg["data"]["test"]["pipeline"]))
+
+    def find(kind):
+        hits = [st for st in steps if st.get("type") in (kind, kind + "Coop")]
+        return hits[0] if hits else None
+
+    rcf = find("ResizeCropFlipImage")
+    if rcf is None:
+        return None
+    if rcf.get("training", True):
+        raise ValueError("the test pipeline's ResizeCropFlipImage step has training=True")
+    aug = rcf["data_aug_conf"]
+    resize, dims, crop = resize_crop_plan((aug["H"], aug["W"]), aug["final_dim"], aug.get("bot_pct_lim", (0.0, 0.0)))
+    norm, pad = find("NormalizeMultiviewImage"), find("PadMultiViewImage")
+    if norm is None or pad is None:
+        raise ValueError("the test pipeline resizes images but has no NormalizeMultiviewImage / PadMultiViewImage step")
+    if pad.get("size_divisor") is None:
+        raise ValueError("PadMultiViewImage with a fixed size is not supported, only size_divisor")
+    return dict(resize=resize, resize_dims=dims, crop=crop, mean=tuple(norm["mean"]), std=tuple(norm["std"]),
+                to_rgb=bool(norm.get("to_rgb", True)), size_divisor=int(pad["size_divisor"]))
+
+
+def prepare_images(frames, crop=None, mean=IMG_MEAN, std=IMG_STD, to_rgb=False, size_divisor=32, out=None, size=None,
+                   resize_dims=None):
     """cmt_img_prepare: uint8 frames [N, Hs, Ws, 3] (interleaved, as cv2 loads them) -> the backbone's input fp32
     [N, 3, Hp, Wp]: crop, normalise, zero-pad, HWC -> CHW in one kernel.  ``crop`` = (x0, y0, x1, y1) in source
     pixels as test_crop returns it (None: the whole frame); crop pixels outside the source count as byte 0
     before normalisation.  (Hp, Wp) is the crop size rounded up to ``size_divisor``, or the explicit
     ``size = (Hp, Wp)``; the pad is 0 after normalisation.  ``mean`` / ``std`` are indexed by output channel,
-    which reads source channel 2 - c when ``to_rgb``."""
+    which reads source channel 2 - c when ``to_rgb``.
+
+    ``resize_dims = (Wr, Hr)`` (as resize_crop_plan returns it) selects cmt_img_resize_prepare: the frame is first
+    resampled to Hr x Wr with the 8-bit fixed-point bilinear of include/cmt_hip.h, in the same kernel; ``crop`` is
+    then in pixels of the resized frame and defaults to all of it."""
     if not torch.is_tensor(frames) or frames.dtype != torch.uint8:
         raise ValueError(f"frames must be a uint8 tensor, got {frames.dtype if torch.is_tensor(frames) else type(frames)}")
     if frames.dim() != 4 or frames.shape[3] != 3 or min(frames.shape) <= 0:
         raise ValueError(f"frames must be a non-empty [N, H, W, 3] tensor, got {tuple(frames.shape)}")
     if not frames.is_contiguous():
         raise ValueError("frames must be contiguous (interleaved HWC rows)")
-    if not frames.is_cuda:
-        raise ValueError("frames must live on a HIP device (no CPU path)")
     n, Hs, Ws = (int(s) for s in frames.shape[:3])
-    x0, y0, x1, y1 = (0, 0, Ws, Hs) if crop is None else (int(v) for v in crop)
+    Wr, Hr = Ws, Hs
+    if resize_dims is not None:
+        if len(tuple(resize_dims)) != 2:
+            raise ValueError(f"resize_dims must be (Wr, Hr), got {resize_dims!r}")
+        Wr, Hr = (int(v) for v in resize_dims)
+        if Wr <= 0 or Hr <= 0 or max(Wr, Hr) >= 2 ** 30:
+            raise ValueError(f"resize_dims must be positive and below 2^30, got {(Wr, Hr)}")
+    elif not frames.is_cuda:
+        raise ValueError("frames must live on a HIP device (no CPU path)")
+    x0, y0, x1, y1 = (0, 0, Wr, Hr) if crop is None else (int(v) for v in crop)
     w, h = x1 - x0, y1 - y0
     if w <= 0 or h <= 0:
         raise ValueError(f"empty crop {(x0, y0, x1, y1)}")
@@ -112,18 +179,24 @@ def prepare_images(frames, crop=None, mean=IMG_MEAN, std=IMG_STD, to_rgb=False, 
     if max(abs(x0), abs(y0), Hp, Wp) >= 2 ** 30 or n * Hp * ((Wp + 3) // 4) >= 2 ** 31:
         raise ValueError("crop or output size beyond the kernel's index range")
     mean32, inv32 = norm_constants(mean, std)
+    if not frames.is_cuda:
+        raise ValueError("frames must live on a HIP device (no CPU path)")
     if out is not None:
         _f32("out", out, (n, 3, Hp, Wp))
         if out.device != frames.device:
             raise ValueError("out must live on the frames' device")
     Y = out if out is not None else torch.empty((n, 3, Hp, Wp), dtype=torch.float32, device=frames.device)
-    a = N.ImgPrepareArgs()
+    a = N.ImgPrepareArgs() if resize_dims is None else N.ImgResizeArgs()
     a.N, a.Hs, a.Ws, a.to_rgb = n, Hs, Ws, int(bool(to_rgb))
     a.x0, a.y0, a.w, a.h, a.Hp, a.Wp = x0, y0, w, h, Hp, Wp
     for c in range(3):
         a.mean[c], a.inv_std[c] = float(mean32[c]), float(inv32[c])
     a.src, a.dst = _p(frames), _p(Y)
-    _check(lib().cmt_img_prepare(ctypes.byref(a), _stream()), "cmt_img_prepare")
+    if resize_dims is None:
+        _check(lib().cmt_img_prepare(ctypes.byref(a), _stream()), "cmt_img_prepare")
+    else:
+        a.Hr, a.Wr = Hr, Wr
+        _check(lib().cmt_img_resize_prepare(ctypes.byref(a), _stream()), "cmt_img_resize_prepare")
     return Y
 
 

@@ -14,11 +14,17 @@ cmt_img_prepare is also timed against the same operation written with torch ops 
 float, sub, mul, F.pad), in alternating windows of --iters calls, and its bytes per second over the bytes it
 must move (source crop once, destination once).
 
+cmt_img_resize_prepare (the bilinear resize fused into the preparation) is timed the same way at the TUMTraf coop
+frame, [4, 1200, 1920, 3] resized to 1600 x 900, rows 260..900 -> [4, 3, 640, 1600], against uint8 -> float, permute,
+F.interpolate(mode='bilinear', align_corners=False), slice, normalise and pad.  The torch chain interpolates in
+float arithmetic, so the two results are compared within 1 grey level, not bit for bit.  ``--only resize`` runs this
+section alone and ``--resize-out FILE`` writes it to a file of its own.
+
 ``--img-precision`` (default ``ref``) is the image backbone's arithmetic (native_img.set_img_precision): ``fp16``
 runs VoVNet on the one-pass fp16 kernels; everything else is unchanged.
 
     python dev/detector_probe.py [--img-precision ref|fp16] [--points 300000] [--repeats 20] [--warmup 3]
-                                 [--iters 20] [--seed 0] [--out FILE]
+                                 [--iters 20] [--seed 0] [--out FILE] [--only resize] [--resize-out FILE]
 
 Needs a HIP device and the built library; there is no CPU path.
 """
@@ -67,6 +73,8 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--img-precision", choices=("ref", "fp16"), default="ref")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--only", choices=("resize",), default=None, help="run this section alone")
+    ap.add_argument("--resize-out", default=None, help="write the cmt_img_resize_prepare section to this file")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("detector_probe needs a HIP device (timings are never taken on the CPU)")
@@ -186,6 +194,9 @@ def main():
             model.check_input_range()
         return inputs[0][0]
 
+    if args.only == "resize":
+        resize_section(args, dev, say, lines)
+        return
     frames = frame("cmt_fusion_nus")
     frame("cmtcoop_fusion_tumtraf")
 
@@ -219,11 +230,66 @@ def main():
         f"{'bit-equal' if same else 'NOT bit-equal'}")
     say(f"{'cmt_img_prepare':>22} {fmt(tn)}   {nbytes * 1e-6:.1f} MB moved -> {nbytes / (tn[0] * 1e-3) * 1e-12:.2f} TB/s")
     say(f"{'torch ops':>22} {fmt(tt)}   native / torch {tn[0] / tt[0]:.2f}")
+    resize_section(args, dev, say, lines)
+
+
+def resize_section(args, dev, say, lines):
+    """cmt_img_resize_prepare against the torch chain at the TUMTraf coop frame (1 + 3 cameras, 1200 x 1920)"""
+    from projects.mmdet3d_plugin import native_img as NI
+    from projects.mmdet3d_plugin import synthetic as S
+    first = len(lines)
+    mean32, inv32 = NI.norm_constants(NI.IMG_MEAN, NI.IMG_STD)
+    mean_t = torch.from_numpy(mean32).to(dev).view(1, 3, 1, 1)
+    inv_t = torch.from_numpy(inv32).to(dev).view(1, 3, 1, 1)
+    Hs, Ws = 1200, 1920
+    _, dims, crop = NI.resize_crop_plan(FRAME, (640, 1600))
+    x0, y0, x1, y1 = crop
+    frames = S.synthetic_frames(4, Hs, Ws, seed=args.seed + 5, device=dev)
+    # smooth frames as well: on noise every interpolator disagrees by its own rounding at every pixel
+    ramp = (torch.arange(Hs, device=dev)[:, None] * 3 + torch.arange(Ws, device=dev)[None, :] * 2) // 40
+    smooth = (ramp[None, :, :, None] + torch.arange(3, device=dev) * 20 + torch.arange(4, device=dev)[:, None, None, None] * 9)
+    smooth = (smooth % 256).to(torch.uint8).contiguous()
+    out = torch.empty((4, 3, y1 - y0, x1 - x0), dtype=torch.float32, device=dev)
+
+    def native_fn(src=frames):
+        return NI.prepare_images(src, crop=crop, resize_dims=dims, out=out)
+
+    def torch_fn(src=frames):
+        x = F.interpolate(src.permute(0, 3, 1, 2).float(), size=(dims[1], dims[0]), mode="bilinear", align_corners=False)
+        return F.pad(((x[:, :, y0:y1, x0:x1] - mean_t) * inv_t).contiguous(), (0, 0, 0, 0))
+
+    def grey_levels(src):
+        # normalised values back to grey levels: (v / inv + mean), so that the difference is in units of one byte step
+        a = native_fn(src).clone() / inv_t + mean_t
+        b = torch_fn(src) / inv_t + mean_t
+        return float((a - b).abs().max())
+
+    d_noise, d_smooth = grey_levels(frames), grey_levels(smooth)
+    for fn in (native_fn, torch_fn):
+        for _ in range(args.warmup):
+            fn()
+    torch.cuda.synchronize()
+    tn, tt = [], []
+    for _ in range(args.repeats):
+        tn.append(event_ms(lambda: [native_fn() for _ in range(args.iters)]) / args.iters)
+        tt.append(event_ms(lambda: [torch_fn() for _ in range(args.iters)]) / args.iters)
+    tn, tt = med(tn), med(tt)
+    # bytes the call must move: the source rows the window's taps reach, once, and the destination, once
+    rows = (y1 - y0) * Hs / dims[1] + 1
+    nbytes = int(4 * (rows * Ws * 3 + (y1 - y0) * (x1 - x0) * 3 * 4))
+    say(f"--- {torch.cuda.get_device_name(0)}: cmt_img_resize_prepare [4, {Hs}, {Ws}, 3] -> resize {dims[0]} x {dims[1]}, rows {y0}..{y1} -> "
+        f"[4, 3, {y1 - y0}, {x1 - x0}]: alternating windows of {args.iters} calls, median of {args.repeats} "
+        "(min .. max), ms per call")
+    say(f"largest difference from the torch chain (float bilinear): {d_noise:.3f} grey levels on uniform noise, "
+        f"{d_smooth:.3f} on a smooth ramp (expected within 1)")
+    say(f"{'cmt_img_resize_prepare':>22} {fmt(tn)}   {nbytes * 1e-6:.1f} MB moved -> {nbytes / (tn[0] * 1e-3) * 1e-12:.2f} TB/s")
+    say(f"{'torch ops':>22} {fmt(tt)}   native / torch {tn[0] / tt[0]:.2f}")
     say(f"peak device memory {torch.cuda.max_memory_allocated() / 2 ** 20:.0f} MiB")
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+    for path, text in ((args.out, lines), (args.resize_out, lines[first:])):
+        if path:
+            os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+            with open(path, "w") as f:
+                f.write("\n".join(text) + "\n")
 
 
 if __name__ == "__main__":

@@ -1181,6 +1181,41 @@ typedef struct cmt_img_prepare_args {
 int64_t cmt_img_prepare_args_size(void);
 int cmt_img_prepare(const cmt_img_prepare_args* args, void* stream);
 
+/* cmt_img_resize_prepare (additive to ABI 25): cmt_img_prepare with "source" replaced by "the source
+ * resized to Hr x Wr", i.e. ResizeCropFlipImage(training=False) at any resize_dims, then normalise
+ * and pad, in one launch.  Layouts, alignment rules, to_rgb, the pad and the limits are
+ * cmt_img_prepare's; additionally Hr, Wr > 0 and < 2^30.  The window (x0, y0, w, h) is in pixels of
+ * the resized image.  For y < h and x < w, with b the byte of RESIZED pixel (y0 + y, x0 + x),
+ * channel (to_rgb ? 2 - c : c), or 0 where that pixel lies outside [0, Hr) x [0, Wr):
+ *     dst[n][c][y][x] = fl32(fl32((float)b - mean[c]) * inv_std[c]);   0 for y >= h or x >= w.
+ * The resized byte is the 8-bit fixed-point bilinear sample written down here (a restatement from
+ * memory of OpenCV's plain C++ INTER_LINEAR path; THIS TEXT is the contract, agreement with a real
+ * cv2.resize has not been verified).  Per axis, source size S, resized size R, resized index d:
+ *     scale = (double)S / R;
+ *     f = (float)((d + 0.5) * scale - 0.5)   float64 multiply, then float64 subtract (no FMA), one
+ *                                            rounding to float32;
+ *     s = floor(f), t = f - s                float32;
+ *     horizontal axis only: s < 0 -> s = 0, t = 0;  s >= S - 1 -> s = S - 1, t = 0;
+ *     c1 = rint(t * 2048), c0 = rint((1.f - t) * 2048)    float32, round-half-even;
+ *     taps at clamp(s, 0, S - 1) and clamp(s + 1, 0, S - 1)   (the vertical axis only clamps).
+ * With (a0, a1) / (b0, b1) the horizontal / vertical coefficients, taps s, s' and rows r0, r1, per
+ * channel k in int32:
+ *     Hrow_r = src[r][s][k] * a0 + src[r][s'][k] * a1
+ *     byte   = (((b0 * (Hrow_r0 >> 4)) >> 16) + ((b1 * (Hrow_r1 >> 4)) >> 16) + 2) >> 2
+ * c0 + c1 == 2048 always, so constants are preserved, R == S reproduces the source and an exact
+ * 2 x downscale is the rounded mean of 4 pixels.  The call never synchronises and allocates nothing. */
+typedef struct cmt_img_resize_args {
+    int N, Hs, Ws, to_rgb;
+    int Hr, Wr;                                   /* the size the frame is resized to */
+    int x0, y0, w, h;                             /* crop window in pixels of the resized image */
+    int Hp, Wp;
+    float mean[3], inv_std[3];                    /* by destination channel */
+    const void* src;
+    void* dst;
+} cmt_img_resize_args;
+int64_t cmt_img_resize_args_size(void);
+int cmt_img_resize_prepare(const cmt_img_resize_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
