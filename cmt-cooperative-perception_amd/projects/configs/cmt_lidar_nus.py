@@ -11,3 +11,12 @@ head_type = 'CmtLidarHead'
 transformer_type = 'CmtLidarTransformer'
 final_kernel = 3
 post_center_range = [-61.2, -61.2, -10.0, 61.2, 61.2, 10.0]
+# The point steps of the reference's test pipeline (e.g. CMT_Nuscenes/lidar/cmt_lidar_voxel0075_cbgs.py:95-125), read by
+# native_pts.points_plan_from_config; the nuScenes test pipelines have no range filter.
+data = dict(test=dict(pipeline=[
+    dict(type='LoadPointsFromFile', coord_type='LIDAR', load_dim=5, use_dim=[0, 1, 2, 3, 4]),
+    dict(type='LoadPointsFromMultiSweeps', sweeps_num=10, use_dim=[0, 1, 2, 3, 4]),
+    dict(type='MultiScaleFlipAug3D', pts_scale_ratio=1, flip=False, transforms=[
+        dict(type='GlobalRotScaleTrans', rot_range=[0, 0], scale_ratio_range=[1.0, 1.0], translation_std=[0, 0, 0]),
+    ]),
+]))

@@ -14,6 +14,9 @@ called by hand.  Differences from the reference, all of scope:
   (``voxelize_batch``); any other encoder module is called on the padded voxels;
 * the batch size handed to the middle encoder is ``len(points)``, not ``coors[-1, 0] + 1`` (cmt.py:81): the
   same number unless the last sample has no voxel, and no host read;
+* a cloud may be the padded buffer of ``native_pts.prepare_points`` (kept rows first, NaN rows after them) as it
+  is: the voxelizer drops non-finite points and keeps input order, so the result equals the trimmed cloud's bit
+  for bit and the count never has to reach the host;
 * ``aug_test`` and ``show_results`` are not built.
 
 State-dict keys are the reference's: ``img_backbone.*``, ``img_neck.*``, ``pts_middle_encoder.*``,

@@ -260,6 +260,23 @@ class ImgResizeArgs(ctypes.Structure):
                 ("mean", _flt * 3), ("inv_std", _flt * 3), ("src", _vp), ("dst", _vp)]
 
 
+PTS_MAX_SEG = 16   # cmt_hip.h CMT_PTS_MAX_SEG
+
+
+class PtsSegment(ctypes.Structure):
+    _fields_ = [("rot", ctypes.c_double * 9), ("trans", ctypes.c_double * 3), ("has_sweep_xform", _int),
+                ("close_radius", _flt), ("time_col", _int), ("time_val", _flt)]
+
+
+class PtsPrepareArgs(ctypes.Structure):
+    _fields_ = [("n_total", _i64), ("S", _int), ("load_dim", _int), ("F_out", _int),
+                ("has_agent_xform", _int), ("has_range", _int), ("reserved", _int),
+                ("seg_start", _i64 * (PTS_MAX_SEG + 1)), ("use_dim", _int * 8),
+                ("rot32", _flt * 9), ("trans32", _flt * 3), ("range", _flt * 6),
+                ("seg", PtsSegment * PTS_MAX_SEG),
+                ("src", _vp), ("dst", _vp), ("count", _vp), ("workspace", _vp), ("workspace_bytes", _i64)]
+
+
 STRUCTS = {"gemm": GemmArgs, "attn": AttnArgs, "ln": LnArgs, "chain": ChainArgs, "gemm_ex": GemmExArgs,
            "attn_train": AttnTrainArgs, "ln_train": LnTrainArgs, "bn": BnArgs, "det_loss": DetLossArgs,
            "match_cost": MatchCostArgs, "adamw": AdamwArgs, "mlp2": Mlp2Args, "mlp2_affine": Mlp2AffineArgs, "lsap": LsapArgs,
@@ -268,7 +285,7 @@ STRUCTS = {"gemm": GemmArgs, "attn": AttnArgs, "ln": LnArgs, "chain": ChainArgs,
            "fpn_lateral": FpnLateralArgs, "rows_to_nchw": RowsToNchwArgs,
            "img_stem": ImgStemArgs, "img_conv": ImgConvArgs, "img_concat": ImgConcatArgs, "img_gate": ImgGateArgs,
            "img_apply": ImgApplyArgs, "img_pool": ImgPoolArgs, "img_prepare": ImgPrepareArgs,
-           "img_resize": ImgResizeArgs}
+           "img_resize": ImgResizeArgs, "pts_prepare": PtsPrepareArgs}
 
 _LIB = None
 
@@ -396,6 +413,10 @@ def _load():
         "cmt_img_prepare": ([P(ImgPrepareArgs), _vp], _int),
         "cmt_img_resize_args_size": ([], _i64),
         "cmt_img_resize_prepare": ([P(ImgResizeArgs), _vp], _int),
+        "cmt_pts_prepare_args_size": ([], _i64),
+        "cmt_pts_prepare_workspace_bytes": ([_i64], _i64),
+        "cmt_pts_prepare_tile_rows": ([], _int),
+        "cmt_pts_prepare": ([P(PtsPrepareArgs), _vp], _int),
         "cmt_adamw_step": ([P(AdamwArgs), _vp], _int),
     }
     for name, (args, res) in sig.items():

@@ -8,6 +8,9 @@ configs (no datasets or checkpoints are available offline).
     given yaws; pad_shape (640, 1600, 3)
   * points [N, 5]: xyz uniform in the point-cloud range, intensity U[0,255],
     time-lag U[0, 0.5]
+  * sweeps: a key frame and K sweeps as slices of one raw buffer, each sweep with a seeded rigid
+    sensor2lidar transform (yaw within 0.05 rad, up to 0.5 m per sweep of age) and a timestamp 50 ms
+    older than the one before; a seeded vehicle2infrastructure matrix for the coop configs
   * weights: the reference's init (xavier decoder, kaiming task heads, cls bias
     -2.19, reference_points U(0,1)), optionally with biases / norm affine
     parameters jittered so every fused epilogue is exercised by the parity tests.
@@ -24,7 +27,7 @@ from .registry import build_head
 
 __all__ = ["CONFIG_DIR", "make_head_cfg", "build_synthetic_head", "camera_lidar2img", "synthetic_metas",
            "synthetic_bev", "synthetic_img", "synthetic_points", "head_state_dict", "CONFIGS", "make_detector_cfg",
-           "synthetic_frames"]
+           "synthetic_frames", "synthetic_sweeps", "synthetic_vehicle2infrastructure"]
 
 CONFIG_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "configs")
 CONFIGS = ("cmt_lidar_nus", "cmt_fusion_nus", "cmtcoop_fusion_tumtraf", "cmtcoop_lidar_tumtraf")
@@ -227,3 +230,36 @@ def synthetic_points(N, pc_range, seed=0, device=None, margin=0.0):
     dt = torch.rand((N, 1), generator=g) * 0.5
     p = torch.cat([xyz, inten, dt], 1)
     return p.to(device) if device is not None else p
+
+
+def _rigid(g, max_yaw, max_trans, max_z):
+    """a seeded rigid transform as float64 numpy: yaw within max_yaw, x / y within max_trans, z within max_z"""
+    u = torch.rand(4, generator=g, dtype=torch.float64).numpy() * 2.0 - 1.0
+    c, s = math.cos(u[0] * max_yaw), math.sin(u[0] * max_yaw)
+    rot = np.array([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]])
+    return rot, np.array([u[1] * max_trans, u[2] * max_trans, u[3] * max_z])
+
+
+def synthetic_sweeps(K, N, pc_range, seed=0, device=None, margin=0.0):
+    """One cloud as the loaders hold it -> (key_points, sweeps, key_ts) for native_pts.sweep_segments: the key frame
+    [N, 5] and K sweeps of N points each, all slices of one raw buffer [(1 + K) N, 5] (``synthetic_points`` with
+    ``margin``, so a range filter has something to drop), ``sweeps`` as the info files list them (``points``,
+    ``sensor2lidar_rotation`` 3 x 3 and ``sensor2lidar_translation`` float64, ``timestamp`` in microseconds, 50 ms
+    apart), ``key_ts`` the key frame's timestamp."""
+    raw = synthetic_points((1 + K) * N, pc_range, seed=seed, device=device, margin=margin)
+    g = torch.Generator().manual_seed(seed + 29)
+    key_ts = 1_600_000_000_000_000 + 100_000 * seed
+    sweeps = []
+    for k in range(K):
+        rot, trans = _rigid(g, 0.05, 0.5 * (k + 1), 0.05)
+        sweeps.append(dict(points=raw[(k + 1) * N:(k + 2) * N], sensor2lidar_rotation=rot,
+                           sensor2lidar_translation=trans, timestamp=key_ts - 50_000 * (k + 1)))
+    return raw[:N], sweeps, key_ts
+
+
+def synthetic_vehicle2infrastructure(seed=0):
+    """a seeded 4 x 4 vehicle -> infrastructure matrix (float64): any yaw, up to 10 m in x / y, 0.5 m in z"""
+    rot, trans = _rigid(torch.Generator().manual_seed(seed + 31), math.pi, 10.0, 0.5)
+    m = np.eye(4)
+    m[:3, :3], m[:3, 3] = rot, trans
+    return m

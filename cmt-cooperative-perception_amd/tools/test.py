@@ -31,6 +31,12 @@ branch instead: ``resize_crop_plan((H, W), final_dim)``, ``prepare_images(resize
 fused into the preparation kernel) and ``resize_crop_lidar2img``; TUMTraf is ``--frame-size 1200 1920 --ida-size
 900 1600``.
 
+With ``--sweeps K`` every cloud is a key frame plus K synthetic sweeps (seeded rigid sensor2lidar transforms and
+time lags, a seeded ``vehicle2infrastructure`` for the coop configs) and goes through ``native_pts.prepare_points``
+with the plan ``points_plan_from_config`` reads from the config: remove_close, sweep transform, time column,
+``use_dim``, the vehicle cloud moved into the infrastructure frame, the range filter.  The detector gets the padded
+buffer (kept rows, then NaN) as it is; the vehicle cameras' ``lidar2img`` follow through ``lidar2img_to_infra``.
+
 Config 1 of BASELINE.json: ``python cmt-cooperative-perception_amd/tools/test.py
 cmt_lidar_nus --synthetic --num-query 32 --num-layers 1 --points 1000 --eval bbox``.
 The head runs on a HIP device only -- there is no CPU path; without a GPU the
@@ -74,7 +80,11 @@ def parse_args(argv=None):
                    help="H and W of the config's ida_aug_conf, for --detector: frames are resized to "
                         "resize_crop_plan((H, W), final_dim) and cropped, whatever --frame-size is (no default: "
                         "without it a frame must already have the size the crop is taken from)")
-    p.add_argument("--points", type=int, default=1000, help="synthetic points per frame and agent")
+    p.add_argument("--points", type=int, default=1000, help="synthetic points per frame and agent (per sweep with "
+                                                            "--sweeps)")
+    p.add_argument("--sweeps", type=int, default=None, metavar="K",
+                   help="for --detector: K synthetic sweeps per cloud, prepared on the device by prepare_points with "
+                        "the config's point plan (default: key-frame points as they are)")
     p.add_argument("--precision", default="bf16", choices=["bf16", "fp16", "ref"], help="compute policy")
     p.add_argument("--img-precision", default=None, choices=["ref", "fp16"],
                    help="arithmetic of the image backbone (--detector): three-pass split-f16 or one-pass fp16; "
@@ -95,6 +105,8 @@ def parse_args(argv=None):
         p.error("--eval and --format-only cannot be both specified")
     if a.out is not None and not a.out.endswith(".json"):
         p.error("The output file must be a .json file.")
+    if a.sweeps is not None and (not a.detector or a.sweeps < 0):
+        p.error("--sweeps K needs --detector and K >= 0")
     if not a.synthetic:
         p.error("dataset loading is out of scope (SURVEY.md 2 rows 18/21): run with --synthetic")
     return a
@@ -191,10 +203,17 @@ def detector_frame_inputs(name, cfg, meta, frame, args, device):
     """One synthetic frame for the detector -> (forward_test keyword arguments, per-agent point clouds)."""
     import numpy as np
     from projects.mmdet3d_plugin import native_img as NI
+    from projects.mmdet3d_plugin import native_pts as NP
     from projects.mmdet3d_plugin import synthetic as S
+    from projects.mmdet3d_plugin.config import load_config
     seed = args.seed + 1000 * frame
     coop = name.startswith("cmtcoop")
     fusion = "fusion" in name
+    plan = v2i = None
+    if args.sweeps is not None:
+        plan = NP.points_plan_from_config(load_config(os.path.join(S.CONFIG_DIR, name + ".py")))
+        if plan["coop"]:
+            v2i = S.synthetic_vehicle2infrastructure(seed)
     body = cfg["vehicle_model"] if coop else cfg
     pcr = body["pts_voxel_layer"]["point_cloud_range"]
     Hf, Wf = args.frame_size
@@ -211,7 +230,17 @@ def detector_frame_inputs(name, cfg, meta, frame, args, device):
         agents = [("", S.NUS_YAWS)]
     metas, kw, points = dict(), dict(), []
     for i, (prefix, yaws) in enumerate(agents):
-        pts = S.synthetic_points(args.points, pcr, seed=seed + 10 * i, device=device)
+        to_infra = v2i if prefix == "vehicle_" else None
+        if plan is None:
+            pts = S.synthetic_points(args.points, pcr, seed=seed + 10 * i, device=device)
+        else:
+            # raw sweep buffers -> the detector's points on the device; the padded buffer goes in as it is
+            key, sweeps, key_ts = S.synthetic_sweeps(args.sweeps, args.points, pcr, seed=seed + 10 * i, device=device,
+                                                     margin=2.0)
+            segs = NP.sweep_segments(key, sweeps, key_ts, time_dim=plan["time_dim"], remove_close=plan["remove_close"],
+                                     sweeps_num=plan["sweeps_num"], coop=plan["coop"])
+            pts, _ = NP.prepare_points(segs, use_dim=plan["use_dim"], load_dim=plan["load_dim"], agent_transform=to_infra,
+                                       point_cloud_range=pcr if plan["point_cloud_range"] is not None else None)
         points.append(pts)
         kw[prefix + "points"] = [[pts]]
         if not fusion:
@@ -227,6 +256,8 @@ def detector_frame_inputs(name, cfg, meta, frame, args, device):
             img = NI.prepare_images(frames, crop=crop)
             metas[prefix + "lidar2img"] = [NI.crop_lidar2img(K, S.camera_lidar2img(y, f=1.0, cx=0.0, cy=0.0), crop)
                                            for y in yaws]
+        if to_infra is not None:
+            metas[prefix + "lidar2img"] = list(NP.lidar2img_to_infra(np.stack(metas[prefix + "lidar2img"]), to_infra))
         metas[prefix + "pad_shape"] = [tuple(img.shape[2:]) + (3,)] * len(yaws)
         kw[prefix + "img"] = [img[None]]
     kw["img_metas"] = [[metas]]
@@ -316,7 +347,7 @@ def _run(args, name, device, rank, world, distributed):
             results.append(dict(frame=f, voxels=vox_stats,
                                 boxes_3d=boxes.float().cpu().tolist(), scores_3d=scores.float().cpu().tolist(),
                                 labels_3d=labels.cpu().tolist(),
-                                points_xyz=torch.cat([p[:, :3] for p in points]).cpu().tolist()
+                                points_xyz=torch.cat([p[:, :3][torch.isfinite(p[:, :3]).all(1)] for p in points]).cpu().tolist()
                                 if args.format_only else None))
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0

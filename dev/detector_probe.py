@@ -20,11 +20,21 @@ F.interpolate(mode='bilinear', align_corners=False), slice, normalise and pad.  
 float arithmetic, so the two results are compared within 1 grey level, not bit for bit.  ``--only resize`` runs this
 section alone and ``--resize-out FILE`` writes it to a file of its own.
 
+cmt_pts_prepare (raw sweep buffers to the detector's points, ``--only points`` / ``--points-out FILE``) is timed per
+cloud at the coop frame's two clouds and the fusion frame's one: a key frame and 10 sweeps of --sweep-points rows,
+load_dim 5, against (b) the same chain as torch ops on the device (per sweep a float64 matmul and add, the time
+column, ``cat``, the float32 agent matmul, the boolean mask and index) and (c) the reference's numpy / torch-CPU
+chain on the host plus the upload of its result, with the host's thread setting as it is.  (a) and (b) alternate in
+windows of --iters calls; (c) is timed call by call with a host clock.  ``--sweeps K`` puts the stage in front of
+the two detector frames (stage ``points``; the end-to-end clock then starts at the raw sweep buffers): use it with
+``--points`` as the rows per sweep.
+
 ``--img-precision`` (default ``ref``) is the image backbone's arithmetic (native_img.set_img_precision): ``fp16``
 runs VoVNet on the one-pass fp16 kernels; everything else is unchanged.
 
     python dev/detector_probe.py [--img-precision ref|fp16] [--points 300000] [--repeats 20] [--warmup 3]
-                                 [--iters 20] [--seed 0] [--out FILE] [--only resize] [--resize-out FILE]
+                                 [--iters 20] [--seed 0] [--out FILE] [--only resize|points] [--resize-out FILE]
+                                 [--points-out FILE] [--sweep-points 27000] [--sweeps K]
 
 Needs a HIP device and the built library; there is no CPU path.
 """
@@ -73,14 +83,21 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--img-precision", choices=("ref", "fp16"), default="ref")
     ap.add_argument("--out", default=None)
-    ap.add_argument("--only", choices=("resize",), default=None, help="run this section alone")
+    ap.add_argument("--only", choices=("resize", "points"), default=None, help="run this section alone")
     ap.add_argument("--resize-out", default=None, help="write the cmt_img_resize_prepare section to this file")
+    ap.add_argument("--points-out", default=None, help="write the cmt_pts_prepare section to this file")
+    ap.add_argument("--sweep-points", type=int, default=27000, help="rows per segment of the cmt_pts_prepare section")
+    ap.add_argument("--sweeps", type=int, default=None,
+                    help="detector frames: every cloud is a key frame and K sweeps of --points rows through "
+                         "prepare_points (stage 'points')")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("detector_probe needs a HIP device (timings are never taken on the CPU)")
     from projects.mmdet3d_plugin import build_detector
     from projects.mmdet3d_plugin import native_img as NI
+    from projects.mmdet3d_plugin import native_pts as NP
     from projects.mmdet3d_plugin import synthetic as S
+    from projects.mmdet3d_plugin.config import load_config
     from projects.mmdet3d_plugin.models.detectors import bbox3d2result
     dev = torch.device("cuda:0")
     lines = []
@@ -91,7 +108,7 @@ def main():
 
     NI.set_img_precision(args.img_precision)
     say(f"device {torch.cuda.get_device_name(0)}; seed {args.seed}; image backbone precision {args.img_precision!r}; frames {FRAME[0]} x {FRAME[1]} uint8, "
-        f"{args.points} points per cloud; per stage: median of {args.repeats} single calls after {args.warmup} "
+        f"{args.points} points per {'sweep, 1 + %d sweeps per cloud' % args.sweeps if args.sweeps is not None else 'cloud'}; per stage: median of {args.repeats} single calls after {args.warmup} "
         "warm-up (min .. max), device events, ms")
     _, crop = NI.test_crop(FRAME, (640, 1600))
 
@@ -113,16 +130,36 @@ def main():
         head = model.pts_bbox_head
         meta = dict()
         inputs = []
+        plan = NP.points_plan_from_config(load_config(os.path.join(S.CONFIG_DIR, name + ".py")))
+        clouds = []
         for i, (prefix, det, yaws) in enumerate(agents):
             pcr = det.pts_voxel_layer.point_cloud_range.tolist()
-            inputs.append((S.synthetic_frames(len(yaws), *FRAME, seed=args.seed + i, device=dev),
-                           [S.synthetic_points(args.points, pcr, seed=args.seed + 10 + i, device=dev)]))
+            if args.sweeps is None:
+                pts = [S.synthetic_points(args.points, pcr, seed=args.seed + 10 + i, device=dev)]
+                clouds.append(None)
+            else:
+                key, sweeps, key_ts = S.synthetic_sweeps(args.sweeps, args.points, pcr, seed=args.seed + 10 + i,
+                                                         device=dev, margin=2.0)
+                segs = NP.sweep_segments(key, sweeps, key_ts, time_dim=plan["time_dim"],
+                                         remove_close=plan["remove_close"], sweeps_num=plan["sweeps_num"],
+                                         coop=plan["coop"])
+                v2i = S.synthetic_vehicle2infrastructure(args.seed) if prefix == "vehicle_" else None
+                n = sum(int(s["points"].shape[0]) for s in segs)
+                clouds.append(dict(segments=segs, use_dim=plan["use_dim"], load_dim=plan["load_dim"], agent_transform=v2i,
+                                   point_cloud_range=plan["point_cloud_range"],
+                                   out=torch.empty((n, len(plan["use_dim"])), dtype=torch.float32, device=dev),
+                                   workspace=NP.PointsWorkspace()))
+                pts = [NP.prepare_points(**clouds[i])[0]]
+            inputs.append((S.synthetic_frames(len(yaws), *FRAME, seed=args.seed + i, device=dev), pts))
             meta.update(S.synthetic_metas(1, yaws=yaws, prefix=prefix, seed=args.seed + 20 + i)[0])
         metas = [meta]
         st = [dict() for _ in agents]
 
         def prepare(i):
             st[i]["img"] = NI.prepare_images(inputs[i][0], crop=crop)
+
+        def points(i):
+            st[i]["pts"] = NP.prepare_points(**clouds[i])
 
         def backbone(i):
             st[i]["bb"] = list(agents[i][1].img_backbone(st[i]["img"]).values())
@@ -148,9 +185,16 @@ def main():
             st[0]["res"] = [bbox3d2result(b, s, l) for b, s, l in head.get_bboxes(outs, metas)]
 
         per_agent = [prepare, backbone, neck, voxelize, middle, bev]
+        stages = STAGES
+        if args.sweeps is not None:
+            per_agent = [points] + per_agent
+            stages = ("points",) + STAGES
 
         def end_to_end():
             imgs = [NI.prepare_images(inputs[i][0], crop=crop)[None] for i in range(len(agents))]
+            if args.sweeps is not None:
+                for i in range(len(agents)):
+                    inputs[i][1][0] = NP.prepare_points(**clouds[i])[0]
             if coop:
                 return model.simple_test(inputs[0][1], inputs[1][1], metas, vehicle_img=imgs[0],
                                          infrastructure_img=imgs[1])
@@ -167,7 +211,7 @@ def main():
             say(f"--- {name}: {type(model).__name__}, cameras {[len(a[2]) for a in agents]}, voxels {vox}, "
                 f"boxes {int(st[0]['res'][0]['scores_3d'].shape[0])}")
             total = 0.0
-            for label, fn in zip(STAGES, per_agent + [head_decode]):
+            for label, fn in zip(stages, per_agent + [head_decode]):
                 n = 1 if fn is head_decode else len(agents)
                 for _ in range(args.warmup):
                     for i in range(n):
@@ -189,13 +233,17 @@ def main():
                 torch.cuda.synchronize()
                 ts.append((time.perf_counter() - t0) * 1e3)
             assert torch.equal(res[0]["pts_bbox"]["scores_3d"], st[0]["res"][0]["scores_3d"])
-            say(f"{'end to end, host clock':>22} {fmt(med(ts))}   (uint8 frames + points -> boxes on the host; equals "
+            what = "uint8 frames + points" if args.sweeps is None else "uint8 frames + raw sweep buffers"
+            say(f"{'end to end, host clock':>22} {fmt(med(ts))}   ({what} -> boxes on the host; equals "
                 "the staged pass bit for bit)")
             model.check_input_range()
         return inputs[0][0]
 
     if args.only == "resize":
         resize_section(args, dev, say, lines)
+        return
+    if args.only == "points":
+        points_section(args, dev, say, lines)
         return
     frames = frame("cmt_fusion_nus")
     frame("cmtcoop_fusion_tumtraf")
@@ -231,6 +279,134 @@ def main():
     say(f"{'cmt_img_prepare':>22} {fmt(tn)}   {nbytes * 1e-6:.1f} MB moved -> {nbytes / (tn[0] * 1e-3) * 1e-12:.2f} TB/s")
     say(f"{'torch ops':>22} {fmt(tt)}   native / torch {tn[0] / tt[0]:.2f}")
     resize_section(args, dev, say, lines)
+    points_section(args, dev, say, lines)
+
+
+def points_section(args, dev, say, lines):
+    """cmt_pts_prepare per cloud against the torch chain on the device and the reference's chain on the host"""
+    import numpy as np
+    from projects.mmdet3d_plugin import native_pts as NP
+    from projects.mmdet3d_plugin import synthetic as S
+    from projects.mmdet3d_plugin.config import load_config
+    first = len(lines)
+    K, N = 10, args.sweep_points
+    say(f"--- {torch.cuda.get_device_name(0)}: cmt_pts_prepare, one cloud = key frame + {K} sweeps of {N} rows, load_dim 5 "
+        f"({(K + 1) * N} rows): (a) prepare_points and (b) torch ops on the device in alternating windows of "
+        f"{args.iters} calls, median of {args.repeats} (min .. max), ms per cloud; (c) the reference's numpy chain on "
+        f"the host + upload, host clock, median of {args.repeats}, {torch.get_num_threads()} threads")
+    for name, prefix in (("cmtcoop_fusion_tumtraf", "vehicle_"), ("cmtcoop_fusion_tumtraf", "infrastructure_"),
+                         ("cmt_fusion_nus", "")):
+        cfg = load_config(os.path.join(S.CONFIG_DIR, name + ".py"))
+        plan = NP.points_plan_from_config(cfg)
+        pcr = plan["point_cloud_range"]
+        key, sweeps, key_ts = S.synthetic_sweeps(K, N, cfg["point_cloud_range"], seed=args.seed + len(prefix), device=dev,
+                                                 margin=2.0)
+        segs = NP.sweep_segments(key, sweeps, key_ts, time_dim=plan["time_dim"], remove_close=plan["remove_close"],
+                                 sweeps_num=plan["sweeps_num"], coop=plan["coop"])
+        v2i = S.synthetic_vehicle2infrastructure(args.seed) if prefix == "vehicle_" else None
+        n, use = (K + 1) * N, plan["use_dim"]
+        out = torch.empty((n, len(use)), dtype=torch.float32, device=dev)
+        ws = NP.PointsWorkspace()
+        rots = [torch.from_numpy(sw["sensor2lidar_rotation"].T.copy()).to(dev) for sw in sweeps]
+        trs = [torch.from_numpy(sw["sensor2lidar_translation"]).to(dev) for sw in sweeps]
+        lags = [s["time"] for s in segs[1:]]
+        r32 = torch.from_numpy(v2i[:3, :3].T.astype(np.float32)).to(dev) if v2i is not None else None
+        t32 = torch.from_numpy(v2i[:3, 3].astype(np.float32)).to(dev) if v2i is not None else None
+        lo = torch.tensor(pcr[:3], dtype=torch.float32, device=dev) if pcr is not None else None
+        hi = torch.tensor(pcr[3:], dtype=torch.float32, device=dev) if pcr is not None else None
+
+        def native_fn():
+            return NP.prepare_points(segs, use_dim=use, load_dim=5, agent_transform=v2i, point_cloud_range=pcr, out=out,
+                                     workspace=ws)
+
+        def torch_fn():
+            parts = [key.clone()]
+            parts[0][:, 4] = 0
+            for sw, rT, t, lag in zip(sweeps, rots, trs, lags):
+                p = sw["points"].clone()
+                p[:, :3] = (p[:, :3].double() @ rT).float()
+                p[:, :3] = (p[:, :3].double() + t).float()
+                p[:, 4] = lag
+                parts.append(p)
+            pts = torch.cat(parts)[:, use]
+            if r32 is not None:
+                pts[:, :3] = pts[:, :3] @ r32
+                pts[:, :3] += t32
+            if lo is not None:
+                pts = pts[((pts[:, :3] > lo) & (pts[:, :3] < hi)).all(1)]   # the index is a host read
+            return pts
+
+        host_key = key.cpu().numpy()
+        host_sweeps = [dict(sw, points=sw["points"].cpu().numpy()) for sw in sweeps]
+
+        def host_fn():
+            parts = [np.copy(host_key)]
+            parts[0][:, 4] = 0
+            for sw in host_sweeps:
+                p = np.copy(sw["points"])
+                p[:, :3] = p[:, :3] @ sw["sensor2lidar_rotation"].T
+                p[:, :3] += sw["sensor2lidar_translation"]
+                p[:, 4] = key_ts / 1e6 - sw["timestamp"] / 1e6
+                parts.append(p)
+            t = torch.from_numpy(np.concatenate(parts, 0)[:, use])
+            if v2i is not None:
+                t[:, :3] = t[:, :3] @ t.new_tensor(v2i[:3, :3].T)
+                t[:, :3] += t.new_tensor(v2i[:3, 3])
+            if pcr is not None:
+                r = np.array(pcr, dtype=np.float32)
+                t = t[(t[:, 0] > r[0]) & (t[:, 1] > r[1]) & (t[:, 2] > r[2]) & (t[:, 0] < r[3]) & (t[:, 1] < r[4])
+                      & (t[:, 2] < r[5])]
+            return t.to(dev)
+
+        padded, count = native_fn()
+        c = int(count.item())
+        tor, hst = torch_fn(), host_fn()
+        d_t = float((padded[:c] - tor).abs().max()) if tor.shape[0] == c else float("nan")
+        d_h = float((padded[:c] - hst).abs().max()) if hst.shape[0] == c else float("nan")
+        for fn in (native_fn, torch_fn, host_fn):
+            for _ in range(args.warmup):
+                fn()
+        torch.cuda.synchronize()
+        tn, tt, th = [], [], []
+        for _ in range(args.repeats):
+            tn.append(event_ms(lambda: [native_fn() for _ in range(args.iters)]) / args.iters)
+            tt.append(event_ms(lambda: [torch_fn() for _ in range(args.iters)]) / args.iters)
+        for _ in range(args.repeats):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            host_fn()
+            torch.cuda.synchronize()
+            th.append((time.perf_counter() - t0) * 1e3)
+        # the two launches alone: args.iters calls captured in one graph, so that the wrapper's host time is not in it
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            native_fn()
+        torch.cuda.current_stream().wait_stream(side)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            for _ in range(args.iters):
+                native_fn()
+        graph.replay()
+        torch.cuda.synchronize()
+        tg = med([event_ms(graph.replay) / args.iters for _ in range(args.repeats)])
+        tn, tt, th = med(tn), med(tt), med(th)
+        nbytes = n * 5 * 4 + n * len(use) * 4   # the source once, the destination once
+        say(f"{name} {prefix or 'cloud'}: agent transform {v2i is not None}, range filter {pcr is not None}; kept {c} of {n}; "
+            f"rows kept by the torch chain {tor.shape[0]}, by the host chain {hst.shape[0]}; largest coordinate "
+            f"distance {d_t:.2e} / {d_h:.2e} m")
+        say(f"{'(a) prepare_points':>26} {fmt(tn)}   {nbytes * 1e-6:.1f} MB moved -> {nbytes / (tn[0] * 1e-3) * 1e-12:.2f} TB/s "
+            "(repeats on one cloud: the buffers stay in the Infinity Cache)")
+        say(f"{'(a) from a graph':>26} {fmt(tg)}   the two launches without the wrapper's host time -> "
+            f"{nbytes / (tg[0] * 1e-3) * 1e-12:.2f} TB/s")
+        say(f"{'(b) torch ops, device':>26} {fmt(tt)}   (a) / (b) {tn[0] / tt[0]:.3f}")
+        say(f"{'(c) numpy on the host':>26} {fmt(th)}   (a) / (c) {tn[0] / th[0]:.4f}")
+    say(f"peak device memory {torch.cuda.max_memory_allocated() / 2 ** 20:.0f} MiB")
+    for path, text in ((args.out, lines), (args.points_out, lines[first:])):
+        if path:
+            os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+            with open(path, "w") as f:
+                f.write("\n".join(text) + "\n")
 
 
 def resize_section(args, dev, say, lines):

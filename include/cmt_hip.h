@@ -1216,6 +1216,78 @@ typedef struct cmt_img_resize_args {
 int64_t cmt_img_resize_args_size(void);
 int cmt_img_resize_prepare(const cmt_img_resize_args* args, void* stream);
 
+/* ---- raw LiDAR sweeps -> the detector's points (ptsprep.hip; additive to ABI 25) -------------------
+ * cmt_pts_prepare: the point side of the reference's test pipeline for ONE cloud (one agent's key frame
+ * plus its sweeps): LoadPointsFromMultiSweeps[Coop] (remove_close, sweep -> key-frame transform, time
+ * column, concatenation, use_dim), VehiclePointsToInfraCoords and PointsRangeFilter[Coop], as an
+ * order-preserving stream compaction.  THIS TEXT is the contract: a restatement of the reference in which
+ * every rounding is fixed.
+ *   src: fp32 [n_total][load_dim], contiguous, 4-byte aligned (rows are read dword by dword), load_dim 3..8.
+ *   S segments, 1 <= S <= CMT_PTS_MAX_SEG: segment s holds rows [seg_start[s], seg_start[s + 1]), with
+ *   seg_start[0] == 0, seg_start non-decreasing and seg_start[S] == n_total.  Empty segments and
+ *   n_total == 0 are legal; n_total < 2^31 (element offsets are 64-bit).
+ *   dst: fp32 [n_total][F_out], contiguous, 4-byte aligned, F_out 3..8; count: one device int32.
+ * Per row of segment s, in this order (x, y, z = columns 0, 1, 2 of the raw row; fl32 = one rounding to
+ * float32, round-to-nearest-even; no operation below is fused with another):
+ *   1. remove_close, on the raw row: with r = close_radius > 0 the row is dropped iff |x| < r && |y| < r
+ *      in float32.  A NaN compares false, so such a row is kept (as numpy does).  r == 0: off.
+ *   2. sweep transform (has_sweep_xform), numpy's float64 matrix on a float32 array, for k = 0, 1, 2:
+ *        q_k = fl32(((double)x * rot[3k] + (double)y * rot[3k + 1]) + (double)z * rot[3k + 2])
+ *      float64 products and float64 sums, left to right, no FMA; then
+ *        p_k = fl32((double)q_k + trans[k]).
+ *      rot is sensor2lidar_rotation row-major (the reference's pts[:, :3] @ rot.T), trans its translation.
+ *   3. time column: time_col >= 0 sets column time_col of the row to time_val (the host's
+ *      fl32(ts - sweep_ts) for a sweep, 0 for the key frame); time_col == -1 leaves the row as it is.
+ *   4. column selection: out[j] = row[use_dim[j]], j < F_out.  use_dim[0..2] must be 0, 1, 2.
+ *   5. agent transform (has_agent_xform), mmdet3d's BasePoints.rotate(R.T) then translate(t) in float32
+ *      on out[0..2], with rot32 = R row-major (the vehicle2infrastructure rotation) and trans32 = t:
+ *        p'_k = fl32(fl32(fl32(fl32(x * rot32[3k]) + fl32(y * rot32[3k + 1])) + fl32(z * rot32[3k + 2])) + trans32[k])
+ *      The reference's float32 matmul leaves the order of its sums to the BLAS; this text fixes one.
+ *   6. range filter (has_range), in_range_3d: the row is kept iff out[k] > range[k] && out[k] < range[3 + k]
+ *      for k = 0, 1, 2, strict, in float32; a NaN or +-inf coordinate drops the row.  Without the filter
+ *      such rows are kept.
+ * Kept rows go to dst[0 .. count) in input order (segment order, then row order: the reference's cat);
+ * rows [count, n_total) are filled with the quiet NaN 0x7FC00000 in every column, so every element of dst
+ * is written and a voxelizer that drops non-finite points sees the trimmed cloud.  count is written once.
+ * Two launches (per-tile kept counts of cmt_pts_prepare_tile_rows() rows into the workspace; then prefix,
+ * scatter and fill), no workgroup waits for another, no host synchronisation, no allocation:
+ * graph-capturable.  The workspace (cmt_pts_prepare_workspace_bytes(n_total) bytes, 4-byte aligned) is
+ * rewritten by every call before it is read: it needs no initialisation and no cleaning, and serves one
+ * stream at a time.  Each workgroup of the second launch reads every tile count, so the call is meant for
+ * clouds of up to a few million rows.
+ * CMT_EINVAL, before any device work: S, load_dim, F_out or use_dim out of range; seg_start[0] != 0,
+ * decreasing, or seg_start[S] != n_total; n_total < 0 or >= 2^31; time_col < -1 or >= load_dim;
+ * close_radius negative or non-finite; a non-finite transform that is switched on; range non-finite or
+ * min >= max; src, dst or workspace null or misaligned with n_total > 0; count null; workspace_bytes
+ * below cmt_pts_prepare_workspace_bytes(n_total). */
+#define CMT_PTS_MAX_SEG 16
+typedef struct cmt_pts_segment {
+    double rot[9], trans[3];                      /* sweep -> key frame, float64 as the info files hold them */
+    int has_sweep_xform;
+    float close_radius;                           /* 0: off */
+    int time_col;                                 /* -1: leave the column */
+    float time_val;
+} cmt_pts_segment;
+typedef struct cmt_pts_prepare_args {
+    int64_t n_total;
+    int S, load_dim, F_out;
+    int has_agent_xform, has_range, reserved;
+    int64_t seg_start[CMT_PTS_MAX_SEG + 1];
+    int use_dim[8];
+    float rot32[9], trans32[3];                   /* agent transform */
+    float range[6];                               /* x, y, z min, then x, y, z max */
+    cmt_pts_segment seg[CMT_PTS_MAX_SEG];
+    const void* src;
+    void* dst;
+    int* count;
+    void* workspace;
+    int64_t workspace_bytes;
+} cmt_pts_prepare_args;
+int64_t cmt_pts_prepare_args_size(void);
+int64_t cmt_pts_prepare_workspace_bytes(int64_t n_total);   /* 0 for n_total <= 0 */
+int cmt_pts_prepare_tile_rows(void);
+int cmt_pts_prepare(const cmt_pts_prepare_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
