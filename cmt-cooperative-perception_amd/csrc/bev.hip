@@ -18,15 +18,6 @@ constexpr int BEV_WMAX = 180;   // the widest map (the NCHW halo conv's limit, s
 constexpr int BEV_DB_WAVES = 2; // deblock: waves per workgroup, 32 output channels each
 constexpr int BEV_DB_TM = 32;   // deblock: input pixels per workgroup
 
-__device__ __forceinline__ f32x16 mma3(pair8_t ahi, pair8_t alo, pair8_t bhi, pair8_t blo, f32x16 c) {
-    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(alo, bhi, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(ahi, blo, c, 0, 0, 0);
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(ahi, bhi, c, 0, 0, 0);
-}
-
-// C/D layout of the 32x32 MFMA: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
-__device__ __forceinline__ int acc_row(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
-
 __global__ __launch_bounds__(256) void bev_conv3x3_kernel(cmt_bev_conv_args a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r = lane & 31, h = lane >> 5;
@@ -164,9 +155,6 @@ __global__ __launch_bounds__(64 * BEV_DB_WAVES) void bev_deblock_kernel(cmt_bev_
     }
 }
 
-template <typename T>
-bool bev_aligned16(const T* p) { return (((uintptr_t)p) & 15) == 0; }
-
 }  // namespace
 
 extern "C" int64_t cmt_bev_conv_args_size(void) { return (int64_t)sizeof(cmt_bev_conv_args); }
@@ -184,7 +172,7 @@ extern "C" int cmt_bev_conv3x3(const cmt_bev_conv_args* a, void* stream) {
     CMT_REQUIRE(a->ldx >= 2 * (int64_t)a->Cin && a->ldx % 8 == 0 && a->ldw >= 18 * (int64_t)a->Cin && a->ldw % 8 == 0 &&
                     a->ldy >= 2 * (int64_t)a->Cout,
                 "cmt_bev_conv3x3: ldx >= 2 Cin, ldw >= 18 Cin (both % 8, 16-bit words) and ldy >= 2 Cout required");
-    CMT_REQUIRE(bev_aligned16(a->X) && bev_aligned16(a->Wt), "cmt_bev_conv3x3: X and Wt must be 16-byte aligned");
+    CMT_REQUIRE(aligned16(a->X) && aligned16(a->Wt), "cmt_bev_conv3x3: X and Wt must be 16-byte aligned");
     const int s = a->stride;
     const int64_t M = (int64_t)a->B * ((a->H - 1) / s + 1) * ((a->W - 1) / s + 1);
     dim3 grid((unsigned)cdiv64(M, BEV_TM), (unsigned)(a->Cout / BEV_TN));
@@ -203,7 +191,7 @@ extern "C" int cmt_bev_deblock(const cmt_bev_deblock_args* a, void* stream) {
     CMT_REQUIRE((int64_t)a->B * a->H * a->W < ((int64_t)1 << 31), "cmt_bev_deblock: B*H*W must be below 2^31");
     CMT_REQUIRE(a->ldx >= 2 * (int64_t)a->Cin && a->ldx % 8 == 0 && a->ldw >= 2 * (int64_t)a->Cin && a->ldw % 8 == 0,
                 "cmt_bev_deblock: ldx, ldw >= 2 Cin and % 8 (16-bit words) required");
-    CMT_REQUIRE(bev_aligned16(a->X) && bev_aligned16(a->Wt), "cmt_bev_deblock: X and Wt must be 16-byte aligned");
+    CMT_REQUIRE(aligned16(a->X) && aligned16(a->Wt), "cmt_bev_deblock: X and Wt must be 16-byte aligned");
     const int64_t M = (int64_t)a->B * a->H * a->W;
     dim3 grid((unsigned)cdiv64(M, BEV_DB_TM), (unsigned)(a->Cout / (32 * BEV_DB_WAVES)), (unsigned)a->k);
     hipStream_t s = (hipStream_t)stream;

@@ -142,6 +142,23 @@ __device__ __forceinline__ void store_pair8(pair_t* row, int C, int c, const flo
     *(pair8_t*)(row + c) = h;
     *(pair8_t*)(row + C + c) = l;
 }
+__device__ __forceinline__ pair8_t zero8() {
+    pair8_t z;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) z[j] = (pair_t)0.f;
+    return z;
+}
+// c += a b on pair fragments in three f16 passes, small terms first (lo * lo dropped)
+__device__ __forceinline__ f32x16 mma3(pair8_t ahi, pair8_t alo, pair8_t bhi, pair8_t blo, f32x16 c) {
+    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(alo, bhi, c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(ahi, blo, c, 0, 0, 0);
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(ahi, bhi, c, 0, 0, 0);
+}
+// C/D layout of the 32x32 MFMA: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
+__device__ __forceinline__ int acc_row(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
+
+template <typename T>
+static inline bool aligned16(const T* p) { return (((uintptr_t)p) & 15) == 0; }
 
 // The long-key f16 attention forward (attention.hip, cmt_attn_fwd's bounded-offset path) that
 // also writes the row statistic lse[(b * H + h) * Nq + q] = log2(sum_k exp2(c s_qk)) (exp2 units

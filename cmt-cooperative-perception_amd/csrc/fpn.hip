@@ -2,7 +2,7 @@
 // include/cmt_hip.h (cmt_fpn_lateral, cmt_rows_to_nchw):
 //   fpn_lateral_kernel    1 x 1 conv read transposed from the fp32 NCHW map, the coarser level's
 //                         nearest-upsampled pair rows added in the epilogue, to CMT_F16P rows
-//   rows_to_nchw_kernel   pair rows -> fp32 NCHW through a 64 x 64 LDS transpose
+//   rows_to_nchw_kernel   pair rows (or plain fp16 rows) -> fp32 NCHW through a 64 x 64 LDS transpose
 // The lateral gathers its A fragments straight into the MFMA operand layout (lane (r, h): pixel r,
 // channels 8h .. 8h+7 of a 16-channel step, one coalesced dword load per channel) and splits them in
 // registers; W's fragments come from the packed [N][2][K] pair rows through LDS; three f16 MFMA passes
@@ -19,9 +19,6 @@ constexpr int FPN_TN = 128;     // lateral: output channels per workgroup
 constexpr int FPN_KC = 64;      // lateral: k per staged chunk of W (four 16-k steps, one 128-byte line per row half)
 constexpr int FPN_WROW = 128;   // lateral: 16-bit words per LDS row of a W chunk (hi 64 | lo 64)
 constexpr int FPN_XCDS = 8;   // workgroups are dealt round-robin over this many L2 domains
-
-// C/D layout of the 32x32 MFMA: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
-__device__ __forceinline__ int acc_row(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
 
 // torch's nearest source index for F.interpolate(size=...): one fp32 multiply by in / out
 __device__ __forceinline__ int nearest_src(int dst, float scale, int in_size) {
@@ -188,10 +185,12 @@ __global__ __launch_bounds__(256) void fpn_lateral_kernel(cmt_fpn_lateral_args a
     raise_range_flag(a.range_flag, bad);
 }
 
-// One workgroup: 64 pixels x 64 channels of one image.  Loads are 16 bytes of hi and of lo along
-// channels (8 lanes per pixel row), stores run along pixels: 16 bytes per lane where HW % 4 == 0 (VEC),
-// 4 bytes otherwise.  LDS tile [64 c][65]: bank (c + p) % 64, conflict-free for both store forms.
-template <bool VEC>
+// One workgroup: 64 pixels x 64 channels of one image.  Loads are 16 bytes along channels (8 lanes per
+// pixel row): of hi and of lo from pair rows (WORDS 2), or one of plain fp16 rows [B*HW][C] widened exactly
+// (WORDS 1, the image backbone's one-pass policy).  Stores run along pixels: 16 bytes per lane where
+// HW % 4 == 0 (VEC), 4 bytes otherwise.  LDS tile [64 c][65]: bank (c + p) % 64, conflict-free for both
+// store forms.
+template <int WORDS, bool VEC>
 __global__ __launch_bounds__(256) void rows_to_nchw_kernel(cmt_rows_to_nchw_args a) {
     __shared__ float tile[64][65];
     const int t = threadIdx.x;
@@ -204,9 +203,15 @@ __global__ __launch_bounds__(256) void rows_to_nchw_kernel(cmt_rows_to_nchw_args
             const int pi = pass * 32 + pl;
             if (p0 + pi < HW && c0 + cg < C) {
                 const pair_t* row = (const pair_t*)a.X + ((int64_t)b * HW + p0 + pi) * a.ldx + c0 + cg;
-                const pair8_t hi = *(const pair8_t*)row, lo = *(const pair8_t*)(row + C);
+                const pair8_t hi = *(const pair8_t*)row;
+                if constexpr (WORDS == 2) {
+                    const pair8_t lo = *(const pair8_t*)(row + C);
 #pragma unroll
-                for (int j = 0; j < 8; ++j) tile[cg + j][pi] = (float)hi[j] + (float)lo[j];
+                    for (int j = 0; j < 8; ++j) tile[cg + j][pi] = (float)hi[j] + (float)lo[j];
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) tile[cg + j][pi] = (float)hi[j];
+                }
             }
         }
     }
@@ -231,51 +236,6 @@ __global__ __launch_bounds__(256) void rows_to_nchw_kernel(cmt_rows_to_nchw_args
         }
     }
 }
-
-// rows_to_nchw_kernel for plain fp16 rows [B*HW][C] (the image backbone's one-pass policy): the same tile,
-// one 16-byte load per lane, the value widened exactly.
-template <bool VEC>
-__global__ __launch_bounds__(256) void rows_to_nchw_f16_kernel(cmt_rows_to_nchw_args a) {
-    __shared__ float tile[64][65];
-    const int t = threadIdx.x;
-    const int p0 = blockIdx.x * 64, c0 = blockIdx.y * 64, b = blockIdx.z;
-    const int C = a.C, HW = a.HW;
-    {
-        const int cg = (t & 7) * 8, pl = t >> 3;
-#pragma unroll
-        for (int pass = 0; pass < 2; ++pass) {
-            const int pi = pass * 32 + pl;
-            if (p0 + pi < HW && c0 + cg < C) {
-                const pair8_t x = *(const pair8_t*)((const f16_t*)a.X + ((int64_t)b * HW + p0 + pi) * a.ldx + c0 + cg);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) tile[cg + j][pi] = (float)x[j];
-            }
-        }
-    }
-    __syncthreads();
-    float* Y = a.Y + (int64_t)b * C * HW;
-    if constexpr (VEC) {
-        const int q = (t & 15) * 4, cr = t >> 4;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int c = c0 + cr + 16 * k, p = p0 + q;
-            if (c < C && p < HW) {   // HW % 4 == 0: the four pixels are inside together
-                const float* s = &tile[cr + 16 * k][q];
-                *(f32x4*)(Y + (int64_t)c * HW + p) = f32x4{s[0], s[1], s[2], s[3]};
-            }
-        }
-    } else {
-        const int px = t & 63, cr = t >> 6;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            const int c = c0 + cr + 4 * k;
-            if (c < C && p0 + px < HW) Y[(int64_t)c * HW + p0 + px] = tile[cr + 4 * k][px];
-        }
-    }
-}
-
-template <typename T>
-bool fpn_aligned16(const T* p) { return (((uintptr_t)p) & 15) == 0; }
 
 }  // namespace
 
@@ -293,12 +253,12 @@ extern "C" int cmt_fpn_lateral(const cmt_fpn_lateral_args* a, void* stream) {
     CMT_REQUIRE(a->x_bstride >= (int64_t)a->Cin * HW, "cmt_fpn_lateral: x_bstride below Cin*H*W");
     CMT_REQUIRE(a->ldw >= 2 * (int64_t)a->Cin && a->ldw % 8 == 0 && a->ldl >= 2 * (int64_t)a->Cout && a->ldl % 8 == 0,
                 "cmt_fpn_lateral: ldw >= 2 Cin and ldl >= 2 Cout, both % 8 (16-bit words), required");
-    CMT_REQUIRE(fpn_aligned16(a->Wt) && fpn_aligned16(a->L), "cmt_fpn_lateral: Wt and L must be 16-byte aligned");
+    CMT_REQUIRE(aligned16(a->Wt) && aligned16(a->L), "cmt_fpn_lateral: Wt and L must be 16-byte aligned");
     float scale_h = 0.f, scale_w = 0.f;
     if (a->T != nullptr) {
         CMT_REQUIRE(a->Htop >= 1 && a->Htop <= a->H && a->Wtop >= 1 && a->Wtop <= a->W,
                     "cmt_fpn_lateral: 1 <= Htop <= H and 1 <= Wtop <= W required with T");
-        CMT_REQUIRE(a->ldt >= 2 * (int64_t)a->Cout && a->ldt % 8 == 0 && fpn_aligned16(a->T),
+        CMT_REQUIRE(a->ldt >= 2 * (int64_t)a->Cout && a->ldt % 8 == 0 && aligned16(a->T),
                     "cmt_fpn_lateral: ldt >= 2 Cout, % 8, and a 16-byte aligned T required");
         scale_h = (float)a->Htop / (float)a->H;
         scale_w = (float)a->Wtop / (float)a->W;
@@ -312,38 +272,25 @@ extern "C" int cmt_fpn_lateral(const cmt_fpn_lateral_args* a, void* stream) {
     return cmt_check_launch("cmt_fpn_lateral");
 }
 
-extern "C" int cmt_rows_to_nchw(const cmt_rows_to_nchw_args* a, void* stream) {
-    CMT_REQUIRE(a != nullptr, "cmt_rows_to_nchw: null argument struct");
-    CMT_REQUIRE(a->X && a->Y, "cmt_rows_to_nchw: X and Y must be non-null");
-    CMT_REQUIRE(a->B > 0 && a->HW > 0, "cmt_rows_to_nchw: B and HW must be positive");
-    CMT_REQUIRE(a->C > 0 && a->C % 8 == 0, "cmt_rows_to_nchw: C must be a positive multiple of 8");
-    CMT_REQUIRE(a->B <= 65535 && a->C <= 65535 * 64, "cmt_rows_to_nchw: B or C beyond the grid");
-    CMT_REQUIRE((int64_t)a->B * a->HW < ((int64_t)1 << 31), "cmt_rows_to_nchw: B*HW must be below 2^31");
-    CMT_REQUIRE(a->ldx >= 2 * (int64_t)a->C && a->ldx % 8 == 0 && fpn_aligned16(a->X),
-                "cmt_rows_to_nchw: ldx >= 2 C, % 8 (16-bit words), and a 16-byte aligned X required");
-    CMT_REQUIRE((((uintptr_t)a->Y) & 3) == 0, "cmt_rows_to_nchw: Y must be 4-byte aligned");
+template <int WORDS>
+static int rows_to_nchw(const char* name, const cmt_rows_to_nchw_args* a, void* stream) {
+    const std::string n = std::string(name) + ": ";
+    CMT_REQUIRE(a != nullptr, n + "null argument struct");
+    CMT_REQUIRE(a->X && a->Y, n + "X and Y must be non-null");
+    CMT_REQUIRE(a->B > 0 && a->HW > 0, n + "B and HW must be positive");
+    CMT_REQUIRE(a->C > 0 && a->C % 8 == 0, n + "C must be a positive multiple of 8");
+    CMT_REQUIRE(a->B <= 65535 && a->C <= 65535 * 64, n + "B or C beyond the grid");
+    CMT_REQUIRE((int64_t)a->B * a->HW < ((int64_t)1 << 31), n + "B*HW must be below 2^31");
+    CMT_REQUIRE(a->ldx >= WORDS * (int64_t)a->C && a->ldx % 8 == 0 && aligned16(a->X),
+                n + (WORDS == 2 ? "ldx >= 2 C" : "ldx >= C") + ", % 8 (16-bit words), and a 16-byte aligned X required");
+    CMT_REQUIRE((((uintptr_t)a->Y) & 3) == 0, n + "Y must be 4-byte aligned");
     dim3 grid((unsigned)cdiv(a->HW, 64), (unsigned)cdiv(a->C, 64), (unsigned)a->B);
-    if (a->HW % 4 == 0 && fpn_aligned16(a->Y))
-        rows_to_nchw_kernel<true><<<grid, 256, 0, (hipStream_t)stream>>>(*a);
+    if (a->HW % 4 == 0 && aligned16(a->Y))
+        rows_to_nchw_kernel<WORDS, true><<<grid, 256, 0, (hipStream_t)stream>>>(*a);
     else
-        rows_to_nchw_kernel<false><<<grid, 256, 0, (hipStream_t)stream>>>(*a);
-    return cmt_check_launch("cmt_rows_to_nchw");
+        rows_to_nchw_kernel<WORDS, false><<<grid, 256, 0, (hipStream_t)stream>>>(*a);
+    return cmt_check_launch(name);
 }
 
-extern "C" int cmt_rows_to_nchw_f16(const cmt_rows_to_nchw_args* a, void* stream) {
-    CMT_REQUIRE(a != nullptr, "cmt_rows_to_nchw_f16: null argument struct");
-    CMT_REQUIRE(a->X && a->Y, "cmt_rows_to_nchw_f16: X and Y must be non-null");
-    CMT_REQUIRE(a->B > 0 && a->HW > 0, "cmt_rows_to_nchw_f16: B and HW must be positive");
-    CMT_REQUIRE(a->C > 0 && a->C % 8 == 0, "cmt_rows_to_nchw_f16: C must be a positive multiple of 8");
-    CMT_REQUIRE(a->B <= 65535 && a->C <= 65535 * 64, "cmt_rows_to_nchw_f16: B or C beyond the grid");
-    CMT_REQUIRE((int64_t)a->B * a->HW < ((int64_t)1 << 31), "cmt_rows_to_nchw_f16: B*HW must be below 2^31");
-    CMT_REQUIRE(a->ldx >= (int64_t)a->C && a->ldx % 8 == 0 && fpn_aligned16(a->X),
-                "cmt_rows_to_nchw_f16: ldx >= C, % 8 (16-bit words), and a 16-byte aligned X required");
-    CMT_REQUIRE((((uintptr_t)a->Y) & 3) == 0, "cmt_rows_to_nchw_f16: Y must be 4-byte aligned");
-    dim3 grid((unsigned)cdiv(a->HW, 64), (unsigned)cdiv(a->C, 64), (unsigned)a->B);
-    if (a->HW % 4 == 0 && fpn_aligned16(a->Y))
-        rows_to_nchw_f16_kernel<true><<<grid, 256, 0, (hipStream_t)stream>>>(*a);
-    else
-        rows_to_nchw_f16_kernel<false><<<grid, 256, 0, (hipStream_t)stream>>>(*a);
-    return cmt_check_launch("cmt_rows_to_nchw_f16");
-}
+extern "C" int cmt_rows_to_nchw(const cmt_rows_to_nchw_args* a, void* s) { return rows_to_nchw<2>("cmt_rows_to_nchw", a, s); }
+extern "C" int cmt_rows_to_nchw_f16(const cmt_rows_to_nchw_args* a, void* s) { return rows_to_nchw<1>("cmt_rows_to_nchw_f16", a, s); }

@@ -24,10 +24,10 @@ sources without a concatenated map, its epilogue leaving the pool's per-tile sum
 selected maps leave through ``cmt_rows_to_nchw`` as contiguous fp32 NCHW, what ``CPFPN`` reads.
 
 Arithmetic.  ``native_img.set_img_precision('ref' | 'fp16')`` (env ``CMT_IMG_PRECISION``, default ``'ref'``),
-read per forward: ``'ref'`` is the routing above, three-pass split-f16 on pair rows; ``'fp16'`` runs the same
-launches on ``cmt_img_*_f16`` -- plain fp16 rows between launches, weights folded in float64 and rounded once to
-fp16, one MFMA per step with fp32 accumulation -- and leaves through ``cmt_rows_to_nchw_f16``; nothing is routed
-to ``cmt_gemm`` there.  The gate stays fp32 (``cmt_img_ese_gate``).  Packs are cached per arithmetic.
+read once per forward: ``'ref'`` is the routing above, three-pass split-f16 on pair rows; ``'fp16'`` is the same walk
+on ``cmt_img_*_f16`` -- plain fp16 rows between launches, weights folded in float64 and rounded once to fp16, one
+MFMA per step with fp32 accumulation -- and leaves through ``cmt_rows_to_nchw_f16``; nothing is routed to
+``cmt_gemm`` there.  The gate stays fp32 (``cmt_img_ese_gate``).  Packs are cached per arithmetic.
 
 state_dict keys carry the ``/`` of the reference's module names: ``stem.stem_1/conv.weight``,
 ``stem.stem_1/norm.{weight, bias, running_mean, running_var, num_batches_tracked}``,
@@ -76,6 +76,11 @@ def route_conv3x3(rows, wp, shift, *, B, H, W, Cin, Cout, stride, relu=True, out
                                range_flag=range_flag)
     return NI.conv3x3(rows, wp, shift, B=B, H=H, W=W, Cin=Cin, Cout=Cout, stride=stride, relu=relu, out=out,
                       range_flag=range_flag)
+
+
+def _op(mod, name, fp16):
+    """the wrapper of the forward's arithmetic, looked up at the call"""
+    return getattr(mod, name + "_f16" if fp16 else name)
 
 
 def _conv_bn(cin, cout, k, stride, name):
@@ -187,63 +192,24 @@ class VoVNet(nn.Module, RangeFlagMixin):
                                        fc.bias.detach().float().contiguous()))
 
     # ---- forward -----------------------------------------------------------------------------------------
-    def conv3x3(self, rows, wp, shift, *, B, H, W, Cin, Cout, stride, flag):
-        return route_conv3x3(rows, wp, shift, B=B, H=H, W=W, Cin=Cin, Cout=Cout, stride=stride, range_flag=flag)
+    def conv3x3(self, rows, w, shift, *, fp16, flag, **kw):
+        """a 3 x 3 layer: 'ref' routes by shape (GEMM_ROUTED), 'fp16' routes nothing"""
+        return (NI.conv3x3_f16 if fp16 else route_conv3x3)(rows, w, shift, range_flag=flag, **kw)
 
-    def _osa(self, name, blk, x, B, H, W, flag):
+    def _osa(self, name, blk, x, B, H, W, flag, fp16=False):
         srcs, cur, cin = [x], x, blk.in_ch
         for i in range(len(blk.layers)):
-            wp, shift = self.packed_layer(name, blk, i)
-            cur = self.conv3x3(cur, wp, shift, B=B, H=H, W=W, Cin=cin, Cout=blk.stage_ch, stride=1, flag=flag)
+            w, shift = self.packed_layer(name, blk, i, fp16=fp16)
+            cur = self.conv3x3(cur, w, shift, B=B, H=H, W=W, Cin=cin, Cout=blk.stage_ch, stride=1, fp16=fp16, flag=flag)
             srcs.append(cur)
             cin = blk.stage_ch
-        wp, shift = self.packed_layer(name, blk, "concat")
-        y, part = NI.concat1x1(srcs, wp, shift, B=B, HW=H * W, Cout=blk.concat_ch, part=True, range_flag=flag)
+        w, shift = self.packed_layer(name, blk, "concat", fp16=fp16)
+        y, part = _op(NI, "concat1x1", fp16)(srcs, w, shift, B=B, HW=H * W, Cout=blk.concat_ch, part=True,
+                                             range_flag=flag)
         fw, fb = self.packed_fc(name, blk)
         gate = NI.ese_gate(part, fw, fb, HW=H * W)
-        return NI.ese_apply(y, gate, B=B, HW=H * W, C=blk.concat_ch, identity=x if blk.identity else None, out=y,
-                            range_flag=flag)
-
-    def _osa_f16(self, name, blk, x, B, H, W, flag):
-        srcs, cur, cin = [x], x, blk.in_ch
-        for i in range(len(blk.layers)):
-            w16, shift = self.packed_layer(name, blk, i, fp16=True)
-            cur = NI.conv3x3_f16(cur, w16, shift, B=B, H=H, W=W, Cin=cin, Cout=blk.stage_ch, stride=1, range_flag=flag)
-            srcs.append(cur)
-            cin = blk.stage_ch
-        w16, shift = self.packed_layer(name, blk, "concat", fp16=True)
-        y, part = NI.concat1x1_f16(srcs, w16, shift, B=B, HW=H * W, Cout=blk.concat_ch, part=True, range_flag=flag)
-        fw, fb = self.packed_fc(name, blk)
-        gate = NI.ese_gate(part, fw, fb, HW=H * W)
-        return NI.ese_apply_f16(y, gate, B=B, HW=H * W, C=blk.concat_ch, identity=x if blk.identity else None, out=y,
-                                range_flag=flag)
-
-    def _forward_f16(self, x, B, H, W, flag):
-        """forward's body on the one-pass fp16 kernels: fp16 rows [B*H*W, C] between launches"""
-        outs = OrderedDict()
-        s = [self.stem[3 * i].out_channels for i in range(3)]
-        w16, shift = self.packed_stem(0, fp16=True)
-        rows = NI.stem_f16(x, w16, shift, Cout=s[0], range_flag=flag)
-        H, W = NB.out_hw(H, W, 2)
-        w16, shift = self.packed_stem(1, fp16=True)
-        rows = NI.conv3x3_f16(rows, w16, shift, B=B, H=H, W=W, Cin=s[0], Cout=s[1], stride=1, range_flag=flag)
-        w16, shift = self.packed_stem(2, fp16=True)
-        rows = NI.conv3x3_f16(rows, w16, shift, B=B, H=H, W=W, Cin=s[1], Cout=s[2], stride=2, range_flag=flag)
-        H, W = NB.out_hw(H, W, 2)
-        C = s[2]
-        if "stem" in self._out_features:
-            outs["stem"] = NF.rows_to_nchw_f16(rows, (B, C, H, W))
-        for name in self.stage_names:
-            for blk_name, blk in getattr(self, name).named_children():
-                if isinstance(blk, _Pool):
-                    rows = NI.maxpool_f16(rows, B=B, H=H, W=W, C=C)
-                    H, W = NI.pool_hw(H, W)
-                else:
-                    rows = self._osa_f16(blk_name, blk, rows, B, H, W, flag)
-                    C = blk.concat_ch
-            if name in self._out_features:
-                outs[name] = NF.rows_to_nchw_f16(rows, (B, C, H, W))
-        return outs
+        return _op(NI, "ese_apply", fp16)(y, gate, B=B, HW=H * W, C=blk.concat_ch, identity=x if blk.identity else None,
+                                          out=y, range_flag=flag)
 
     def forward(self, x):
         """[B, input_ch, H, W] -> an ordered dict name -> contiguous fp32 NCHW map for ``out_features``, in the
@@ -264,28 +230,27 @@ class VoVNet(nn.Module, RangeFlagMixin):
         with torch.no_grad():
             flag = self._range_flag(x.device)
             x = x.float().contiguous()
-            if NI.img_precision() == "fp16":
-                return self._forward_f16(x, B, H, W, flag)
+            fp16 = NI.img_precision() == "fp16"     # rows between launches: plain fp16 [B*H*W, C], else pair rows
             s = [self.stem[3 * i].out_channels for i in range(3)]
-            wp, shift = self.packed_stem(0)
-            rows = NI.stem(x, wp, shift, Cout=s[0], range_flag=flag)
+            w, shift = self.packed_stem(0, fp16=fp16)
+            rows = _op(NI, "stem", fp16)(x, w, shift, Cout=s[0], range_flag=flag)
             H, W = NB.out_hw(H, W, 2)
-            wp, shift = self.packed_stem(1)
-            rows = self.conv3x3(rows, wp, shift, B=B, H=H, W=W, Cin=s[0], Cout=s[1], stride=1, flag=flag)
-            wp, shift = self.packed_stem(2)
-            rows = self.conv3x3(rows, wp, shift, B=B, H=H, W=W, Cin=s[1], Cout=s[2], stride=2, flag=flag)
+            w, shift = self.packed_stem(1, fp16=fp16)
+            rows = self.conv3x3(rows, w, shift, B=B, H=H, W=W, Cin=s[0], Cout=s[1], stride=1, fp16=fp16, flag=flag)
+            w, shift = self.packed_stem(2, fp16=fp16)
+            rows = self.conv3x3(rows, w, shift, B=B, H=H, W=W, Cin=s[1], Cout=s[2], stride=2, fp16=fp16, flag=flag)
             H, W = NB.out_hw(H, W, 2)
             C = s[2]
             if "stem" in self._out_features:
-                outs["stem"] = NF.rows_to_nchw(rows, (B, C, H, W))
+                outs["stem"] = _op(NF, "rows_to_nchw", fp16)(rows, (B, C, H, W))
             for name in self.stage_names:
                 for blk_name, blk in getattr(self, name).named_children():
                     if isinstance(blk, _Pool):
-                        rows = NI.maxpool(rows, B=B, H=H, W=W, C=C)
+                        rows = _op(NI, "maxpool", fp16)(rows, B=B, H=H, W=W, C=C)
                         H, W = NI.pool_hw(H, W)
                     else:
-                        rows = self._osa(blk_name, blk, rows, B, H, W, flag)
+                        rows = self._osa(blk_name, blk, rows, B, H, W, flag, fp16)
                         C = blk.concat_ch
                 if name in self._out_features:
-                    outs[name] = NF.rows_to_nchw(rows, (B, C, H, W))
+                    outs[name] = _op(NF, "rows_to_nchw", fp16)(rows, (B, C, H, W))
         return outs

@@ -10,6 +10,7 @@ import torch
 from . import native as N
 from .native import _check, _dev, _p, _stream, lib
 from .native_bev import RowMap, _flag, _pair_rows, _shift, fold_bn, pack_conv3x3, split_pair
+from .native_img import FP16, PAIR, _bind
 
 __all__ = ["lateral", "rows_to_nchw", "rows_to_nchw_f16", "pack_conv1x1", "pack_conv3x3_bias", "nearest_index"]
 
@@ -91,42 +92,28 @@ def lateral(x, Wp, shift, *, Cout, top=None, top_hw=None, relu=False, out=None, 
     return L
 
 
-def rows_to_nchw(rows, shape, out=None):
-    """cmt_rows_to_nchw: pair rows [B*H*W, 2, C] of the map ``shape`` = (B, C, H, W) -> contiguous fp32 NCHW,
-    bit-equal to RowMap.nchw()"""
+def _rows_to_nchw(fmt, rows, shape, out=None):
+    """cmt_rows_to_nchw[_f16]: rows of width C of the map ``shape`` = (B, C, H, W) -> contiguous fp32 NCHW.
+    ``rows_to_nchw``: pair rows [B*H*W, 2, C], bit-equal to RowMap.nchw(); ``rows_to_nchw_f16``: fp16 rows
+    [B*H*W, C] (the image backbone's one-pass policy), every value widened exactly"""
     if isinstance(rows, RowMap):
         raise ValueError("pass RowMap.rows and RowMap.shape")
     B, C, H, W = (int(s) for s in shape)
     if min(B, H, W) <= 0 or C <= 0 or C % 8:
         raise ValueError(f"a non-empty map with C % 8 == 0 required, got {(B, C, H, W)}")
-    _pair_rows("rows", rows, B * H * W, C)
+    if not torch.is_tensor(rows):
+        raise ValueError(f"rows must be {fmt.what}, got {type(rows)}")
+    fmt.check("rows", rows, B * H * W, C)
     if out is not None and (out.dtype != torch.float32 or tuple(out.shape) != (B, C, H, W) or not out.is_contiguous()):
         raise ValueError(f"out must be contiguous fp32 {(B, C, H, W)}, got {out.dtype} {tuple(out.shape)}")
     _dev(rows, out)
     Y = out if out is not None else torch.empty((B, C, H, W), dtype=torch.float32, device=rows.device)
     a = N.RowsToNchwArgs()
     a.B, a.C, a.HW, a.reserved = B, C, H * W, 0
-    a.X, a.ldx, a.Y = _p(rows), 2 * C, _p(Y)
-    _check(lib().cmt_rows_to_nchw(ctypes.byref(a), _stream()), "cmt_rows_to_nchw")
+    a.X, a.ldx, a.Y = _p(rows), fmt.words * C, _p(Y)
+    name = "cmt_rows_to_nchw" + fmt.suffix
+    _check(getattr(lib(), name)(ctypes.byref(a), _stream()), name)
     return Y
 
 
-def rows_to_nchw_f16(rows, shape, out=None):
-    """cmt_rows_to_nchw_f16: fp16 rows [B*H*W, C] of the map ``shape`` = (B, C, H, W) (the image backbone's one-pass
-    policy) -> contiguous fp32 NCHW, every value widened exactly"""
-    B, C, H, W = (int(s) for s in shape)
-    if min(B, H, W) <= 0 or C <= 0 or C % 8:
-        raise ValueError(f"a non-empty map with C % 8 == 0 required, got {(B, C, H, W)}")
-    if not torch.is_tensor(rows) or rows.dtype != torch.float16 or rows.dim() != 2 or rows.shape[1] != C or \
-            rows.shape[0] < B * H * W or not rows.is_contiguous():
-        raise ValueError(f"rows must be contiguous fp16 rows [>= {B * H * W}, {C}], got "
-                         f"{(rows.dtype, tuple(rows.shape)) if torch.is_tensor(rows) else type(rows)}")
-    if out is not None and (out.dtype != torch.float32 or tuple(out.shape) != (B, C, H, W) or not out.is_contiguous()):
-        raise ValueError(f"out must be contiguous fp32 {(B, C, H, W)}, got {out.dtype} {tuple(out.shape)}")
-    _dev(rows, out)
-    Y = out if out is not None else torch.empty((B, C, H, W), dtype=torch.float32, device=rows.device)
-    a = N.RowsToNchwArgs()
-    a.B, a.C, a.HW, a.reserved = B, C, H * W, 0
-    a.X, a.ldx, a.Y = _p(rows), C, _p(Y)
-    _check(lib().cmt_rows_to_nchw_f16(ctypes.byref(a), _stream()), "cmt_rows_to_nchw_f16")
-    return Y
+rows_to_nchw, rows_to_nchw_f16 = _bind(_rows_to_nchw, PAIR), _bind(_rows_to_nchw, FP16)

@@ -4,6 +4,7 @@ device check, tensors must live on a HIP device, there is no CPU fallback, no wr
 host.  The packing reuses native_bev's float64 BN fold and f16 hi / lo split.
 """
 import ctypes
+import functools
 import os
 
 import numpy as np
@@ -11,8 +12,7 @@ import torch
 
 from . import native as N
 from .native import _check, _dev, _p, _stream, lib
-from .native_bev import _flag, _pair_rows, _shift, fold_bn, out_hw, split_pair
-from .native_fpn import pack_conv1x1
+from .native_bev import _flag, _shift, fold_bn, out_hw, split_pair
 
 __all__ = ["STEM_K", "CONCAT_TM", "MAX_SRC", "pack_stem", "pack_concat", "pool_hw", "concat_tiles", "stem", "conv3x3",
            "conv3x3_gemm", "concat1x1", "ese_gate", "ese_apply", "maxpool", "IMG_MEAN", "IMG_STD", "norm_constants",
@@ -200,24 +200,98 @@ def prepare_images(frames, crop=None, mean=IMG_MEAN, std=IMG_STD, to_rgb=False, 
     return Y
 
 
-def pack_stem(w, bn):
+class RowFormat:
+    """What the wrappers below need to know of a row buffer of the backbone kernels.  Two instances: PAIR, the
+    split-f16 pair rows uint16 [rows, 2, C] of cmt_img_*, and FP16, the plain fp16 rows [rows, C] of cmt_img_*_f16
+    (the one-pass policy).  ``words``: 16-bit words per element; ``suffix``: of the entry names; ``quantize``:
+    float64 weight rows -> the format's W image.  What a wrapper takes beyond contiguous buffers differs between
+    the two and is data here: ``strided_stem`` (the stem takes a strided batch axis), ``sliced_conv`` (conv3x3
+    takes column slices of wider row buffers for X and out; the concat's sources may be slices in both)."""
+
+    def __init__(self, what, dtype, words, suffix, quantize, strided_stem, sliced_conv):
+        self.what, self.dtype, self.words, self.suffix, self.quantize = what, dtype, words, suffix, quantize
+        self.strided_stem, self.sliced_conv = strided_stem, sliced_conv
+
+    def shape(self, rows, C):
+        return (rows, 2, C) if self.words == 2 else (rows, C)
+
+    def empty(self, rows, C, device):
+        return torch.empty(self.shape(rows, C), dtype=self.dtype, device=device)
+
+    def width(self, t):
+        """C of a row buffer, 0 for anything of another rank"""
+        return int(t.shape[-1]) if torch.is_tensor(t) and t.dim() == len(self.shape(0, 0)) else 0
+
+    def check(self, name, t, rows, C, sliced=False):
+        """``t`` holds at least ``rows`` rows of width C: contiguous, or with ``sliced`` a column slice of a wider
+        row buffer (a row's words contiguous at a leading dimension % 8) -> the leading dimension in words"""
+        shape = self.shape(rows, C)
+        if t.dtype != self.dtype or t.dim() != len(shape) or tuple(t.shape[1:]) != shape[1:] or t.shape[0] < rows or \
+                not (sliced or t.is_contiguous()):
+            raise ValueError(f"{name} must be {'' if sliced else 'contiguous '}{self.what} [>= {rows}, "
+                             f"{', '.join(str(s) for s in shape[1:])}], got {t.dtype} {tuple(t.shape)}")
+        n = self.words * C
+        if not sliced:
+            return n
+        ld = int(t.stride(0)) if t.shape[0] > 1 else max(int(t.stride(0)), n)
+        if tuple(t.stride()[1:]) != ((C, 1) if self.words == 2 else (1,)) or ld < n or ld % 8:
+            raise ValueError(f"{name}: a row must be {n} contiguous words at a leading dimension >= {n}, % 8; got "
+                             f"strides {tuple(t.stride())}")
+        return ld
+
+    def call(self, kind, args):
+        name = f"cmt_img_{kind}{self.suffix}"
+        _check(getattr(lib(), name)(ctypes.byref(args), _stream()), name)
+
+
+PAIR = RowFormat("split-f16 pair rows uint16", torch.uint16, 2, "", split_pair, strided_stem=False, sliced_conv=False)
+FP16 = RowFormat("fp16 rows", torch.float16, 1, "_f16", lambda w64: round_f16(w64), strided_stem=True, sliced_conv=True)
+
+
+def _bind(fn, fmt):
+    """the public wrapper of one format: ``fn`` with its first argument bound"""
+    f = functools.partial(fn, fmt)
+    f.__doc__, f.__name__ = fn.__doc__, fn.__name__.lstrip("_") + fmt.suffix
+    return f
+
+
+def _pack_stem(fmt, w, bn):
     """Conv2d weight (Cout, Cin <= 3, 3, 3) and its BN (weight, bias, running_mean, running_var, eps) ->
-    (pair rows [Cout, 2, 32] with k = (ky*3 + kx) * Cin + c and zeros from 9 Cin on, fp32 shift [Cout])."""
+    (W rows of K = 32 with k = (ky*3 + kx) * Cin + c and zeros from 9 Cin on, fp32 shift [Cout]); the rows are
+    pair rows [Cout, 2, 32] (pack_stem) or fp16 [Cout, 32] (pack_stem_f16)."""
     if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or not 1 <= w.shape[1] <= 3:
         raise ValueError(f"expected a (Cout, Cin <= 3, 3, 3) conv weight, got {tuple(w.shape)}")
     scale, shift = fold_bn(*bn)
     w64 = (w.detach().double() * scale[:, None, None, None]).permute(0, 2, 3, 1).reshape(w.shape[0], -1)
     rows = torch.zeros((w.shape[0], STEM_K), dtype=torch.float64, device=w.device)
     rows[:, :w64.shape[1]] = w64
-    return split_pair(rows), shift.float().contiguous()
+    return fmt.quantize(rows), shift.float().contiguous()
 
 
-def pack_concat(w, bn):
-    """The OSA aggregation's Conv2d weight (Cout, sum C_s, 1, 1) and its BN -> (pair rows [Cout, 2, K] in the
-    concatenation's channel order, fp32 shift [Cout])"""
+def _pack_concat(fmt, w, bn):
+    """The OSA aggregation's Conv2d weight (Cout, sum C_s, 1, 1) and its BN -> (W rows in the concatenation's
+    channel order, fp32 shift [Cout]); pair rows [Cout, 2, K] (pack_concat) or fp16 [Cout, K] (pack_concat_f16)."""
     if not isinstance(bn, (list, tuple)) or len(bn) != 5:
         raise ValueError("bn must be (weight, bias, running_mean, running_var, eps)")
-    return pack_conv1x1(w, list(bn))
+    if w.dim() != 4 or tuple(w.shape[2:]) != (1, 1):
+        raise ValueError(f"expected a (Cout, Cin, 1, 1) conv weight, got {tuple(w.shape)}")
+    scale, shift = fold_bn(*bn)
+    w64 = w.detach().double().reshape(w.shape[0], w.shape[1]) * scale[:, None]
+    return fmt.quantize(w64), shift.float().contiguous()
+
+
+def pack_conv3x3_f16(w, bn):
+    """native_bev.pack_conv3x3 for cmt_img_conv3x3_f16 -> (fp16 [Cout, 9 Cin] with k = (ky*3 + kx) * Cin + c,
+    fp32 shift [Cout])"""
+    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3):
+        raise ValueError(f"expected a (Cout, Cin, 3, 3) conv weight, got {tuple(w.shape)}")
+    scale, shift = fold_bn(*bn)
+    w64 = w.detach().double() * scale[:, None, None, None]
+    return round_f16(w64.permute(0, 2, 3, 1).reshape(w.shape[0], -1)), shift.float().contiguous()
+
+
+pack_stem, pack_stem_f16 = _bind(_pack_stem, PAIR), _bind(_pack_stem, FP16)
+pack_concat, pack_concat_f16 = _bind(_pack_concat, PAIR), _bind(_pack_concat, FP16)
 
 
 def pool_hw(H, W):
@@ -243,36 +317,45 @@ def _positive(**kw):
             raise ValueError(f"{k} must be positive, got {v}")
 
 
-def stem(x, Wp, shift, *, Cout, relu=True, out=None, range_flag=None):
-    """cmt_img_stem: the 3 x 3 / stride 2 / pad 1 conv of the fp32 NCHW image [B, Cin <= 3, H, W] -> pair rows
-    [B*Ho*Wo, 2, Cout] (rows beyond stay untouched)"""
-    if x.dim() != 4 or x.dtype != torch.float32 or not x.is_contiguous():
-        raise ValueError("x must be a contiguous fp32 [B, C, H, W] image")
+def _w_rows(fmt, Wt, Cout, K):
+    fmt.check("W", Wt, Cout, K)
+    if Wt.shape[0] != Cout:
+        raise ValueError(f"W must hold {Cout} rows, got {Wt.shape[0]}")
+
+
+def _stem(fmt, x, Wt, shift, *, Cout, relu=True, out=None, range_flag=None):
+    """cmt_img_stem[_f16]: the 3 x 3 / stride 2 / pad 1 conv of the fp32 NCHW image [B, Cin <= 3, H, W] -> rows
+    of width Cout for the B*Ho*Wo outputs (rows beyond stay untouched).  ``stem``: a contiguous image to pair rows
+    [B*Ho*Wo, 2, Cout]; ``stem_f16``: a strided batch axis is taken as it is, to fp16 rows [B*Ho*Wo, Cout]."""
+    if x.dim() != 4 or x.dtype != torch.float32 or not (fmt.strided_stem or x.is_contiguous()):
+        raise ValueError(f"x must be {'an' if fmt.strided_stem else 'a contiguous'} fp32 [B, C, H, W] image")
     B, Cin, H, W = (int(s) for s in x.shape)
     if min(B, H, W) <= 0 or not 1 <= Cin <= 3 or Cout <= 0 or Cout % 32:
         raise ValueError(f"a non-empty image with 1 <= Cin <= 3 and Cout % 32 == 0 required, got {tuple(x.shape)} "
                          f"and Cout {Cout}")
+    bstride = int(x.stride(0)) if fmt.strided_stem and B > 1 else Cin * H * W
+    if fmt.strided_stem and (tuple(x.stride()[1:]) != (H * W, W, 1) or bstride < Cin * H * W):
+        raise ValueError("every image of x must be contiguous [C, H, W] at a batch stride >= C*H*W")
     if B * H * W >= 2 ** 31:
         raise ValueError("B*H*W must be below 2^31")
     Ho, Wo = out_hw(H, W, 2)
-    _pair_rows("Wp", Wp, Cout, STEM_K)
-    if Wp.shape[0] != Cout:
-        raise ValueError(f"Wp must hold {Cout} rows, got {Wp.shape[0]}")
+    _w_rows(fmt, Wt, Cout, STEM_K)
     _shift(shift, Cout)
     _flag(range_flag)
     if out is not None:
-        _pair_rows("out", out, B * Ho * Wo, Cout)
-    _dev(x, Wp, shift, out, range_flag)
-    Y = out if out is not None else torch.empty((B * Ho * Wo, 2, Cout), dtype=torch.uint16, device=x.device)
+        fmt.check("out", out, B * Ho * Wo, Cout)
+    _dev(x, Wt, shift, out, range_flag)
+    Y = out if out is not None else fmt.empty(B * Ho * Wo, Cout, x.device)
     a = N.ImgStemArgs()
     a.B, a.H, a.W, a.Cin, a.Cout, a.relu = B, H, W, Cin, Cout, int(bool(relu))
-    a.X, a.x_bstride, a.Wt, a.shift = _p(x), Cin * H * W, _p(Wp), _p(shift)
-    a.Y, a.ldy, a.range_flag = _p(Y), 2 * Cout, _p(range_flag)
-    _check(lib().cmt_img_stem(ctypes.byref(a), _stream()), "cmt_img_stem")
+    a.X, a.x_bstride, a.Wt, a.shift = _p(x), bstride, _p(Wt), _p(shift)
+    a.Y, a.ldy, a.range_flag = _p(Y), fmt.words * Cout, _p(range_flag)
+    fmt.call("stem", a)
     return Y
 
 
-def _conv_checks(X, Wp, shift, B, H, W, Cin, Cout, stride, out, range_flag, mult):
+def _conv_checks(fmt, X, Wt, shift, B, H, W, Cin, Cout, stride, out, range_flag, mult, sliced):
+    """-> (Ho, Wo, ldx, ldy)"""
     if min(B, H, W) <= 0:
         raise ValueError(f"B, H and W must be positive, got {(B, H, W)}")
     if stride not in (1, 2):
@@ -282,67 +365,51 @@ def _conv_checks(X, Wp, shift, B, H, W, Cin, Cout, stride, out, range_flag, mult
     if B * H * W >= 2 ** 31:
         raise ValueError("B*H*W must be below 2^31")
     Ho, Wo = out_hw(H, W, stride)
-    _pair_rows("X", X, B * H * W, Cin)
-    _pair_rows("Wp", Wp, Cout, 9 * Cin)
-    if Wp.shape[0] != Cout:
-        raise ValueError(f"Wp must hold {Cout} rows, got {Wp.shape[0]}")
+    ldx = fmt.check("X", X, B * H * W, Cin, sliced)
+    _w_rows(fmt, Wt, Cout, 9 * Cin)
     _shift(shift, Cout)
     _flag(range_flag)
-    if out is not None:
-        _pair_rows("out", out, B * Ho * Wo, Cout)
-    return Ho, Wo
+    ldy = fmt.words * Cout if out is None else fmt.check("out", out, B * Ho * Wo, Cout, sliced)
+    return Ho, Wo, ldx, ldy
 
 
 def conv3x3_gemm(X, Wp, shift, *, B, H, W, Cin, Cout, relu=True, out=None, range_flag=None):
     """The stride-1 conv of conv3x3's contract on cmt_gemm's CMT_A_CONV3X3 pair-row path (batch in M, any
     width): Cin % 64 == 0 and Cout % 64 == 0.  Same K order, so the rows are bit-equal to conv3x3's."""
-    _conv_checks(X, Wp, shift, B, H, W, Cin, Cout, 1, out, range_flag, 64)
+    _conv_checks(PAIR, X, Wp, shift, B, H, W, Cin, Cout, 1, out, range_flag, 64, False)
     _dev(X, Wp, shift, out, range_flag)
     M = B * H * W
-    Y = out if out is not None else torch.empty((M, 2, Cout), dtype=torch.uint16, device=X.device)
+    Y = out if out is not None else PAIR.empty(M, Cout, X.device)
     N.gemm(X, Wp, Y, M=M, N=Cout, K=9 * Cin, lda=Cin, ldw=9 * Cin, ldc=Cout, bias=shift, relu=relu,
            a_mode=N.A_CONV3X3, conv=(H, W, Cin), range_flag=range_flag)
     return Y
 
 
-def conv3x3(X, Wp, shift, *, B, H, W, Cin, Cout, stride, relu=True, out=None, range_flag=None, nb=0):
-    """cmt_img_conv3x3: pair rows [B*H*W, 2, Cin] -> pair rows [B*Ho*Wo, 2, Cout] (rows beyond stay untouched);
-    Cin % 32 == 0, Cout % 32 == 0, Cout <= 256, any width.  ``nb``: 32-column blocks per workgroup, a divisor
-    of Cout / 32 (0: the library chooses from the row count; the result is the same)"""
+def _conv3x3(fmt, X, Wt, shift, *, B, H, W, Cin, Cout, stride, relu=True, out=None, range_flag=None, nb=0):
+    """cmt_img_conv3x3[_f16]: rows of width Cin for B*H*W pixels -> rows of width Cout for B*Ho*Wo (rows beyond
+    stay untouched); Cin % 32 == 0, Cout % 32 == 0, Cout <= 256, any map width.  ``conv3x3``: contiguous pair rows
+    [.., 2, C]; ``conv3x3_f16``: fp16 rows [.., C], where X and out may be column slices of wider row buffers
+    (leading dimension % 8).  ``nb``: 32-column blocks per workgroup, a divisor of Cout / 32 (0: the library
+    chooses from the row count; the result is the same)"""
     if nb < 0 or (nb and Cout > 0 and (Cout // 32) % nb):
         raise ValueError(f"nb must be 0 or a divisor of Cout / 32 = {Cout // 32}, got {nb}")
-    Ho, Wo = _conv_checks(X, Wp, shift, B, H, W, Cin, Cout, stride, out, range_flag, 32)
-    _dev(X, Wp, shift, out, range_flag)
-    Y = out if out is not None else torch.empty((B * Ho * Wo, 2, Cout), dtype=torch.uint16, device=X.device)
+    Ho, Wo, ldx, ldy = _conv_checks(fmt, X, Wt, shift, B, H, W, Cin, Cout, stride, out, range_flag, 32, fmt.sliced_conv)
+    _dev(X, Wt, shift, out, range_flag)
+    Y = out if out is not None else fmt.empty(B * Ho * Wo, Cout, X.device)
     a = N.ImgConvArgs()
     a.B, a.H, a.W, a.Cin, a.Cout, a.stride, a.relu, a.nb = B, H, W, Cin, Cout, stride, int(bool(relu)), nb
-    a.X, a.ldx, a.Wt, a.ldw, a.shift = _p(X), 2 * Cin, _p(Wp), 18 * Cin, _p(shift)
-    a.Y, a.ldy, a.range_flag = _p(Y), 2 * Cout, _p(range_flag)
-    _check(lib().cmt_img_conv3x3(ctypes.byref(a), _stream()), "cmt_img_conv3x3")
+    a.X, a.ldx, a.Wt, a.ldw, a.shift = _p(X), ldx, _p(Wt), 9 * fmt.words * Cin, _p(shift)
+    a.Y, a.ldy, a.range_flag = _p(Y), ldy, _p(range_flag)
+    fmt.call("conv3x3", a)
     return Y
 
 
-def _source(i, t, rows):
-    """a source of the concat: uint16 [>= rows, 2, C], C % 32 == 0, rows of 2 C contiguous words at a leading
-    dimension (stride(0)) >= 2 C that is a multiple of 8 -> (C, ld)"""
-    if t.dtype != torch.uint16 or t.dim() != 3 or t.shape[1] != 2 or t.shape[0] < rows:
-        raise ValueError(f"source {i} must be split-f16 pair rows uint16 [>= {rows}, 2, C], got {t.dtype} "
-                         f"{tuple(t.shape)}")
-    C = int(t.shape[2])
-    if C <= 0 or C % 32:
-        raise ValueError(f"source {i}: width {C} is no positive multiple of 32")
-    ld = int(t.stride(0)) if t.shape[0] > 1 else max(int(t.stride(0)), 2 * C)
-    if t.stride(2) != 1 or t.stride(1) != C or ld < 2 * C or ld % 8:
-        raise ValueError(f"source {i}: a row must be 2 C contiguous words at a leading dimension >= 2 C, % 8; got "
-                         f"strides {tuple(t.stride())}")
-    return C, ld
-
-
-def concat1x1(sources, Wp, shift, *, B, HW, Cout, relu=True, out=None, part=None, range_flag=None):
-    """cmt_img_concat1x1: the 1 x 1 conv of the channel concatenation of up to 8 pair-row ``sources``
-    ([B*HW, 2, C_s] each, possibly a column slice of a wider row buffer) -> pair rows [B*HW, 2, Cout].
-    ``part``: True allocates, a tensor is used, None writes none: fp32 [B, concat_tiles(HW), Cout], the
-    per-tile column sums of the stored values.  Returns (rows, part)."""
+def _concat1x1(fmt, sources, Wt, shift, *, B, HW, Cout, relu=True, out=None, part=None, range_flag=None):
+    """cmt_img_concat1x1[_f16]: the 1 x 1 conv of the channel concatenation of up to 8 ``sources`` (rows of
+    width C_s % 32 == 0 for B*HW pixels each, possibly a column slice of a wider row buffer) -> rows of width Cout;
+    pair rows (``concat1x1``) or fp16 rows (``concat1x1_f16``).  ``part``: True allocates, a tensor is used, None
+    writes none: fp32 [B, concat_tiles(HW), Cout], the per-tile column sums of the values as stored.  Returns
+    (rows, part)."""
     sources = list(sources)
     if not 1 <= len(sources) <= MAX_SRC:
         raise ValueError(f"1 to {MAX_SRC} sources required, got {len(sources)}")
@@ -351,30 +418,34 @@ def concat1x1(sources, Wp, shift, *, B, HW, Cout, relu=True, out=None, part=None
         raise ValueError(f"Cout must be a positive multiple of 128, got {Cout}")
     if B * HW >= 2 ** 31 or B > 65535:
         raise ValueError("B*HW must be below 2^31 and B at most 65535")
-    dims = [_source(i, t, B * HW) for i, t in enumerate(sources)]
+    dims = []
+    for i, t in enumerate(sources):
+        C = fmt.width(t)
+        if C <= 0 or C % 32:
+            raise ValueError(f"source {i} must be {fmt.what} [>= {B * HW}, ..., C] with C a positive multiple of 32, got "
+                             f"{tuple(t.shape) if torch.is_tensor(t) else type(t)}")
+        dims.append((C, fmt.check(f"source {i}", t, B * HW, C, sliced=True)))
     K = sum(c for c, _ in dims)
-    _pair_rows("Wp", Wp, Cout, K)
-    if Wp.shape[0] != Cout:
-        raise ValueError(f"Wp must hold {Cout} rows, got {Wp.shape[0]}")
+    _w_rows(fmt, Wt, Cout, K)
     _shift(shift, Cout)
     _flag(range_flag)
     if out is not None:
-        _pair_rows("out", out, B * HW, Cout)
+        fmt.check("out", out, B * HW, Cout)
     tiles = concat_tiles(HW)
     if part is not None and part is not True:
         _f32("part", part, (B, tiles, Cout))
-    _dev(*sources, Wp, shift, out, None if part is True else part, range_flag)
+    _dev(*sources, Wt, shift, out, None if part is True else part, range_flag)
     dev = sources[0].device
-    Y = out if out is not None else torch.empty((B * HW, 2, Cout), dtype=torch.uint16, device=dev)
+    Y = out if out is not None else fmt.empty(B * HW, Cout, dev)
     if part is True:
         part = torch.empty((B, tiles, Cout), dtype=torch.float32, device=dev)
     a = N.ImgConcatArgs()
     a.B, a.HW, a.Cout, a.nsrc, a.relu = B, HW, Cout, len(sources), int(bool(relu))
     for i, (t, (c, ld)) in enumerate(zip(sources, dims)):
         a.C[i], a.X[i], a.ldx[i] = c, t.data_ptr(), ld
-    a.Wt, a.ldw, a.shift = _p(Wp), 2 * K, _p(shift)
-    a.Y, a.ldy, a.part, a.range_flag = _p(Y), 2 * Cout, _p(part), _p(range_flag)
-    _check(lib().cmt_img_concat1x1(ctypes.byref(a), _stream()), "cmt_img_concat1x1")
+    a.Wt, a.ldw, a.shift = _p(Wt), fmt.words * K, _p(shift)
+    a.Y, a.ldy, a.part, a.range_flag = _p(Y), fmt.words * Cout, _p(part), _p(range_flag)
+    fmt.call("concat1x1", a)
     return Y, part
 
 
@@ -402,50 +473,58 @@ def ese_gate(part, w, bias, *, HW, out=None):
     return G
 
 
-def ese_apply(X, gate, *, B, HW, C, identity=None, out=None, range_flag=None):
-    """cmt_img_ese_apply: pair rows x [B*HW, 2, C] times gate [B, C] (plus the pair rows ``identity``) -> pair
-    rows; ``out`` may be X (in place)"""
+def _ese_apply(fmt, X, gate, *, B, HW, C, identity=None, out=None, range_flag=None):
+    """cmt_img_ese_apply[_f16]: rows x of width C for B*HW pixels times gate [B, C] (plus the rows ``identity``),
+    in fp32, converted once -> rows; ``out`` may be X (in place).  Pair rows (``ese_apply``) or fp16 rows
+    (``ese_apply_f16``)."""
     _positive(B=B, HW=HW)
     if C <= 0 or C % 8:
         raise ValueError(f"C must be a positive multiple of 8, got {C}")
     if B * HW >= 2 ** 31:
         raise ValueError("B*HW must be below 2^31")
-    _pair_rows("X", X, B * HW, C)
+    fmt.check("X", X, B * HW, C)
     _f32("gate", gate, (B, C))
     if identity is not None:
-        _pair_rows("identity", identity, B * HW, C)
+        fmt.check("identity", identity, B * HW, C)
     if out is not None:
-        _pair_rows("out", out, B * HW, C)
+        fmt.check("out", out, B * HW, C)
     _flag(range_flag)
     _dev(X, gate, identity, out, range_flag)
-    Y = out if out is not None else torch.empty((B * HW, 2, C), dtype=torch.uint16, device=X.device)
+    Y = out if out is not None else fmt.empty(B * HW, C, X.device)
     a = N.ImgApplyArgs()
     a.B, a.HW, a.C = B, HW, C
-    a.X, a.ldx, a.gate, a.R, a.ldr = _p(X), 2 * C, _p(gate), _p(identity), 2 * C
-    a.Y, a.ldy, a.range_flag = _p(Y), 2 * C, _p(range_flag)
-    _check(lib().cmt_img_ese_apply(ctypes.byref(a), _stream()), "cmt_img_ese_apply")
+    a.X, a.ldx, a.gate, a.R, a.ldr = _p(X), fmt.words * C, _p(gate), _p(identity), fmt.words * C
+    a.Y, a.ldy, a.range_flag = _p(Y), fmt.words * C, _p(range_flag)
+    fmt.call("ese_apply", a)
     return Y
 
 
-def maxpool(X, *, B, H, W, C, out=None):
-    """cmt_img_maxpool: 3 x 3 / stride 2 / ceil-mode / no-pad max, pair rows [B*H*W, 2, C] -> [B*Ho*Wo, 2, C]
-    with (Ho, Wo) = pool_hw(H, W)"""
+def _maxpool(fmt, X, *, B, H, W, C, out=None):
+    """cmt_img_maxpool[_f16]: 3 x 3 / stride 2 / ceil-mode / no-pad max, rows of width C for B*H*W pixels -> rows
+    for B*Ho*Wo with (Ho, Wo) = pool_hw(H, W).  Pair rows (``maxpool``) or fp16 rows (``maxpool_f16``)."""
     _positive(B=B)
     Ho, Wo = pool_hw(H, W)
     if C <= 0 or C % 8:
         raise ValueError(f"C must be a positive multiple of 8, got {C}")
     if B * H * W >= 2 ** 31:
         raise ValueError("B*H*W must be below 2^31")
-    _pair_rows("X", X, B * H * W, C)
+    fmt.check("X", X, B * H * W, C)
     if out is not None:
-        _pair_rows("out", out, B * Ho * Wo, C)
+        fmt.check("out", out, B * Ho * Wo, C)
     _dev(X, out)
-    Y = out if out is not None else torch.empty((B * Ho * Wo, 2, C), dtype=torch.uint16, device=X.device)
+    Y = out if out is not None else fmt.empty(B * Ho * Wo, C, X.device)
     a = N.ImgPoolArgs()
     a.B, a.H, a.W, a.C = B, H, W, C
-    a.X, a.ldx, a.Y, a.ldy = _p(X), 2 * C, _p(Y), 2 * C
-    _check(lib().cmt_img_maxpool(ctypes.byref(a), _stream()), "cmt_img_maxpool")
+    a.X, a.ldx, a.Y, a.ldy = _p(X), fmt.words * C, _p(Y), fmt.words * C
+    fmt.call("maxpool", a)
     return Y
+
+
+stem, stem_f16 = _bind(_stem, PAIR), _bind(_stem, FP16)
+conv3x3, conv3x3_f16 = _bind(_conv3x3, PAIR), _bind(_conv3x3, FP16)
+concat1x1, concat1x1_f16 = _bind(_concat1x1, PAIR), _bind(_concat1x1, FP16)
+ese_apply, ese_apply_f16 = _bind(_ese_apply, PAIR), _bind(_ese_apply, FP16)
+maxpool, maxpool_f16 = _bind(_maxpool, PAIR), _bind(_maxpool, FP16)
 
 
 # ---- the one-pass fp16 policy -------------------------------------------------------------------------------------
@@ -485,206 +564,3 @@ def round_f16(w64):
     if w64.numel() and w64.abs().max().item() > 65504.0:
         raise ValueError("folded weights beyond the f16 range (65504) cannot take the fp16 format")
     return w64.half().contiguous()
-
-
-def pack_stem_f16(w, bn):
-    """pack_stem for cmt_img_stem_f16 -> (fp16 [Cout, 32], fp32 shift [Cout])"""
-    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or not 1 <= w.shape[1] <= 3:
-        raise ValueError(f"expected a (Cout, Cin <= 3, 3, 3) conv weight, got {tuple(w.shape)}")
-    scale, shift = fold_bn(*bn)
-    w64 = (w.detach().double() * scale[:, None, None, None]).permute(0, 2, 3, 1).reshape(w.shape[0], -1)
-    rows = torch.zeros((w.shape[0], STEM_K), dtype=torch.float64, device=w.device)
-    rows[:, :w64.shape[1]] = w64
-    return round_f16(rows), shift.float().contiguous()
-
-
-def pack_conv3x3_f16(w, bn):
-    """native_bev.pack_conv3x3 for cmt_img_conv3x3_f16 -> (fp16 [Cout, 9 Cin] with k = (ky*3 + kx) * Cin + c,
-    fp32 shift [Cout])"""
-    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3):
-        raise ValueError(f"expected a (Cout, Cin, 3, 3) conv weight, got {tuple(w.shape)}")
-    scale, shift = fold_bn(*bn)
-    w64 = w.detach().double() * scale[:, None, None, None]
-    return round_f16(w64.permute(0, 2, 3, 1).reshape(w.shape[0], -1)), shift.float().contiguous()
-
-
-def pack_concat_f16(w, bn):
-    """pack_concat for cmt_img_concat1x1_f16 -> (fp16 [Cout, K] in the concatenation's channel order, fp32 shift)"""
-    if not isinstance(bn, (list, tuple)) or len(bn) != 5:
-        raise ValueError("bn must be (weight, bias, running_mean, running_var, eps)")
-    if w.dim() != 4 or tuple(w.shape[2:]) != (1, 1):
-        raise ValueError(f"expected a (Cout, Cin, 1, 1) conv weight, got {tuple(w.shape)}")
-    scale, shift = fold_bn(*bn)
-    w64 = w.detach().double().reshape(w.shape[0], w.shape[1]) * scale[:, None]
-    return round_f16(w64), shift.float().contiguous()
-
-
-def _rows16(name, t, rows, C):
-    if t.dtype != torch.float16 or t.dim() != 2 or t.shape[1] != C or t.shape[0] < rows or not t.is_contiguous():
-        raise ValueError(f"{name} must be contiguous fp16 rows [>= {rows}, {C}], got {t.dtype} {tuple(t.shape)}")
-
-
-def stem_f16(x, W16, shift, *, Cout, relu=True, out=None, range_flag=None):
-    """cmt_img_stem_f16: the 3 x 3 / stride 2 / pad 1 conv of the fp32 NCHW image [B, Cin <= 3, H, W] (a strided
-    batch axis is taken as it is) -> fp16 rows [B*Ho*Wo, Cout] (rows beyond stay untouched)"""
-    if x.dim() != 4 or x.dtype != torch.float32:
-        raise ValueError("x must be an fp32 [B, C, H, W] image")
-    B, Cin, H, W = (int(s) for s in x.shape)
-    if min(B, H, W) <= 0 or not 1 <= Cin <= 3 or Cout <= 0 or Cout % 32:
-        raise ValueError(f"a non-empty image with 1 <= Cin <= 3 and Cout % 32 == 0 required, got {tuple(x.shape)} "
-                         f"and Cout {Cout}")
-    bstride = int(x.stride(0)) if B > 1 else Cin * H * W
-    if tuple(x.stride()[1:]) != (H * W, W, 1) or bstride < Cin * H * W:
-        raise ValueError("every image of x must be contiguous [C, H, W] at a batch stride >= C*H*W")
-    if B * H * W >= 2 ** 31:
-        raise ValueError("B*H*W must be below 2^31")
-    Ho, Wo = out_hw(H, W, 2)
-    _rows16("W16", W16, Cout, STEM_K)
-    if W16.shape[0] != Cout:
-        raise ValueError(f"W16 must hold {Cout} rows, got {W16.shape[0]}")
-    _shift(shift, Cout)
-    _flag(range_flag)
-    if out is not None:
-        _rows16("out", out, B * Ho * Wo, Cout)
-    _dev(x, W16, shift, out, range_flag)
-    Y = out if out is not None else torch.empty((B * Ho * Wo, Cout), dtype=torch.float16, device=x.device)
-    a = N.ImgStemArgs()
-    a.B, a.H, a.W, a.Cin, a.Cout, a.relu = B, H, W, Cin, Cout, int(bool(relu))
-    a.X, a.x_bstride, a.Wt, a.shift = _p(x), bstride, _p(W16), _p(shift)
-    a.Y, a.ldy, a.range_flag = _p(Y), Cout, _p(range_flag)
-    _check(lib().cmt_img_stem_f16(ctypes.byref(a), _stream()), "cmt_img_stem_f16")
-    return Y
-
-
-def _ld16(name, t, rows, C):
-    """fp16 rows [>= rows, C], possibly a column slice of a wider row buffer -> the leading dimension"""
-    if t.dtype != torch.float16 or t.dim() != 2 or t.shape[1] != C or t.shape[0] < rows:
-        raise ValueError(f"{name} must be fp16 rows [>= {rows}, {C}], got {t.dtype} {tuple(t.shape)}")
-    ld = int(t.stride(0)) if t.shape[0] > 1 else max(int(t.stride(0)), C)
-    if t.stride(1) != 1 or ld < C or ld % 8:
-        raise ValueError(f"{name}: a row must be C contiguous words at a leading dimension >= C, % 8; got strides "
-                         f"{tuple(t.stride())}")
-    return ld
-
-
-def conv3x3_f16(X, W16, shift, *, B, H, W, Cin, Cout, stride, relu=True, out=None, range_flag=None, nb=0):
-    """cmt_img_conv3x3_f16: fp16 rows [B*H*W, Cin] -> fp16 rows [B*Ho*Wo, Cout] (rows beyond stay untouched);
-    Cin % 32 == 0, Cout % 32 == 0, Cout <= 256, any width.  X and out may be column slices of wider row buffers
-    (leading dimension % 8).  ``nb`` as in conv3x3: the result does not depend on it."""
-    if nb < 0 or (nb and Cout > 0 and (Cout // 32) % nb):
-        raise ValueError(f"nb must be 0 or a divisor of Cout / 32 = {Cout // 32}, got {nb}")
-    if min(B, H, W) <= 0:
-        raise ValueError(f"B, H and W must be positive, got {(B, H, W)}")
-    if stride not in (1, 2):
-        raise ValueError(f"stride must be 1 or 2, got {stride}")
-    if Cin <= 0 or Cin % 32 or Cout <= 0 or Cout % 32 or Cout > 256:
-        raise ValueError(f"Cin and Cout must be multiples of 32, Cout at most 256, got {Cin} and {Cout}")
-    if B * H * W >= 2 ** 31:
-        raise ValueError("B*H*W must be below 2^31")
-    Ho, Wo = out_hw(H, W, stride)
-    ldx = _ld16("X", X, B * H * W, Cin)
-    _rows16("W16", W16, Cout, 9 * Cin)
-    if W16.shape[0] != Cout:
-        raise ValueError(f"W16 must hold {Cout} rows, got {W16.shape[0]}")
-    _shift(shift, Cout)
-    _flag(range_flag)
-    ldy = Cout if out is None else _ld16("out", out, B * Ho * Wo, Cout)
-    _dev(X, W16, shift, out, range_flag)
-    Y = out if out is not None else torch.empty((B * Ho * Wo, Cout), dtype=torch.float16, device=X.device)
-    a = N.ImgConvArgs()
-    a.B, a.H, a.W, a.Cin, a.Cout, a.stride, a.relu, a.nb = B, H, W, Cin, Cout, stride, int(bool(relu)), nb
-    a.X, a.ldx, a.Wt, a.ldw, a.shift = _p(X), ldx, _p(W16), 9 * Cin, _p(shift)
-    a.Y, a.ldy, a.range_flag = _p(Y), ldy, _p(range_flag)
-    _check(lib().cmt_img_conv3x3_f16(ctypes.byref(a), _stream()), "cmt_img_conv3x3_f16")
-    return Y
-
-
-def concat1x1_f16(sources, W16, shift, *, B, HW, Cout, relu=True, out=None, part=None, range_flag=None):
-    """cmt_img_concat1x1_f16: the 1 x 1 conv of the channel concatenation of up to 8 fp16 ``sources`` ([B*HW, C_s]
-    each, possibly a column slice of a wider row buffer) -> fp16 rows [B*HW, Cout].  ``part`` as in concat1x1: the
-    fp32 per-tile column sums of the fp16 values as stored.  Returns (rows, part)."""
-    sources = list(sources)
-    if not 1 <= len(sources) <= MAX_SRC:
-        raise ValueError(f"1 to {MAX_SRC} sources required, got {len(sources)}")
-    _positive(B=B, HW=HW)
-    if Cout <= 0 or Cout % 128:
-        raise ValueError(f"Cout must be a positive multiple of 128, got {Cout}")
-    if B * HW >= 2 ** 31 or B > 65535:
-        raise ValueError("B*HW must be below 2^31 and B at most 65535")
-    dims = []
-    for i, t in enumerate(sources):
-        C = int(t.shape[1]) if torch.is_tensor(t) and t.dim() == 2 else 0
-        if C <= 0 or C % 32:
-            raise ValueError(f"source {i} must be fp16 rows [>= {B * HW}, C] with C a positive multiple of 32, got "
-                             f"{tuple(t.shape) if torch.is_tensor(t) else type(t)}")
-        dims.append((C, _ld16(f"source {i}", t, B * HW, C)))
-    K = sum(c for c, _ in dims)
-    _rows16("W16", W16, Cout, K)
-    if W16.shape[0] != Cout:
-        raise ValueError(f"W16 must hold {Cout} rows, got {W16.shape[0]}")
-    _shift(shift, Cout)
-    _flag(range_flag)
-    if out is not None:
-        _rows16("out", out, B * HW, Cout)
-    tiles = concat_tiles(HW)
-    if part is not None and part is not True:
-        _f32("part", part, (B, tiles, Cout))
-    _dev(*sources, W16, shift, out, None if part is True else part, range_flag)
-    dev = sources[0].device
-    Y = out if out is not None else torch.empty((B * HW, Cout), dtype=torch.float16, device=dev)
-    if part is True:
-        part = torch.empty((B, tiles, Cout), dtype=torch.float32, device=dev)
-    a = N.ImgConcatArgs()
-    a.B, a.HW, a.Cout, a.nsrc, a.relu = B, HW, Cout, len(sources), int(bool(relu))
-    for i, (t, (c, ld)) in enumerate(zip(sources, dims)):
-        a.C[i], a.X[i], a.ldx[i] = c, t.data_ptr(), ld
-    a.Wt, a.ldw, a.shift = _p(W16), K, _p(shift)
-    a.Y, a.ldy, a.part, a.range_flag = _p(Y), Cout, _p(part), _p(range_flag)
-    _check(lib().cmt_img_concat1x1_f16(ctypes.byref(a), _stream()), "cmt_img_concat1x1_f16")
-    return Y, part
-
-
-def ese_apply_f16(X, gate, *, B, HW, C, identity=None, out=None, range_flag=None):
-    """cmt_img_ese_apply_f16: fp16 rows x [B*HW, C] times gate [B, C] (plus the fp16 rows ``identity``), in fp32,
-    rounded once -> fp16 rows; ``out`` may be X (in place)"""
-    _positive(B=B, HW=HW)
-    if C <= 0 or C % 8:
-        raise ValueError(f"C must be a positive multiple of 8, got {C}")
-    if B * HW >= 2 ** 31:
-        raise ValueError("B*HW must be below 2^31")
-    _rows16("X", X, B * HW, C)
-    _f32("gate", gate, (B, C))
-    if identity is not None:
-        _rows16("identity", identity, B * HW, C)
-    if out is not None:
-        _rows16("out", out, B * HW, C)
-    _flag(range_flag)
-    _dev(X, gate, identity, out, range_flag)
-    Y = out if out is not None else torch.empty((B * HW, C), dtype=torch.float16, device=X.device)
-    a = N.ImgApplyArgs()
-    a.B, a.HW, a.C = B, HW, C
-    a.X, a.ldx, a.gate, a.R, a.ldr = _p(X), C, _p(gate), _p(identity), C
-    a.Y, a.ldy, a.range_flag = _p(Y), C, _p(range_flag)
-    _check(lib().cmt_img_ese_apply_f16(ctypes.byref(a), _stream()), "cmt_img_ese_apply_f16")
-    return Y
-
-
-def maxpool_f16(X, *, B, H, W, C, out=None):
-    """cmt_img_maxpool_f16: 3 x 3 / stride 2 / ceil-mode / no-pad max, fp16 rows [B*H*W, C] -> [B*Ho*Wo, C] with
-    (Ho, Wo) = pool_hw(H, W)"""
-    _positive(B=B)
-    Ho, Wo = pool_hw(H, W)
-    if C <= 0 or C % 8:
-        raise ValueError(f"C must be a positive multiple of 8, got {C}")
-    if B * H * W >= 2 ** 31:
-        raise ValueError("B*H*W must be below 2^31")
-    _rows16("X", X, B * H * W, C)
-    if out is not None:
-        _rows16("out", out, B * Ho * Wo, C)
-    _dev(X, out)
-    Y = out if out is not None else torch.empty((B * Ho * Wo, C), dtype=torch.float16, device=X.device)
-    a = N.ImgPoolArgs()
-    a.B, a.H, a.W, a.C = B, H, W, C
-    a.X, a.ldx, a.Y, a.ldy = _p(X), C, _p(Y), C
-    _check(lib().cmt_img_maxpool_f16(ctypes.byref(a), _stream()), "cmt_img_maxpool_f16")
-    return Y

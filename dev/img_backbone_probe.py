@@ -178,7 +178,7 @@ def main():
         names = dict(stem_f16=NI, conv3x3_f16=NI, concat1x1_f16=NI, ese_gate=NI, ese_apply_f16=NI, maxpool_f16=NI,
                      rows_to_nchw_f16=NF) if f16 else \
             dict(stem=NI, conv3x3=NI, conv3x3_gemm=NI, concat1x1=NI, ese_gate=NI, ese_apply=NI, maxpool=NI, rows_to_nchw=NF)
-        osa_name = "_osa_f16" if f16 else "_osa"
+        osa_name = "_osa"
         real = {k: getattr(mod, k) for k, mod in names.items()}
         events, stage = [], ["stem"]
 
