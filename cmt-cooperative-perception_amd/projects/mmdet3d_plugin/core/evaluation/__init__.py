@@ -1,0 +1,261 @@
+"""nuScenes-style detection evaluation (AP per distance threshold, the four TP errors, NDS) for boxes on the device.
+
+The arithmetic is the contract of ``cmt_det_eval_*`` in include/cmt_hip.h (csrc/deteval.hip), a restatement of the
+evaluator the reference carries in its dataset class (a9coop_dataset.py: accumulate, cummean, calc_ap, calc_tp,
+filter_eval_boxes, _evaluate_a9_nusc).  ``DetectionEvaluator`` collects frames in device buffers without a host
+read; ``compute()`` runs sort -> match -> curves on the device and reads back C x T APs and C x 4 errors, the means
+over them (nine classes, four numbers each) are float64 on the host.
+"""
+import math
+from dataclasses import dataclass
+from typing import Sequence
+
+import numpy as np
+import torch
+
+from ... import native_eval as NE
+
+__all__ = ["DetEvalConfig", "tumtraf_eval_config", "nuscenes_eval_config", "DetectionEvaluator", "summarize", "TUMTRAF_CLASSES",
+           "TP_METRICS", "ERR_NAME_MAPPING"]
+
+TUMTRAF_CLASSES = ("CAR", "TRAILER", "TRUCK", "VAN", "PEDESTRIAN", "BUS", "MOTORCYCLE", "BICYCLE", "EMERGENCY_VEHICLE")
+_TUMTRAF_RANGE = {"CAR": 50, "TRUCK": 50, "BUS": 50, "TRAILER": 50, "VAN": 50, "EMERGENCY_VEHICLE": 50,
+                  "PEDESTRIAN": 40, "MOTORCYCLE": 40, "BICYCLE": 40}
+TP_METRICS = ("trans_err", "scale_err", "orient_err", "vel_err")   # the reference's order in its dictionaries
+ERR_NAME_MAPPING = {"trans_err": "mATE", "scale_err": "mASE", "orient_err": "mAOE", "vel_err": "mAVE"}
+CURVE_NAMES = ("recall", "precision", "confidence") + NE.ERR_NAMES
+
+
+@dataclass
+class DetEvalConfig:
+    """The evaluation constants.  ``class_range`` and ``yaw_period`` follow ``class_names``; ``gt_velocity_zero``
+    replaces the ground truth's velocity by zero, as the reference's load_gt does."""
+    class_names: Sequence[str]
+    class_range: Sequence[float]
+    yaw_period: Sequence[float]
+    dist_ths: Sequence[float] = (0.5, 1.0, 2.0, 4.0)
+    dist_th_tp: float = 2.0
+    min_recall: float = 0.1
+    min_precision: float = 0.1
+    mean_ap_weight: float = 5.0
+    max_boxes_per_sample: int = 500
+    gt_velocity_zero: bool = False
+
+    def __post_init__(self):
+        self.class_names = tuple(self.class_names)
+        if len(self.class_names) != len(tuple(self.class_range)):
+            raise ValueError(f"{len(self.class_names)} class names but {len(tuple(self.class_range))} class ranges")
+        NE.check_config(self.class_range, self.yaw_period, self.dist_ths, self.dist_th_tp,
+                        self.min_recall, self.min_precision)
+        if not 1 <= int(self.max_boxes_per_sample) <= NE.MAX_PER_SAMPLE:
+            raise ValueError(f"max_boxes_per_sample must be in [1, {NE.MAX_PER_SAMPLE}], got {self.max_boxes_per_sample}")
+        if not math.isfinite(self.mean_ap_weight) or self.mean_ap_weight < 0:
+            raise ValueError(f"mean_ap_weight must be finite and >= 0, got {self.mean_ap_weight}")
+
+
+def tumtraf_eval_config(class_names=TUMTRAF_CLASSES):
+    """The reference's A9 / TUMTraf constants: class ranges 50 / 40 m, thresholds 0.5 / 1 / 2 / 4 m, TP errors at
+    2 m, min recall = min precision = 0.1, mAP weight 5, at most 500 boxes per sample, period 2 pi for every class
+    (none is called 'barrier'), ground-truth velocity zero."""
+    names = tuple(class_names)
+    unknown = [n for n in names if n not in _TUMTRAF_RANGE]
+    if unknown:
+        raise ValueError(f"no TUMTraf class range for {unknown}")
+    return DetEvalConfig(class_names=names, class_range=[float(_TUMTRAF_RANGE[n]) for n in names],
+                         yaw_period=[2 * math.pi] * len(names), gt_velocity_zero=True)
+
+
+# nuScenes detection_cvpr_2019 class ranges (the devkit's public configuration file)
+_NUSCENES_RANGE = {"car": 50, "truck": 50, "bus": 50, "trailer": 50, "construction_vehicle": 50, "pedestrian": 40,
+                   "motorcycle": 40, "bicycle": 40, "traffic_cone": 30, "barrier": 30}
+
+
+def nuscenes_eval_config(class_names):
+    """The nuScenes detection constants: class ranges 50 / 40 / 30 m, the same thresholds, and a barrier's
+    orientation known up to pi only.  The attribute error and the per-class ignored errors of the devkit are not
+    part of this evaluator."""
+    names = tuple(class_names)
+    unknown = [n for n in names if n not in _NUSCENES_RANGE]
+    if unknown:
+        raise ValueError(f"no nuScenes class range for {unknown}")
+    return DetEvalConfig(class_names=names, class_range=[float(_NUSCENES_RANGE[n]) for n in names],
+                         yaw_period=[math.pi if n == "barrier" else 2 * math.pi for n in names])
+
+
+def summarize(cfg, ap, tp_err):
+    """The reference's metrics_summary from ap [C, T] and tp_err [C, 4] (columns trans, vel, scale, orient), in
+    float64 on the host."""
+    ap = np.asarray(ap, dtype=np.float64)
+    tp_err = np.asarray(tp_err, dtype=np.float64)
+    ths = [float(t) for t in cfg.dist_ths]
+    col = {n: i for i, n in enumerate(NE.ERR_NAMES)}
+    label_aps = {n: {t: float(ap[c, k]) for k, t in enumerate(ths)} for c, n in enumerate(cfg.class_names)}
+    label_tp = {n: {m: float(tp_err[c, col[m]]) for m in TP_METRICS} for c, n in enumerate(cfg.class_names)}
+    mean_dist_aps = {n: float(np.mean(list(d.values()))) for n, d in label_aps.items()}
+    mean_ap = float(np.mean(list(mean_dist_aps.values())))
+    tp_errors = {m: float(np.nanmean([label_tp[n][m] for n in cfg.class_names])) for m in TP_METRICS}
+    tp_scores = {m: max(0.0, 1.0 - tp_errors[m]) for m in TP_METRICS}
+    nd = float(cfg.mean_ap_weight * mean_ap + np.sum(list(tp_scores.values())))
+    nd = nd / float(cfg.mean_ap_weight + len(tp_scores))
+    return dict(label_aps=label_aps, mean_dist_aps=mean_dist_aps, mean_ap=mean_ap, label_tp_errors=label_tp,
+                tp_errors=tp_errors, tp_scores=tp_scores, nd_score=nd)
+
+
+class DetectionEvaluator:
+    """Collects detections and ground truth frame by frame on the device and scores them.
+
+    ``capacity_frames`` frames of at most ``cfg.max_boxes_per_sample`` predictions fit; the prediction buffers are
+    allocated once, ``add`` copies into them on the device and reads nothing back."""
+
+    def __init__(self, cfg: DetEvalConfig, capacity_frames: int, device):
+        if not isinstance(cfg, DetEvalConfig):
+            raise ValueError("cfg must be a DetEvalConfig")
+        if not 1 <= int(capacity_frames) <= NE.MAX_SAMPLES:
+            raise ValueError(f"capacity_frames must be in [1, 2^24], got {capacity_frames}")
+        self.cfg = cfg
+        self.capacity_frames = int(capacity_frames)
+        self.device = torch.device(device)
+        rows = self.capacity_frames * int(cfg.max_boxes_per_sample)
+        if rows >= 2 ** 31:
+            raise ValueError("capacity_frames * max_boxes_per_sample must be below 2^31")
+        self._rows = rows
+        self._buf = None
+        self.reset()
+
+    def reset(self):
+        self._frames = 0
+        self._n = 0
+        self._gt = []          # (boxes, labels, samples, num_pts) per frame
+        self._gt_cat = None    # their concatenation, built by the first run after an add
+        self._result = None
+
+    def _alloc(self):
+        if self._buf is None:
+            d, n = self.device, self._rows
+            self._buf = dict(box=torch.empty((n, 9), dtype=torch.float32, device=d),
+                             score=torch.empty(n, dtype=torch.float32, device=d),
+                             label=torch.empty(n, dtype=torch.int32, device=d),
+                             sample=torch.empty(n, dtype=torch.int32, device=d))
+
+    def add(self, boxes, scores, labels, count=None, gt_boxes=None, gt_labels=None, gt_num_pts=None):
+        """One or more frames.  ``boxes`` [B, max_num, 9] / ``scores`` / ``labels`` [B, max_num] with the device
+        ``count`` [B] of ``box_decode``, or the ``get_bboxes`` tuple of one frame ([n, 9], [n], [n], count None).
+        ``gt_boxes`` / ``gt_labels``: one tensor per frame ([g, 9] and [g]; a bare tensor for one frame),
+        ``gt_num_pts`` likewise or None (unknown: every box counts)."""
+        if not (torch.is_tensor(boxes) and torch.is_tensor(scores) and torch.is_tensor(labels)):
+            raise ValueError("boxes, scores and labels must be tensors")
+        if boxes.dim() == 2:
+            boxes, scores, labels = boxes[None], scores[None], labels[None]
+        if boxes.dim() != 3 or boxes.shape[-1] != 9 or tuple(scores.shape) != tuple(boxes.shape[:2]) or \
+                tuple(labels.shape) != tuple(boxes.shape[:2]):
+            raise ValueError(f"boxes must be [B, n, 9] with scores and labels [B, n], got {tuple(boxes.shape)}, "
+                             f"{tuple(scores.shape)}, {tuple(labels.shape)}")
+        if boxes.dtype != torch.float32 or scores.dtype != torch.float32:
+            raise ValueError("boxes and scores must be fp32")
+        if labels.dtype not in (torch.int32, torch.int64):
+            raise ValueError("labels must be int32 or int64")
+        B, M = int(boxes.shape[0]), int(boxes.shape[1])
+        if M > int(self.cfg.max_boxes_per_sample):
+            raise ValueError(f"only <= {self.cfg.max_boxes_per_sample} boxes per sample allowed, got {M}")
+        if count is not None and (not torch.is_tensor(count) or count.dtype != torch.int32 or count.numel() != B):
+            raise ValueError(f"count must be int32 [{B}]")
+        if gt_boxes is None or gt_labels is None:
+            raise ValueError("gt_boxes and gt_labels are required")
+        if torch.is_tensor(gt_boxes):
+            gt_boxes, gt_labels = [gt_boxes], [gt_labels]
+            gt_num_pts = None if gt_num_pts is None else [gt_num_pts]
+        gt_boxes, gt_labels = list(gt_boxes), list(gt_labels)
+        gt_num_pts = [None] * B if gt_num_pts is None else list(gt_num_pts)
+        if not len(gt_boxes) == len(gt_labels) == len(gt_num_pts) == B:
+            raise ValueError(f"{B} frames of predictions but {len(gt_boxes)} / {len(gt_labels)} / {len(gt_num_pts)} "
+                             "of ground truth")
+        for b, l, q in zip(gt_boxes, gt_labels, gt_num_pts):
+            if not torch.is_tensor(b) or b.dim() != 2 or b.shape[1] != 9 or b.dtype != torch.float32:
+                raise ValueError("every gt_boxes entry must be fp32 [g, 9]")
+            if not torch.is_tensor(l) or tuple(l.shape) != (b.shape[0],) or l.dtype not in (torch.int32, torch.int64):
+                raise ValueError("every gt_labels entry must be int [g]")
+            if q is not None and (not torch.is_tensor(q) or tuple(q.shape) != (b.shape[0],) or
+                                  q.dtype not in (torch.int32, torch.int64)):
+                raise ValueError("every gt_num_pts entry must be int [g] or None")
+        if self._frames + B > self.capacity_frames:
+            raise ValueError(f"capacity of {self.capacity_frames} frames exceeded")
+        tensors = [boxes, scores, labels] + gt_boxes + gt_labels + [q for q in gt_num_pts if q is not None]
+        if count is not None:
+            tensors.append(count)
+        if any(not t.is_cuda for t in tensors):
+            raise ValueError("the evaluator needs its tensors on a HIP device (no CPU path)")
+        self._alloc()
+        dev = self.device
+        lab = labels.to(device=dev, dtype=torch.int32)
+        if count is not None:   # rows at or beyond a frame's count do not exist: label -1
+            live = torch.arange(M, device=dev, dtype=torch.int32)[None, :] < count.to(dev).reshape(B, 1)
+            lab = torch.where(live, lab, torch.full_like(lab, -1))
+        n0, n1 = self._n, self._n + B * M
+        self._buf["box"][n0:n1].copy_(boxes.reshape(B * M, 9))
+        self._buf["score"][n0:n1].copy_(scores.reshape(B * M))
+        self._buf["label"][n0:n1].copy_(lab.reshape(B * M))
+        frame = torch.arange(self._frames, self._frames + B, device=dev, dtype=torch.int32)
+        self._buf["sample"][n0:n1].copy_(frame[:, None].expand(B, M).reshape(B * M))
+        for i, (b, l, q) in enumerate(zip(gt_boxes, gt_labels, gt_num_pts)):
+            g = int(b.shape[0])
+            b = b.to(dev)
+            if self.cfg.gt_velocity_zero:
+                b = b.clone()
+                b[:, 7:9] = 0
+            num = torch.full((g,), -1, dtype=torch.int32, device=dev) if q is None else q.to(device=dev, dtype=torch.int32)
+            self._gt.append((b.contiguous(), l.to(device=dev, dtype=torch.int32),
+                             torch.full((g,), self._frames + i, dtype=torch.int32, device=dev), num))
+        self._n, self._frames = n1, self._frames + B
+        self._result = self._gt_cat = None
+
+    # ---- results -------------------------------------------------------------------------------------
+
+    def run(self, events=None):
+        """sort -> match -> curves on the device -> the dict of device tensors of ``native_eval.det_eval``"""
+        if self._frames == 0:
+            raise ValueError("no frame was added")
+        dev, cfg = self.device, self.cfg
+        if self._gt_cat is None:
+            self._gt_cat = tuple(torch.cat([g[k] for g in self._gt]).contiguous() for k in range(4))
+        gb, gl, gs, gn = self._gt_cat
+        n = self._n
+        buf = self._buf
+        self._result = NE.det_eval(buf["box"][:n], buf["score"][:n], buf["label"][:n], buf["sample"][:n], gb, gl, gs, gn,
+                                   num_samples=self._frames, class_range=cfg.class_range, yaw_period=cfg.yaw_period,
+                                   dist_ths=cfg.dist_ths, dist_th_tp=cfg.dist_th_tp, min_recall=cfg.min_recall,
+                                   min_precision=cfg.min_precision, events=events)
+        return self._result
+
+    def compute(self):
+        """The reference's metrics_summary: label_aps, mean_dist_aps, mean_ap, label_tp_errors, tp_errors,
+        tp_scores, nd_score."""
+        res = self.run()
+        return summarize(self.cfg, res["ap"].cpu().numpy(), res["tp_err"].cpu().numpy())
+
+    def detail(self):
+        """The ``object/...`` dictionary of the reference's _evaluate_single (values rounded to four decimals,
+        nds and map as they are)."""
+        m = self.compute() if self._result is None else summarize(self.cfg, self._result["ap"].cpu().numpy(),
+                                                                   self._result["tp_err"].cpu().numpy())
+        detail = dict()
+        for name in self.cfg.class_names:
+            for k, v in m["label_aps"][name].items():
+                detail["object/{}_ap_dist_{}".format(name, k)] = float("{:.4f}".format(v))
+            for k, v in m["label_tp_errors"][name].items():
+                detail["object/{}_{}".format(name, k)] = float("{:.4f}".format(v))
+            for k, v in m["tp_errors"].items():
+                detail["object/{}".format(ERR_NAME_MAPPING[k])] = float("{:.4f}".format(v))
+        detail["object/nds"] = m["nd_score"]
+        detail["object/map"] = m["mean_ap"]
+        return detail
+
+    def metric_data(self):
+        """The seven 101-point curves per (class, threshold), keyed ``'<class>:<threshold>'`` as the reference's
+        metrics_details.json."""
+        res = self.run() if self._result is None else self._result
+        md = res["md"].cpu().numpy()
+        out = dict()
+        for c, name in enumerate(self.cfg.class_names):
+            for k, th in enumerate(self.cfg.dist_ths):
+                out[name + ":" + str(float(th))] = {cn: md[c, k, i].tolist() for i, cn in enumerate(CURVE_NAMES)}
+        return out

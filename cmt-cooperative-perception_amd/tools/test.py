@@ -17,6 +17,13 @@ the same "at least one of --out / --eval / --format-only" check and the same
   (``core/openlabel.py``, the reference's inference_to_openlabel_coop.py);
 * ``--eval bbox`` has no annotations offline: it prints detection / voxel
   statistics instead of nuScenes AP;
+* ``--eval nds`` (alone or with ``bbox``) scores the boxes against synthetic
+  ground truth (``synthetic_gt`` seeded by seed and frame, 20 boxes per frame)
+  with ``DetectionEvaluator``: every frame's device boxes go into the
+  evaluator's device buffers and the reference's metrics summary (label_aps,
+  mean_ap, tp_errors, nd_score, ...) is printed as one more JSON line after
+  the statistics line.  With random weights the score says nothing about a
+  model; the path is the one a dataset's ground truth would take;
 * ``--launcher pytorch``: frames are sharded over ranks (frame i on rank
   i % world) and rank 0 gathers the results (all_gather_object), as
   multi_gpu_test's result collection.
@@ -64,7 +71,9 @@ def parse_args(argv=None):
     p.add_argument("--out", help="output result file (JSON)")
     p.add_argument("--format-only", action="store_true", help="format the results (OpenLABEL) without evaluation")
     p.add_argument("--openlabel-dir", default="openlabel_out", help="OpenLABEL output folder for --format-only")
-    p.add_argument("--eval", type=str, nargs="+", help="evaluation metrics (bbox: detection statistics)")
+    p.add_argument("--eval", type=str, nargs="+",
+                   help="evaluation metrics (bbox: detection statistics; nds: nuScenes-style AP / TP errors / NDS "
+                        "against synthetic ground truth, on the device)")
     p.add_argument("--synthetic", action="store_true", help="synthetic frames of the config's shapes (required)")
     p.add_argument("--frames", type=int, default=1, help="synthetic frames")
     p.add_argument("--num-query", type=int, default=None, help="override num_query (config 1: 32)")
@@ -264,6 +273,29 @@ def detector_frame_inputs(name, cfg, meta, frame, args, device):
     return kw, points
 
 
+GT_PER_FRAME = 20
+
+
+def eval_pc_range(name):
+    from projects.mmdet3d_plugin import synthetic as S
+    return S.make_head_cfg(name)[1]["point_cloud_range"]
+
+
+def frame_ground_truth(frame, seed, pc_range, num_classes):
+    """the synthetic ground truth of one frame -> (boxes [20, 9] fp32, labels [20] int64), on the host"""
+    from projects.mmdet3d_plugin import synthetic as S
+    boxes, labels = S.synthetic_gt(1, pc_range, num_classes, n=GT_PER_FRAME, seed=seed + 1000 * frame)
+    return boxes[0].float(), labels[0]
+
+
+def eval_config(class_names):
+    """TUMTraf constants for TUMTraf class names, the nuScenes detection constants otherwise"""
+    from projects.mmdet3d_plugin.core import evaluation as E
+    if all(n in E.TUMTRAF_CLASSES for n in class_names):
+        return E.tumtraf_eval_config(class_names)
+    return E.nuscenes_eval_config(class_names)
+
+
 def run_frame(head, name, feats, metas):
     if name.startswith("cmtcoop"):
         (xv, iv), (xi_, ii) = feats
@@ -326,6 +358,19 @@ def _run(args, name, device, rank, world, distributed):
                              max_num_points=vcfg["max_num_points"], max_voxels=vcfg["max_voxels"],
                              num_point_features=vcfg["num_point_features"]).eval()
     class_names = list(cfg["tasks"][0]["class_names"])
+    want_nds = bool(args.eval) and "nds" in args.eval
+    evaluator = None
+    if want_nds:
+        from projects.mmdet3d_plugin.core.evaluation import DetectionEvaluator
+        pcr = meta["point_cloud_range"]
+        if rank == 0:
+            evaluator = DetectionEvaluator(eval_config(class_names), max(args.frames, 1), device)
+
+    def feed(frame, boxes, scores, labels):
+        gb, gl = frame_ground_truth(frame, args.seed, pcr, len(class_names))
+        # the head's boxes are on the device already; the detector's result dict (bbox3d2result) is on the host
+        evaluator.add(boxes.to(device), scores.to(device), labels.to(device), None, gb.to(device), gl.to(device))
+
     results = []
     t0 = time.perf_counter()
     with torch.no_grad():
@@ -344,6 +389,8 @@ def _run(args, name, device, rank, world, distributed):
                 boxes, scores, labels = res["boxes_3d"], res["scores_3d"], res["labels_3d"]
             else:
                 boxes, scores, labels = run_frame(head, name, feats, metas)
+            if want_nds and not distributed:   # the boxes as tensors: no lists, no JSON
+                feed(f, boxes.float(), scores.float(), labels)
             results.append(dict(frame=f, voxels=vox_stats,
                                 boxes_3d=boxes.float().cpu().tolist(), scores_3d=scores.float().cpu().tolist(),
                                 labels_3d=labels.cpu().tolist(),
@@ -384,6 +431,13 @@ def _run(args, name, device, rank, world, distributed):
                      seconds=round(elapsed, 4),
                      note="synthetic frames: no annotations offline, so no nuScenes AP")
         print(json.dumps(stats))
+    if want_nds:
+        if distributed:   # rank 0 evaluates the gathered results
+            for r in results:
+                feed(r["frame"], torch.tensor(r["boxes_3d"], dtype=torch.float32, device=device).reshape(-1, 9),
+                     torch.tensor(r["scores_3d"], dtype=torch.float32, device=device),
+                     torch.tensor(r["labels_3d"], dtype=torch.int64, device=device))
+        print(json.dumps(dict(metric="nds", frames=len(results), gt_per_frame=GT_PER_FRAME, **evaluator.compute())))
     return 0
 
 

@@ -29,12 +29,18 @@ windows of --iters calls; (c) is timed call by call with a host clock.  ``--swee
 the two detector frames (stage ``points``; the end-to-end clock then starts at the raw sweep buffers): use it with
 ``--points`` as the rows per sweep.
 
+``--only eval`` times ``DetectionEvaluator.compute()`` (cmt_det_eval_*: keys, the three sorts, match, curves, by
+device events) on 800 frames x 300 predictions, 9 classes, 4 thresholds and 20 ground-truth boxes per frame (jittered
+ground truth plus false positives) against one run of the contract's numpy restatement (tests/_eval_ref.py, the
+reference's algorithm in its own style of loop) on the host, and checks that both give the same summary.
+
 ``--img-precision`` (default ``ref``) is the image backbone's arithmetic (native_img.set_img_precision): ``fp16``
 runs VoVNet on the one-pass fp16 kernels; everything else is unchanged.
 
     python dev/detector_probe.py [--img-precision ref|fp16] [--points 300000] [--repeats 20] [--warmup 3]
-                                 [--iters 20] [--seed 0] [--out FILE] [--only resize|points] [--resize-out FILE]
-                                 [--points-out FILE] [--sweep-points 27000] [--sweeps K]
+                                 [--iters 20] [--seed 0] [--out FILE] [--only resize|points|eval] [--resize-out FILE]
+                                 [--points-out FILE] [--sweep-points 27000] [--sweeps K] [--eval-out FILE]
+                                 [--eval-frames 800]
 
 Needs a HIP device and the built library; there is no CPU path.
 """
@@ -83,7 +89,9 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--img-precision", choices=("ref", "fp16"), default="ref")
     ap.add_argument("--out", default=None)
-    ap.add_argument("--only", choices=("resize", "points"), default=None, help="run this section alone")
+    ap.add_argument("--only", choices=("resize", "points", "eval"), default=None, help="run this section alone")
+    ap.add_argument("--eval-out", default=None, help="write the detection-evaluation section to this file")
+    ap.add_argument("--eval-frames", type=int, default=800, help="frames of the detection-evaluation section")
     ap.add_argument("--resize-out", default=None, help="write the cmt_img_resize_prepare section to this file")
     ap.add_argument("--points-out", default=None, help="write the cmt_pts_prepare section to this file")
     ap.add_argument("--sweep-points", type=int, default=27000, help="rows per segment of the cmt_pts_prepare section")
@@ -245,6 +253,9 @@ def main():
     if args.only == "points":
         points_section(args, dev, say, lines)
         return
+    if args.only == "eval":
+        eval_section(args, dev, say, lines)
+        return
     frames = frame("cmt_fusion_nus")
     frame("cmtcoop_fusion_tumtraf")
 
@@ -280,6 +291,84 @@ def main():
     say(f"{'torch ops':>22} {fmt(tt)}   native / torch {tn[0] / tt[0]:.2f}")
     resize_section(args, dev, say, lines)
     points_section(args, dev, say, lines)
+
+
+def eval_section(args, dev, say, lines):
+    """DetectionEvaluator.compute() on the device against the numpy restatement of its contract on the host"""
+    import numpy as np
+    from projects.mmdet3d_plugin.core.evaluation import DetectionEvaluator, tumtraf_eval_config
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import _eval_ref as R
+    first = len(lines)
+    S_, M, G, cfg = args.eval_frames, 300, 20, tumtraf_eval_config()
+    C, T = len(cfg.class_names), len(cfg.dist_ths)
+    rng = np.random.RandomState(args.seed)
+    gb = np.zeros((S_, G, 9), np.float32)
+    gb[..., :2] = rng.uniform(-45, 45, (S_, G, 2))
+    gb[..., 2] = rng.uniform(-2, 0, (S_, G))
+    gb[..., 3:6] = rng.uniform(1, 4, (S_, G, 3))
+    gb[..., 6] = rng.uniform(-np.pi, np.pi, (S_, G))
+    gl = rng.randint(0, C, (S_, G))
+    pb = np.zeros((S_, M, 9), np.float32)
+    src = rng.randint(0, G, (S_, M))
+    hit = rng.rand(S_, M) < 0.4                      # jittered ground truth; the rest are false positives
+    take = np.take_along_axis
+    pb[..., :2] = np.where(hit[..., None], take(gb[..., :2], src[..., None], 1) + rng.normal(0, 0.7, (S_, M, 2)),
+                           rng.uniform(-50, 50, (S_, M, 2)))
+    pb[..., 3:6] = take(gb[..., 3:6], src[..., None], 1) * rng.uniform(0.8, 1.25, (S_, M, 3))
+    pb[..., 6] = take(gb[..., 6], src, 1) + rng.normal(0, 0.2, (S_, M))
+    pb[..., 7:9] = rng.normal(0, 0.5, (S_, M, 2))
+    pl = np.where(hit, take(gl, src, 1), rng.randint(0, C, (S_, M))).astype(np.int32)
+    ps = np.where(hit, rng.uniform(0.2, 1.0, (S_, M)), rng.uniform(0.0, 0.6, (S_, M))).astype(np.float32)
+    order = np.argsort(-ps, 1)                       # box_decode's rows come in descending score order
+    pb, pl, ps = take(pb, order[..., None], 1), take(pl, order, 1), take(ps, order, 1)
+    count = torch.full((S_,), M, dtype=torch.int32, device=dev)
+    ev = DetectionEvaluator(cfg, S_, dev)
+    t0 = time.perf_counter()
+    ev.add(torch.from_numpy(pb).to(dev), torch.from_numpy(ps).to(dev), torch.from_numpy(pl).to(dev), count,
+           [torch.from_numpy(gb[s]).to(dev) for s in range(S_)], [torch.from_numpy(gl[s]).to(dev) for s in range(S_)])
+    torch.cuda.synchronize()
+    t_add = time.perf_counter() - t0
+    for _ in range(args.warmup):
+        ev.run()
+    torch.cuda.synchronize()
+    total, phases, host_clock = [], {}, []
+    for _ in range(args.repeats):
+        events = []
+        h0 = time.perf_counter()
+        total.append(event_ms(lambda: ev.run(events=events)))
+        host_clock.append((time.perf_counter() - h0) * 1e3)
+        for name, a, b in events:
+            phases.setdefault(name, []).append(a.elapsed_time(b))
+    got = ev.compute()
+    gz = gb.copy()
+    gz[..., 7:9] = 0                                  # the TUMTraf configuration: ground-truth velocity zero
+    h0 = time.perf_counter()
+    ref = R.evaluate(pb.reshape(-1, 9), ps.reshape(-1), pl.reshape(-1), np.repeat(np.arange(S_), M), gz.reshape(-1, 9),
+                     gl.reshape(-1), np.repeat(np.arange(S_), G), np.full(S_ * G, -1), num_samples=S_,
+                     class_range=cfg.class_range, yaw_period=cfg.yaw_period, dist_ths=cfg.dist_ths,
+                     dist_th_tp=cfg.dist_th_tp, min_recall=cfg.min_recall, min_precision=cfg.min_precision,
+                     mean_ap_weight=cfg.mean_ap_weight)
+    t_host = (time.perf_counter() - h0) * 1e3
+    say(f"--- {torch.cuda.get_device_name(0)}: detection evaluation (cmt_det_eval_*), {S_} frames x {M} predictions "
+        f"({S_ * M} rows), {S_ * G} ground-truth boxes, {C} classes, {T} thresholds; DetectionEvaluator.run(): median "
+        f"of {args.repeats} single calls after {args.warmup} warm-up (min .. max), device events, ms")
+    say(f"{'whole run':>26} {fmt(med(total))}   host clock around it {fmt(med(host_clock))}")
+    for name in ("keys", "sort", "match", "curves"):
+        say(f"{name:>26} {fmt(med(phases[name]))}")
+    say(f"{'add(), all frames at once':>26} {t_add * 1e3:9.3f}   (host clock, one call: copies into the device buffers)")
+    say(f"{'numpy loops on the host':>26} {t_host:9.3f}   (tests/_eval_ref.py, one run)   device / host "
+        f"{med(total)[0] / t_host:.6f}")
+    say(f"mean_ap {got['mean_ap']:.6f} (host {ref['summary']['mean_ap']:.6f}), nd_score {got['nd_score']:.6f} "
+        f"(host {ref['summary']['nd_score']:.6f}); largest |difference| over AP, TP errors and NDS "
+        f"{max(float(np.abs(ev._result['ap'].cpu().numpy() - ref['ap']).max()), float(np.abs(ev._result['tp_err'].cpu().numpy() - ref['tp_err']).max()), abs(got['nd_score'] - ref['summary']['nd_score'])):.2e}; "
+        f"tp flags equal: {bool(np.array_equal(ev._result['tp'].cpu().numpy(), ref['tp']))}")
+    say(f"peak device memory {torch.cuda.max_memory_allocated() / 2 ** 20:.0f} MiB")
+    for path, text in ((args.out, lines), (args.eval_out, lines[first:])):
+        if path:
+            os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+            with open(path, "w") as f:
+                f.write("\n".join(text) + "\n")
 
 
 def points_section(args, dev, say, lines):

@@ -1288,6 +1288,94 @@ int64_t cmt_pts_prepare_workspace_bytes(int64_t n_total);   /* 0 for n_total <= 
 int cmt_pts_prepare_tile_rows(void);
 int cmt_pts_prepare(const cmt_pts_prepare_args* args, void* stream);
 
+/* ---- detection evaluation: nuScenes-style AP / TP errors on the device (deteval.hip; additive to ABI 25) ----
+ * The reference's in-tree evaluator (a9coop_dataset.py accumulate / cummean / calc_ap / calc_tp /
+ * filter_eval_boxes) for boxes that already live on the device.  THIS TEXT is the contract.  All arithmetic
+ * is float64 on the float32 inputs, every product, sum, quotient and square root is rounded on its own
+ * (no FMA), sums run left to right as written.
+ *
+ * Inputs.  Predictions: N rows of box[9] fp32 (x, y, z, w, l, h, yaw, vx, vy), score fp32, label int32,
+ * sample int32, in arrival order (the reference's list index).  Ground truth: G rows of box[9] fp32, label,
+ * sample, num_pts int32 (-1: unknown), the rows of one sample in annotation order (rows of different samples
+ * may interleave).  N and G are capacities: with n_pred / n_gt non-null only rows below that device word
+ * (clamped to [0, capacity]) exist.  A row whose label is outside [0, C) or whose sample is outside [0, S)
+ * does not exist either.  Scores must not be NaN (a NaN score is ordered by its bit pattern).
+ * Config: C <= 32 classes with range[c] and yaw_period[c], T <= 8 thresholds dist_th[t], tp_index (the
+ * position of dist_th_tp), first_ind = round(100 * min_recall) + 1 in [1, 100], min_precision in [0, 1).
+ *
+ * Filters.  A row is kept iff sqrt(x * x + y * y) < range[label] (strict; NaN drops it); a ground-truth row
+ * additionally only if num_pts != 0.
+ * Order.  Within a class predictions are visited by descending score, equal scores (-0 equals +0) by
+ * descending row index.
+ * Match, per (class c, threshold t): the visited prediction takes, among the not yet taken kept ground truth
+ * of its sample and class, the one with the smallest d = sqrt(dx * dx + dy * dy) (dx, dy: centre
+ * differences); equal d: the lowest annotation index.  tp = 1 iff d < dist_th[t] (strict), and only then is
+ * that ground truth taken (for this t alone) and match_gt = its row; else tp = 0, match_gt = -1.
+ * Errors of a match (prediction p, ground truth g), NaN for a row without one:
+ *   err[0] trans = d;   err[1] vel = sqrt(dvx * dvx + dvy * dvy);
+ *   err[2] scale = 1 - i / ((vg + vp) - i), v = (w * l) * h, i = (min(wg, wp) * min(lg, lp)) * min(hg, hp),
+ *          min as numpy.minimum (a NaN operand gives NaN);
+ *   err[3] orient = |diff|, diff = pymod((yaw_g - yaw_p) + P / 2, P) - P / 2, then diff -= 2 pi if diff > pi;
+ *          pymod(a, P) = fmod(a, P), plus P when that is negative (Python's %), P = yaw_period[c] > 0.
+ * Curves, per (c, t).  npos[c] = kept ground truth of the class; the class's kept predictions in visiting
+ * order are j = 0 .. n - 1, ctp[j] the inclusive running count of tp, M = ctp[n - 1].  npos == 0 or M == 0
+ * (n == 0 included) gives the "no predictions" block: recall r, precision = confidence = 0, the four errors 1.
+ * Otherwise, with r_k = k * 0.01 (r_100 = 1), rec[j] = ctp[j] / npos, prec[j] = ctp[j] / (j + 1):
+ *   precision = interp(r, rec, prec, right = 0), confidence = interp(r, rec, score, right = 0);
+ *   each error curve e: value_k = interp(confidence_k, mc reversed, cm_e reversed), where mc[m] is the score
+ *   of the m-th match in visiting order and cm_e the NaN-aware cumulative mean of err[e] over the matches:
+ *   (sum of the non-NaN values up to m) / (their count), 0 while the count is 0, and 1 everywhere when all
+ *   are NaN.  The cumulative sums use a fixed tree (8 consecutive terms per thread, a wave scan, the waves,
+ *   the 2048-term chunks in order); two runs are bit-equal.
+ *   interp(x, xp, fp) is numpy.interp: j = the largest index with xp[j] <= x; x > xp[last]: right (default
+ *   fp[last]); x < xp[0]: fp[0]; j == last or xp[j] == x: fp[j]; else
+ *   ((fp[j + 1] - fp[j]) / (xp[j + 1] - xp[j])) * (x - xp[j]) + fp[j].
+ * Scalars.  ap[c][t] = mean over k >= first_ind of max(precision_k - min_precision, 0), divided by
+ * (1 - min_precision).  tp_err[c][e], from the t = tp_index curves: with last_ind the last k of non-zero
+ * confidence (0 if none), 1 when last_ind < first_ind, else the mean of the error curve over
+ * [first_ind, last_ind].  Means are serial sums in index order divided by the count.
+ *
+ * Three stream-ordered calls on one args struct, with two sorts by the caller between the first two:
+ *   cmt_det_eval_keys   writes the int64 sort keys key_class[N], key_sample[N] (both for row N - 1 - j at
+ *                       position j, so that a STABLE ascending sort visits equal scores by descending row) and
+ *                       key_gt[G] (row j at position j).  Rows that do not exist or are filtered get INT64_MAX.
+ *                       key_class = class << 32 | ~ord(score), key_sample = (sample << 6 | class) << 32 |
+ *                       ~ord(score), key_gt = sample << 6 | class; ord() is the order-preserving uint32 of a float.
+ *   the caller sorts each key array ascending and stable and passes the sorted keys and the int64 indices
+ *   (sk_class / si_class, sk_sample / si_sample, sk_gt / si_gt).
+ *   cmt_det_eval_match  one wave per (sample, class): tp[T][N] uint8, match_gt[T][N] int32, err[T][4][N]
+ *                       float64 and npos[C]; every element is written by exactly one lane, no atomics.
+ *   cmt_det_eval_curves one workgroup per (class, threshold): md[C][T][7][101] float64 (recall, precision,
+ *                       confidence, trans, vel, scale, orient), ap[C][T], tp_err[C][4].
+ * No host synchronisation and no allocation inside.  The workspace (cmt_det_eval_workspace_bytes, 8-byte
+ * aligned) needs no initialisation.  CMT_EINVAL before any device work: N or G outside [0, 2^31), S outside
+ * [1, 2^24], C outside [1, 32], T outside [1, 8], tp_index outside [0, T), first_ind outside [1, 100],
+ * min_precision outside [0, 1), a non-finite or non-positive range, yaw_period or dist_th, a null or
+ * misaligned pointer that the call uses, a short workspace. */
+#define CMT_DET_MAX_CLASSES 32
+#define CMT_DET_MAX_THRESHOLDS 8
+#define CMT_DET_NELEM 101
+typedef struct cmt_det_eval_args {
+    int64_t N, G;                                  /* capacities (rows) */
+    int S, C, T, tp_index, first_ind, reserved;
+    double range[CMT_DET_MAX_CLASSES], yaw_period[CMT_DET_MAX_CLASSES], dist_th[CMT_DET_MAX_THRESHOLDS];
+    double min_precision;
+    const void *pred_box, *pred_score, *pred_label, *pred_sample;
+    const void *gt_box, *gt_label, *gt_sample, *gt_num_pts;
+    const int *n_pred, *n_gt;                      /* device words, or null: all rows */
+    void *key_class, *key_sample, *key_gt;         /* int64 [N], [N], [G]: written by cmt_det_eval_keys */
+    const void *sk_class, *si_class, *sk_sample, *si_sample, *sk_gt, *si_gt;   /* int64, sorted keys and indices */
+    void *tp, *match_gt, *err, *npos;              /* written by cmt_det_eval_match */
+    void *md, *ap, *tp_err;                        /* written by cmt_det_eval_curves */
+    void* workspace;
+    int64_t workspace_bytes;
+} cmt_det_eval_args;
+int64_t cmt_det_eval_args_size(void);
+int64_t cmt_det_eval_workspace_bytes(int64_t N, int64_t G, int S, int C, int T);   /* -1 for arguments out of range */
+int cmt_det_eval_keys(const cmt_det_eval_args* args, void* stream);
+int cmt_det_eval_match(const cmt_det_eval_args* args, void* stream);
+int cmt_det_eval_curves(const cmt_det_eval_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
