@@ -277,6 +277,33 @@ class PtsPrepareArgs(ctypes.Structure):
                 ("src", _vp), ("dst", _vp), ("count", _vp), ("workspace", _vp), ("workspace_bytes", _i64)]
 
 
+AUG_MAX_BOXES = 128    # cmt_hip.h CMT_AUG_MAX_BOXES
+AUG_MAX_ANN = 65536    # cmt_hip.h CMT_AUG_MAX_ANN
+
+
+class AugXform(ctypes.Structure):
+    _fields_ = [("has_rot", _int), ("has_scale", _int), ("has_trans", _int), ("flip_h", _int), ("flip_v", _int),
+                ("has_range", _int), ("rot32", _flt * 9), ("angle32", _flt), ("scale", _flt),
+                ("trans32", _flt * 3), ("range", _flt * 6)]
+
+
+class PointsInBoxesArgs(ctypes.Structure):
+    _fields_ = [("N", _i64), ("M", _int), ("F", _int), ("D", _int), ("reserved", _int),
+                ("points", _vp), ("count_in", _vp), ("boxes", _vp), ("box_of_point", _vp), ("count_per_box", _vp)]
+
+
+class PtsAugmentArgs(ctypes.Structure):
+    _fields_ = [("n_src", _i64), ("n_paste", _i64), ("F", _int), ("K", _int), ("paste_first", _int),
+                ("shift_height", _int), ("xf", AugXform),
+                ("src", _vp), ("count_in", _vp), ("paste", _vp), ("paste_boxes", _vp), ("order", _vp),
+                ("dst", _vp), ("count", _vp), ("workspace", _vp), ("workspace_bytes", _i64)]
+
+
+class BoxesAugmentArgs(ctypes.Structure):
+    _fields_ = [("n", _int), ("D", _int), ("num_classes", _int), ("gravity", _int), ("xf", AugXform),
+                ("boxes", _vp), ("labels", _vp), ("out_boxes", _vp), ("out_labels", _vp), ("count", _vp)]
+
+
 STRUCTS = {"gemm": GemmArgs, "attn": AttnArgs, "ln": LnArgs, "chain": ChainArgs, "gemm_ex": GemmExArgs,
            "attn_train": AttnTrainArgs, "ln_train": LnTrainArgs, "bn": BnArgs, "det_loss": DetLossArgs,
            "match_cost": MatchCostArgs, "adamw": AdamwArgs, "mlp2": Mlp2Args, "mlp2_affine": Mlp2AffineArgs, "lsap": LsapArgs,
@@ -285,7 +312,8 @@ STRUCTS = {"gemm": GemmArgs, "attn": AttnArgs, "ln": LnArgs, "chain": ChainArgs,
            "fpn_lateral": FpnLateralArgs, "rows_to_nchw": RowsToNchwArgs,
            "img_stem": ImgStemArgs, "img_conv": ImgConvArgs, "img_concat": ImgConcatArgs, "img_gate": ImgGateArgs,
            "img_apply": ImgApplyArgs, "img_pool": ImgPoolArgs, "img_prepare": ImgPrepareArgs,
-           "img_resize": ImgResizeArgs, "pts_prepare": PtsPrepareArgs}
+           "img_resize": ImgResizeArgs, "pts_prepare": PtsPrepareArgs,
+           "points_in_boxes": PointsInBoxesArgs, "pts_augment": PtsAugmentArgs, "boxes_augment": BoxesAugmentArgs}
 
 _LIB = None
 
@@ -417,6 +445,15 @@ def _load():
         "cmt_pts_prepare_workspace_bytes": ([_i64], _i64),
         "cmt_pts_prepare_tile_rows": ([], _int),
         "cmt_pts_prepare": ([P(PtsPrepareArgs), _vp], _int),
+        "cmt_points_in_boxes_args_size": ([], _i64),
+        "cmt_pts_augment_args_size": ([], _i64),
+        "cmt_boxes_augment_args_size": ([], _i64),
+        "cmt_points_in_boxes_chunk": ([], _int),
+        "cmt_pts_augment_tile_rows": ([], _int),
+        "cmt_pts_augment_workspace_bytes": ([_i64], _i64),
+        "cmt_points_in_boxes": ([P(PointsInBoxesArgs), _vp], _int),
+        "cmt_pts_augment": ([P(PtsAugmentArgs), _vp], _int),
+        "cmt_boxes_augment": ([P(BoxesAugmentArgs), _vp], _int),
         "cmt_adamw_step": ([P(AdamwArgs), _vp], _int),
     }
     for name, (args, res) in sig.items():

@@ -44,6 +44,11 @@ with the plan ``points_plan_from_config`` reads from the config: remove_close, s
 ``use_dim``, the vehicle cloud moved into the infrastructure frame, the range filter.  The detector gets the padded
 buffer (kept rows, then NaN) as it is; the vehicle cameras' ``lidar2img`` follow through ``lidar2img_to_infra``.
 
+``--eval nds --count-gt-points`` (opt-in) counts the frame's points inside every ground-truth box on the device
+(``native_aug.points_in_boxes`` over the frame's cloud or clouds, padded buffers included) and passes the counts to
+the evaluator as ``gt_num_pts``: ground truth without a point is dropped, as the reference's dataset does.  The nds
+line then also carries ``gt_without_points``.  Not with ``--launcher pytorch`` (rank 0 holds no clouds).
+
 Config 1 of BASELINE.json: ``python cmt-cooperative-perception_amd/tools/test.py
 cmt_lidar_nus --synthetic --num-query 32 --num-layers 1 --points 1000 --eval bbox``.
 The head runs on a HIP device only -- there is no CPU path; without a GPU the
@@ -94,6 +99,9 @@ def parse_args(argv=None):
     p.add_argument("--sweeps", type=int, default=None, metavar="K",
                    help="for --detector: K synthetic sweeps per cloud, prepared on the device by prepare_points with "
                         "the config's point plan (default: key-frame points as they are)")
+    p.add_argument("--count-gt-points", action="store_true",
+                   help="with --eval nds: count the points inside every ground-truth box on the device and drop "
+                        "ground truth without points (gt_num_pts)")
     p.add_argument("--precision", default="bf16", choices=["bf16", "fp16", "ref"], help="compute policy")
     p.add_argument("--img-precision", default=None, choices=["ref", "fp16"],
                    help="arithmetic of the image backbone (--detector): three-pass split-f16 or one-pass fp16; "
@@ -116,6 +124,8 @@ def parse_args(argv=None):
         p.error("The output file must be a .json file.")
     if a.sweeps is not None and (not a.detector or a.sweeps < 0):
         p.error("--sweeps K needs --detector and K >= 0")
+    if a.count_gt_points and (not a.eval or "nds" not in a.eval or a.launcher != "none"):
+        p.error("--count-gt-points needs --eval nds and --launcher none")
     if not a.synthetic:
         p.error("dataset loading is out of scope (SURVEY.md 2 rows 18/21): run with --synthetic")
     return a
@@ -288,6 +298,19 @@ def frame_ground_truth(frame, seed, pc_range, num_classes):
     return boxes[0].float(), labels[0]
 
 
+def gt_point_counts(gt_boxes, points):
+    """gt_num_pts of one frame: the points of every cloud in ``points`` (fp32 [n, F] on the device, NaN padding
+    allowed) inside each gravity-centre ground-truth box [g, 9] -> int32 [g] on the device, no host read"""
+    from projects.mmdet3d_plugin import native_aug as NA
+    lidar = gt_boxes[:, :7].clone()
+    lidar[:, 2] -= lidar[:, 5] * 0.5   # gravity centre -> bottom centre
+    total = None
+    for pts in points:
+        c = NA.points_in_boxes(pts.float().contiguous(), lidar, want="count_per_box")
+        total = c if total is None else total + c
+    return total
+
+
 def eval_config(class_names):
     """TUMTraf constants for TUMTraf class names, the nuScenes detection constants otherwise"""
     from projects.mmdet3d_plugin.core import evaluation as E
@@ -366,10 +389,18 @@ def _run(args, name, device, rank, world, distributed):
         if rank == 0:
             evaluator = DetectionEvaluator(eval_config(class_names), max(args.frames, 1), device)
 
-    def feed(frame, boxes, scores, labels):
+    empty_gt = []   # per frame, a device count of the ground truth without points (--count-gt-points)
+
+    def feed(frame, boxes, scores, labels, points=None):
         gb, gl = frame_ground_truth(frame, args.seed, pcr, len(class_names))
         # the head's boxes are on the device already; the detector's result dict (bbox3d2result) is on the host
-        evaluator.add(boxes.to(device), scores.to(device), labels.to(device), None, gb.to(device), gl.to(device))
+        if points is None:
+            evaluator.add(boxes.to(device), scores.to(device), labels.to(device), None, gb.to(device), gl.to(device))
+            return
+        gb = gb.to(device)
+        num_pts = gt_point_counts(gb, points)
+        empty_gt.append((num_pts == 0).sum())
+        evaluator.add(boxes.to(device), scores.to(device), labels.to(device), None, gb, gl.to(device), num_pts)
 
     results = []
     t0 = time.perf_counter()
@@ -390,7 +421,7 @@ def _run(args, name, device, rank, world, distributed):
             else:
                 boxes, scores, labels = run_frame(head, name, feats, metas)
             if want_nds and not distributed:   # the boxes as tensors: no lists, no JSON
-                feed(f, boxes.float(), scores.float(), labels)
+                feed(f, boxes.float(), scores.float(), labels, points if args.count_gt_points else None)
             results.append(dict(frame=f, voxels=vox_stats,
                                 boxes_3d=boxes.float().cpu().tolist(), scores_3d=scores.float().cpu().tolist(),
                                 labels_3d=labels.cpu().tolist(),
@@ -437,7 +468,8 @@ def _run(args, name, device, rank, world, distributed):
                 feed(r["frame"], torch.tensor(r["boxes_3d"], dtype=torch.float32, device=device).reshape(-1, 9),
                      torch.tensor(r["scores_3d"], dtype=torch.float32, device=device),
                      torch.tensor(r["labels_3d"], dtype=torch.int64, device=device))
-        print(json.dumps(dict(metric="nds", frames=len(results), gt_per_frame=GT_PER_FRAME, **evaluator.compute())))
+        extra = dict(gt_without_points=int(sum(int(c.item()) for c in empty_gt))) if args.count_gt_points else {}
+        print(json.dumps(dict(metric="nds", frames=len(results), gt_per_frame=GT_PER_FRAME, **extra, **evaluator.compute())))
     return 0
 
 

@@ -34,11 +34,17 @@ device events) on 800 frames x 300 predictions, 9 classes, 4 thresholds and 20 g
 ground truth plus false positives) against one run of the contract's numpy restatement (tests/_eval_ref.py, the
 reference's algorithm in its own style of loop) on the host, and checks that both give the same summary.
 
+``--only augment`` (``--augment-out FILE``) times ``native_aug.augment_points`` on one training cloud of --points rows
+(F = 5) with 32 paste boxes and 4 000 paste rows, every step on (remove_points_in_boxes, rotation, scale, translation,
+both flips, range filter, shuffle), against the same chain as torch ops on the device (the inside test by
+broadcasting, boolean indexing, ``randperm``), in alternating windows of --iters calls.
+
 ``--img-precision`` (default ``ref``) is the image backbone's arithmetic (native_img.set_img_precision): ``fp16``
 runs VoVNet on the one-pass fp16 kernels; everything else is unchanged.
 
     python dev/detector_probe.py [--img-precision ref|fp16] [--points 300000] [--repeats 20] [--warmup 3]
-                                 [--iters 20] [--seed 0] [--out FILE] [--only resize|points|eval] [--resize-out FILE]
+                                 [--iters 20] [--seed 0] [--out FILE] [--only resize|points|eval|augment]
+                                 [--resize-out FILE] [--augment-out FILE]
                                  [--points-out FILE] [--sweep-points 27000] [--sweeps K] [--eval-out FILE]
                                  [--eval-frames 800]
 
@@ -89,7 +95,8 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--img-precision", choices=("ref", "fp16"), default="ref")
     ap.add_argument("--out", default=None)
-    ap.add_argument("--only", choices=("resize", "points", "eval"), default=None, help="run this section alone")
+    ap.add_argument("--only", choices=("resize", "points", "eval", "augment"), default=None, help="run this section alone")
+    ap.add_argument("--augment-out", default=None, help="write the cmt_pts_augment section to this file")
     ap.add_argument("--eval-out", default=None, help="write the detection-evaluation section to this file")
     ap.add_argument("--eval-frames", type=int, default=800, help="frames of the detection-evaluation section")
     ap.add_argument("--resize-out", default=None, help="write the cmt_img_resize_prepare section to this file")
@@ -255,6 +262,9 @@ def main():
         return
     if args.only == "eval":
         eval_section(args, dev, say, lines)
+        return
+    if args.only == "augment":
+        augment_section(args, dev, say, lines)
         return
     frames = frame("cmt_fusion_nus")
     frame("cmtcoop_fusion_tumtraf")
@@ -492,6 +502,110 @@ def points_section(args, dev, say, lines):
         say(f"{'(c) numpy on the host':>26} {fmt(th)}   (a) / (c) {tn[0] / th[0]:.4f}")
     say(f"peak device memory {torch.cuda.max_memory_allocated() / 2 ** 20:.0f} MiB")
     for path, text in ((args.out, lines), (args.points_out, lines[first:])):
+        if path:
+            os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+            with open(path, "w") as f:
+                f.write("\n".join(text) + "\n")
+
+
+def augment_section(args, dev, say, lines):
+    """cmt_pts_augment on one training cloud against the same chain written as torch ops on the device"""
+    import math
+    import numpy as np
+    from projects.mmdet3d_plugin import native_aug as NA
+    from projects.mmdet3d_plugin import synthetic as S
+    first = len(lines)
+    N, K, P = args.points, 32, 4000
+    pcr = [-54.0, -54.0, -5.0, 54.0, 54.0, 3.0]
+    say(f"--- {torch.cuda.get_device_name(0)}: cmt_pts_augment, one cloud of {N} rows (F = 5), {K} paste boxes with {P} "
+        f"paste rows, rotation + scale + translation + both flips + range filter + shuffle: (a) augment_points and (b) "
+        f"torch ops on the device (inside test by broadcasting, boolean indexing, randperm) in alternating windows of "
+        f"{args.iters} calls, median of {args.repeats} (min .. max) after {args.warmup} warm-up calls, device events, ms "
+        "per cloud")
+    src = S.synthetic_points(N, pcr, seed=args.seed, device=dev, margin=2.0)
+    g = torch.Generator().manual_seed(args.seed + 5)
+    boxes = torch.zeros((K, 7))
+    boxes[:, :2] = (torch.rand((K, 2), generator=g) * 2 - 1) * 45
+    boxes[:, 2] = -4.0 + torch.rand(K, generator=g)
+    boxes[:, 3:6] = 1.5 + 3.0 * torch.rand((K, 3), generator=g)
+    boxes[:, 6] = (torch.rand(K, generator=g) * 2 - 1) * math.pi
+    # paste rows: P / K points inside each box, in its own frame
+    u = (torch.rand((K, P // K, 3), generator=g) - 0.5) * 0.98
+    loc = u * boxes[:, None, 3:6]
+    c, s = torch.cos(boxes[:, 6])[:, None], torch.sin(boxes[:, 6])[:, None]
+    xyz = torch.stack([boxes[:, None, 0] + loc[..., 0] * c - loc[..., 1] * s,
+                       boxes[:, None, 1] + loc[..., 0] * s + loc[..., 1] * c,
+                       boxes[:, None, 2] + boxes[:, None, 5] * 0.5 + loc[..., 2]], -1).reshape(-1, 3)
+    paste = torch.cat([xyz, torch.rand((xyz.shape[0], 2), generator=g)], 1).to(dev)
+    boxes = boxes.to(dev)
+    n_in = N + paste.shape[0]
+    params = dict(angle=0.31, scale=1.04, trans=np.array([0.4, -0.3, 0.1]), flip_h=True, flip_v=True)
+    out = torch.empty((n_in, 5), dtype=torch.float32, device=dev)
+    ws = NA.PointsWorkspace()
+    rT = torch.from_numpy(NA.rotation_matrix(params["angle"]).T.astype(np.float32)).to(dev)
+    t32 = torch.from_numpy(params["trans"].astype(np.float32)).to(dev)
+    lo, hi = torch.tensor(pcr[:3], device=dev), torch.tensor(pcr[3:], device=dev)
+    bc, bs = torch.cos(boxes[:, 6]), torch.sin(boxes[:, 6])
+    hx, hy, dz = boxes[:, 3] * 0.5, boxes[:, 4] * 0.5, boxes[:, 5]
+
+    def native_fn(shuffle=True):
+        return NA.augment_points(src, params, paste_points=paste, paste_boxes=boxes, point_cloud_range=pcr,
+                                 shuffle=shuffle, out=out, workspace=ws)
+
+    def torch_fn(shuffle=True):
+        d = src[:, None, :3] - boxes[None, :, :3]
+        lx = d[..., 0] * bc + d[..., 1] * bs
+        ly = d[..., 1] * bc - d[..., 0] * bs
+        inside = (lx.abs() < hx) & (ly.abs() < hy) & (d[..., 2] > 0) & (d[..., 2] < dz)
+        pts = torch.cat([src[~inside.any(1)], paste])             # the index is a host read
+        pts[:, :3] = pts[:, :3] @ rT
+        pts[:, :3] *= params["scale"]
+        pts[:, :3] += t32
+        pts[:, 1] = -pts[:, 1]
+        pts[:, 0] = -pts[:, 0]
+        pts = pts[((pts[:, :3] > lo) & (pts[:, :3] < hi)).all(1)]   # and another
+        if shuffle:
+            pts = pts[torch.randperm(pts.shape[0], device=dev)]
+        return pts
+
+    padded, count = native_fn(None)
+    k = int(count.item())
+    tor = torch_fn(False)
+    diff = float((padded[:k] - tor).abs().max()) if tor.shape[0] == k else float("nan")
+    for fn in (native_fn, torch_fn):
+        for _ in range(args.warmup):
+            fn()
+    torch.cuda.synchronize()
+    tn, tt = [], []
+    for _ in range(args.repeats):
+        tn.append(event_ms(lambda: [native_fn() for _ in range(args.iters)]) / args.iters)
+        tt.append(event_ms(lambda: [torch_fn() for _ in range(args.iters)]) / args.iters)
+    # the two launches alone, with a fixed permutation: args.iters calls captured in one graph
+    order = torch.randperm(n_in, dtype=torch.int32, device=dev)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        native_fn(order)
+    torch.cuda.current_stream().wait_stream(side)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        for _ in range(args.iters):
+            native_fn(order)
+    graph.replay()
+    torch.cuda.synchronize()
+    tg = med([event_ms(graph.replay) / args.iters for _ in range(args.repeats)])
+    tn, tt = med(tn), med(tt)
+    nbytes = 2 * n_in * 5 * 4 + n_in * 4 * 2 + n_in * 5 * 4   # rows and order read by both launches, the destination once
+    say(f"kept {k} of {n_in} rows; rows kept by the torch chain {tor.shape[0]}; largest coordinate distance of the "
+        f"unshuffled results {diff:.2e} m (the torch matmul fixes no order of its sums)")
+    say(f"{'(a) augment_points':>26} {fmt(tn)}   randperm + 2 launches: the cloud is read twice and written once")
+    say(f"{'(a) from a graph':>26} {fmt(tg)}   the two launches with a fixed permutation, without the wrapper's host time; "
+        f"{nbytes * 1e-6:.1f} MB moved -> {nbytes / (tg[0] * 1e-3) * 1e-12:.2f} TB/s")
+    say(f"{'(b) torch ops, device':>26} {fmt(tt)}   (a) / (b) {tn[0] / tt[0]:.3f}; about 9 passes over [N, {K}] "
+        "temporaries for the inside test, then 2 boolean indexings (host reads), cat, matmul, 4 in-place passes, the "
+        "range mask and the permuted gather")
+    say(f"peak device memory {torch.cuda.max_memory_allocated() / 2 ** 20:.0f} MiB")
+    for path, text in ((args.out, lines), (args.augment_out, lines[first:])):
         if path:
             os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
             with open(path, "w") as f:

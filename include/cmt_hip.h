@@ -1376,6 +1376,141 @@ int cmt_det_eval_keys(const cmt_det_eval_args* args, void* stream);
 int cmt_det_eval_match(const cmt_det_eval_args* args, void* stream);
 int cmt_det_eval_curves(const cmt_det_eval_args* args, void* stream);
 
+/* ---- training-side point and box pipeline (ptsaug.hip; additive to ABI 25) ---------------------------
+ * The chain every reference config that trains on points runs between loading and the voxelizer:
+ * [Unified]ObjectSample[Coop] (the part after the database sampler has chosen its objects),
+ * GlobalRotScaleTransAll[Coop], CustomRandomFlip3D, PointsRangeFilter[Coop], ObjectRangeFilter,
+ * ObjectNameFilter and PointShuffle[Coop].  THIS TEXT is the contract: a restatement in which every rounding
+ * is fixed.  The conventions are mmdet3d v1.0.0rc6's as the reference calls them (BasePoints.rotate / scale /
+ * translate / flip, LiDARInstance3DBoxes.rotate / scale / translate / flip / in_range_bev / limit_yaw,
+ * box_np_ops.points_in_rbbox); they have not been compared with an installed mmdet3d.
+ * fl32 = one rounding to float32, round-to-nearest-even; no operation below is fused with another.
+ * All three calls: caller-owned buffers, stream-ordered, no host synchronisation, no allocation, no
+ * workgroup waits for another: graph-capturable.  Every output element has exactly one writer, the counts
+ * of cmt_points_in_boxes excepted (integer atomics).  Inputs and outputs must not overlap.
+ *
+ * A LiDAR box is a row of D fp32, D 7 or 9: x, y, z_bottom, dx, dy, dz, yaw [, vx, vy].
+ * The inside test of a point p and a box, in real arithmetic:
+ *   d = p - (x, y, z_bottom),  lx = d.x * cos(yaw) + d.y * sin(yaw),  ly = -d.x * sin(yaw) + d.y * cos(yaw),
+ *   inside iff |lx| < dx / 2 && |ly| < dy / 2 && 0 < d.z && d.z < dz, all strict
+ * (points_in_rbbox with the bottom-centre origin (0.5, 0.5, 0): the open interior).  A NaN anywhere in the
+ * point or the box gives "outside"; so does dx, dy or dz <= 0.  The kernels evaluate it in float32 with
+ * the device's sinf / cosf, one pair per box: the contract binds only points farther than
+ * 1e-4 * (1 + max |coordinate|) metres from every face plane of every box (max over the point and the
+ * box centre); nearer ones may fall on either side, the same side in both launches of cmt_pts_augment.
+ *
+ * The transform parameters (cmt_aug_xform), applied where a step below names them:
+ *   rotation (has_rot): rot32 = R row-major, R = [[c, -s, 0], [s, c, 0], [0, 0, 1]] for the angle a
+ *     (counter-clockwise, p' = R p: BasePoints.rotate(a)), built by the caller in float64 and rounded once;
+ *     angle32 = fl32(a).  For k = 0, 1, 2, the arithmetic of cmt_pts_prepare step 5 without the translation:
+ *       p'_k = fl32(fl32(fl32(x * rot32[3k]) + fl32(y * rot32[3k + 1])) + fl32(z * rot32[3k + 2]))
+ *   scale (has_scale): p_k = fl32(p_k * scale).   translation (has_trans): p_k = fl32(p_k + trans32[k]).
+ *   flip_h ('horizontal'): y = -y.   flip_v ('vertical'): x = -x.   (sign changes, exact)
+ *   range (has_range): x, y, z min, then x, y, z max.
+ *
+ * cmt_points_in_boxes: N points fp32 [N][F], F 3..8 (columns 0..2 are read), M boxes fp32 [M][D].
+ *   count_in: null, or a device int32 clamped to [0, N]: rows at or beyond it belong to no box.
+ *   box_of_point int32 [N] (null: skipped): the lowest index of a box that contains the point, -1 for none.
+ *   count_per_box int32 [M] (null: skipped): zeroed by the call, then every containing box is incremented
+ *   (points_in_rbbox(...).sum(0)) with integer atomics, at most one per wave and box.
+ *   Boxes are staged per workgroup cmt_points_in_boxes_chunk() at a time; a workgroup owns
+ *   cmt_pts_augment_tile_rows() consecutive points.  N == 0 and M == 0 are legal; N < 2^31, M < 2^24.
+ *   CMT_EINVAL before any device work: N, M, F or D out of range; points null or misaligned with N > 0;
+ *   boxes null or misaligned with M > 0; a misaligned count_in, box_of_point or count_per_box.
+ *
+ * cmt_pts_augment: one cloud.  src fp32 [n_src][F] with the optional device count_in (clamped to
+ *   [0, n_src]; the padded pair of cmt_pts_prepare), paste fp32 [n_paste][F] (the sampled objects' points),
+ *   paste_boxes fp32 [K][7], K <= CMT_AUG_MAX_BOXES, order int32 [n_in] or null, n_in = n_src + n_paste < 2^31.
+ *   The concatenated index space is the paste rows then the src rows (paste_first != 0: ObjectSampleCoop)
+ *   or the src rows then the paste rows (UnifiedObjectSample[Coop], points.cat([points, sampled])).
+ *   Slot j = 0 .. n_in - 1 visits row i = order ? order[j] : j; an i outside [0, n_in) drops the slot.
+ *   Per visited row, in this order:
+ *     1. a src row at or beyond *count_in is dropped;
+ *     2. remove_points_in_boxes: a src row inside any paste box (the inside test above) is dropped; paste
+ *        rows are never tested;
+ *     3. rotation, 4. scale, 5. translation, 6. flips, on columns 0..2 as written above;
+ *     7. in_range_3d (has_range): kept iff p_k > range[k] && p_k < range[3 + k], k = 0, 1, 2, strict, float32;
+ *        a NaN or +-inf coordinate drops the row.  Without the filter such rows are kept.
+ *   Columns 3 and beyond are copied bit for bit.  Kept rows go to dst[0 .. count) in slot order; rows
+ *   [count, n_in) of dst fp32 [n_in][F] are the quiet NaN 0x7FC00000 in every column; count is written once.
+ *   PointShuffle needs no sort: a uniform permutation of all rows restricted to the kept rows is a uniform
+ *   shuffle of the kept rows, so the caller passes a random permutation as order.
+ *   Two launches, as cmt_pts_prepare (per-tile kept counts of cmt_pts_augment_tile_rows() slots; then prefix,
+ *   scatter and fill); the workspace (cmt_pts_augment_workspace_bytes(n_in) bytes, 4-byte aligned) is
+ *   rewritten by every call before it is read.  shift_height is not built.
+ *   CMT_EINVAL before any device work: F outside 3..8; K outside [0, CMT_AUG_MAX_BOXES]; n_src, n_paste
+ *   negative or n_in >= 2^31; shift_height != 0; a non-finite rotation, angle, scale, translation or range
+ *   that is switched on; range min >= max; count null or misaligned; with rows present a null or misaligned
+ *   src (n_src > 0), paste (n_paste > 0), paste_boxes (K > 0), dst or workspace (n_in > 0); a misaligned
+ *   count_in or order; workspace_bytes below cmt_pts_augment_workspace_bytes(n_in).
+ *
+ * cmt_boxes_augment: the same parameters on the annotations (the ground truth followed by the pasted boxes,
+ *   concatenated by the caller): boxes fp32 [n][D], labels int64 [n] -> out_boxes fp32 [n][D], out_labels
+ *   int64 [n], count (device int32).  One workgroup; n <= CMT_AUG_MAX_ANN.  Per box, in this order:
+ *     rotation (has_rot): the centre (columns 0..2) like a point; yaw = fl32(yaw + angle32); D == 9:
+ *       vx' = fl32(fl32(vx * rot32[0]) + fl32(vy * rot32[1])), vy' = fl32(fl32(vx * rot32[3]) + fl32(vy * rot32[4]));
+ *     scale: columns 0..5 and 7..8;   translation: columns 0..2;
+ *     flip_h: columns 1 and 8 negated, yaw = -yaw;
+ *     flip_v: columns 0 and 7 negated, yaw = fl32(fl32(-yaw) + fl32(pi));
+ *     ObjectRangeFilter (has_range), in_range_bev: kept iff x > range[0] && y > range[1] && x < range[3] &&
+ *       y < range[4], strict, float32 (a NaN drops the box);
+ *     ObjectNameFilter: a label < 0 or >= num_classes drops the box;
+ *     limit_yaw(0.5, 2 pi): yaw = fl32(yaw - fl32(floorf(fl32(fl32(yaw / P) + 0.5f)) * P)), P = fl32(2 pi),
+ *       the division correctly rounded;
+ *     gravity != 0: column 2 = fl32(z + fl32(dz * 0.5f)) (the head's gravity-centre layout).
+ *   Kept boxes and their labels go to rows [0, count) in input order; rows [count, n) are quiet NaN / -1.
+ *   CMT_EINVAL before any device work: n outside [0, CMT_AUG_MAX_ANN]; D not 7 or 9; num_classes < 0; the
+ *   transform conditions of cmt_pts_augment; count null or misaligned; with n > 0 a null or misaligned (boxes
+ *   and out_boxes 4 bytes, labels 8 bytes) buffer. */
+#define CMT_AUG_MAX_BOXES 128
+#define CMT_AUG_MAX_ANN 65536
+typedef struct cmt_aug_xform {
+    int has_rot, has_scale, has_trans, flip_h, flip_v, has_range;
+    float rot32[9], angle32, scale;
+    float trans32[3], range[6];
+} cmt_aug_xform;
+typedef struct cmt_points_in_boxes_args {
+    int64_t N;
+    int M, F, D, reserved;
+    const void* points;
+    const int* count_in;
+    const void* boxes;
+    int* box_of_point;
+    int* count_per_box;
+} cmt_points_in_boxes_args;
+typedef struct cmt_pts_augment_args {
+    int64_t n_src, n_paste;
+    int F, K, paste_first, shift_height;
+    cmt_aug_xform xf;
+    const void* src;
+    const int* count_in;
+    const void* paste;
+    const void* paste_boxes;
+    const int* order;
+    void* dst;
+    int* count;
+    void* workspace;
+    int64_t workspace_bytes;
+} cmt_pts_augment_args;
+typedef struct cmt_boxes_augment_args {
+    int n, D, num_classes, gravity;
+    cmt_aug_xform xf;
+    const void* boxes;
+    const void* labels;
+    void* out_boxes;
+    void* out_labels;
+    int* count;
+} cmt_boxes_augment_args;
+int64_t cmt_points_in_boxes_args_size(void);
+int64_t cmt_pts_augment_args_size(void);
+int64_t cmt_boxes_augment_args_size(void);
+int cmt_points_in_boxes_chunk(void);
+int cmt_pts_augment_tile_rows(void);
+int64_t cmt_pts_augment_workspace_bytes(int64_t n_in);   /* 0 for n_in <= 0 */
+int cmt_points_in_boxes(const cmt_points_in_boxes_args* args, void* stream);
+int cmt_pts_augment(const cmt_pts_augment_args* args, void* stream);
+int cmt_boxes_augment(const cmt_boxes_augment_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
