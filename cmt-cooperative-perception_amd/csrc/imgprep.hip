@@ -9,6 +9,7 @@
 // 12 bytes and funnel-shifts them (v_alignbyte_b32), so the loads stay dword loads.  Groups that touch the
 // crop's right edge or pixels outside the source take a per-pixel path with byte loads.
 #include "cmt_common.h"
+#include "img_resize.h"   // img_resize_coord, img_resize_coefs, img_resize_taps
 
 struct img_prep_p {
     const uint8_t* src;
@@ -153,41 +154,6 @@ struct img_resize_p {
     int rgb;
     float mean[3], inv[3];
 };
-
-struct __attribute__((aligned(4))) img_prep_dw2 { unsigned a, b; };
-
-// floor and the two integer coefficients of resized index d on an axis of scale sc
-__device__ __forceinline__ void img_resize_coord(int d, double sc, int& s, float& t) {
-#pragma clang fp contract(off)   // __dmul_rn / __dsub_rn are plain operators here and would still fuse
-    const double m = ((double)d + 0.5) * sc;
-    const float f = (float)(m - 0.5);
-    const float fl = floorf(f);
-    s = (int)fl;
-    t = __fsub_rn(f, fl);
-}
-
-__device__ __forceinline__ void img_resize_coefs(float t, int& c0, int& c1) {
-    c1 = (int)rintf(__fmul_rn(t, 2048.f));
-    c0 = (int)rintf(__fmul_rn(__fsub_rn(1.f, t), 2048.f));
-}
-
-// the bytes at ap, 6 (PAIR) or 3 of them, as lo = bytes 0..3 and hi = bytes 4..5 (the rest is not used)
-template <bool PAIR>
-__device__ __forceinline__ void img_resize_taps(const uint8_t* ap, unsigned& lo, unsigned& hi) {
-    const unsigned sh = (unsigned)((uintptr_t)ap & 3);
-    const unsigned* q = (const unsigned*)(ap - sh);
-    unsigned d0, d1, d2 = 0u;
-    if (PAIR) {
-        const img_prep_dw2 d = *(const img_prep_dw2*)q;   // bytes sh .. sh + 5 reach the second dword at any phase
-        d0 = d.a, d1 = d.b;
-        if (sh == 3u) d2 = q[2];
-    } else {
-        d0 = q[0];
-        d1 = sh >= 2u ? q[1] : 0u;
-    }
-    lo = __builtin_amdgcn_alignbyte(d1, d0, sh);
-    hi = __builtin_amdgcn_alignbyte(d2, d1, sh);
-}
 
 template <bool VEC, bool PAIR>
 __global__ __launch_bounds__(256) void img_resize_prepare_kernel(img_resize_p p) {

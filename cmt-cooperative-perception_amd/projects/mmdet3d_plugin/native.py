@@ -260,6 +260,45 @@ class ImgResizeArgs(ctypes.Structure):
                 ("mean", _flt * 3), ("inv_std", _flt * 3), ("src", _vp), ("dst", _vp)]
 
 
+IMG_AUG_MAX = 16        # cmt_hip.h CMT_IMG_AUG_MAX
+PASTE_MAX_RECTS = 256   # cmt_hip.h CMT_PASTE_MAX_RECTS
+
+
+class GridParams(ctypes.Structure):
+    _fields_ = [("d", _int), ("l", _int), ("st_h", _int), ("st_w", _int),
+                ("use_h", _int), ("use_w", _int), ("mode", _int), ("reserved", _int)]
+
+
+class ImgAugImage(ctypes.Structure):
+    _fields_ = [("Hr", _int), ("Wr", _int), ("x0", _int), ("y0", _int), ("flip", _int), ("zero", _int),
+                ("iM", ctypes.c_double * 6)]
+
+
+class ImgAugmentArgs(ctypes.Structure):
+    _fields_ = [("N", _int), ("Hs", _int), ("Ws", _int), ("to_rgb", _int),
+                ("w", _int), ("h", _int), ("Hp", _int), ("Wp", _int),
+                ("mean", _flt * 3), ("inv_std", _flt * 3), ("grid", GridParams),
+                ("img", ImgAugImage * IMG_AUG_MAX), ("src", _vp), ("dst", _vp)]
+
+
+class GridMaskArgs(ctypes.Structure):
+    _fields_ = [("planes", _i64), ("h", _int), ("w", _int), ("grid", GridParams), ("x", _vp)]
+
+
+class PasteRect(ctypes.Structure):
+    _fields_ = [("x0", _int), ("y0", _int), ("x1", _int), ("y1", _int), ("crop", _int)]
+
+
+class PastePatch(ctypes.Structure):
+    _fields_ = [("offset", _i64), ("hc", _int), ("wc", _int)]
+
+
+class ImgPasteArgs(ctypes.Structure):
+    _fields_ = [("N", _int), ("Hs", _int), ("Ws", _int), ("n_patches", _int), ("count", _int * IMG_AUG_MAX),
+                ("mixup", ctypes.c_double), ("rects", _vp), ("patches", _vp), ("rects_dev", _vp),
+                ("patches_dev", _vp), ("patch_bytes", _vp), ("patch_bytes_size", _i64), ("frames", _vp)]
+
+
 PTS_MAX_SEG = 16   # cmt_hip.h CMT_PTS_MAX_SEG
 
 
@@ -312,7 +351,8 @@ STRUCTS = {"gemm": GemmArgs, "attn": AttnArgs, "ln": LnArgs, "chain": ChainArgs,
            "fpn_lateral": FpnLateralArgs, "rows_to_nchw": RowsToNchwArgs,
            "img_stem": ImgStemArgs, "img_conv": ImgConvArgs, "img_concat": ImgConcatArgs, "img_gate": ImgGateArgs,
            "img_apply": ImgApplyArgs, "img_pool": ImgPoolArgs, "img_prepare": ImgPrepareArgs,
-           "img_resize": ImgResizeArgs, "pts_prepare": PtsPrepareArgs,
+           "img_resize": ImgResizeArgs, "img_augment": ImgAugmentArgs, "grid_mask": GridMaskArgs,
+           "img_paste": ImgPasteArgs, "pts_prepare": PtsPrepareArgs,
            "points_in_boxes": PointsInBoxesArgs, "pts_augment": PtsAugmentArgs, "boxes_augment": BoxesAugmentArgs}
 
 _LIB = None
@@ -441,6 +481,12 @@ def _load():
         "cmt_img_prepare": ([P(ImgPrepareArgs), _vp], _int),
         "cmt_img_resize_args_size": ([], _i64),
         "cmt_img_resize_prepare": ([P(ImgResizeArgs), _vp], _int),
+        "cmt_img_augment_args_size": ([], _i64),
+        "cmt_grid_mask_args_size": ([], _i64),
+        "cmt_img_paste_args_size": ([], _i64),
+        "cmt_img_augment": ([P(ImgAugmentArgs), _vp], _int),
+        "cmt_grid_mask": ([P(GridMaskArgs), _vp], _int),
+        "cmt_img_paste": ([P(ImgPasteArgs), _vp], _int),
         "cmt_pts_prepare_args_size": ([], _i64),
         "cmt_pts_prepare_workspace_bytes": ([_i64], _i64),
         "cmt_pts_prepare_tile_rows": ([], _int),

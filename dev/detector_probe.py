@@ -39,12 +39,18 @@ reference's algorithm in its own style of loop) on the host, and checks that bot
 both flips, range filter, shuffle), against the same chain as torch ops on the device (the inside test by
 broadcasting, boolean indexing, ``randperm``), in alternating windows of --iters calls.
 
+``--only img-augment`` (``--img-augment-out FILE``) times the image side of one coop training sample (3 infrastructure
+frames and 1 vehicle frame of 1200 x 1920, ``resize_lim`` drawn per agent, one paste list of 32 boxes per camera at
+mixup 0.5, GridMask on): ``native_imgaug.paste_images`` + ``augment_images`` against the same steps as torch ops on the
+device (per-rectangle ``F.interpolate`` and blend, ``F.interpolate`` of the frames, crop, normalise, pad, the mask built
+in numpy and uploaded as the reference does), in alternating windows of --iters samples.
+
 ``--img-precision`` (default ``ref``) is the image backbone's arithmetic (native_img.set_img_precision): ``fp16``
 runs VoVNet on the one-pass fp16 kernels; everything else is unchanged.
 
     python dev/detector_probe.py [--img-precision ref|fp16] [--points 300000] [--repeats 20] [--warmup 3]
-                                 [--iters 20] [--seed 0] [--out FILE] [--only resize|points|eval|augment]
-                                 [--resize-out FILE] [--augment-out FILE]
+                                 [--iters 20] [--seed 0] [--out FILE] [--only resize|points|eval|augment|img-augment]
+                                 [--resize-out FILE] [--augment-out FILE] [--img-augment-out FILE]
                                  [--points-out FILE] [--sweep-points 27000] [--sweeps K] [--eval-out FILE]
                                  [--eval-frames 800]
 
@@ -95,7 +101,9 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--img-precision", choices=("ref", "fp16"), default="ref")
     ap.add_argument("--out", default=None)
-    ap.add_argument("--only", choices=("resize", "points", "eval", "augment"), default=None, help="run this section alone")
+    ap.add_argument("--only", choices=("resize", "points", "eval", "augment", "img-augment"), default=None,
+                    help="run this section alone")
+    ap.add_argument("--img-augment-out", default=None, help="write the cmt_img_augment section to this file")
     ap.add_argument("--augment-out", default=None, help="write the cmt_pts_augment section to this file")
     ap.add_argument("--eval-out", default=None, help="write the detection-evaluation section to this file")
     ap.add_argument("--eval-frames", type=int, default=800, help="frames of the detection-evaluation section")
@@ -265,6 +273,9 @@ def main():
         return
     if args.only == "augment":
         augment_section(args, dev, say, lines)
+        return
+    if args.only == "img-augment":
+        img_augment_section(args, dev, say, lines)
         return
     frames = frame("cmt_fusion_nus")
     frame("cmtcoop_fusion_tumtraf")
@@ -606,6 +617,118 @@ def augment_section(args, dev, say, lines):
         "range mask and the permuted gather")
     say(f"peak device memory {torch.cuda.max_memory_allocated() / 2 ** 20:.0f} MiB")
     for path, text in ((args.out, lines), (args.augment_out, lines[first:])):
+        if path:
+            os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+            with open(path, "w") as f:
+                f.write("\n".join(text) + "\n")
+
+
+def img_augment_section(args, dev, say, lines):
+    """the image side of one coop training sample: paste_images + augment_images against torch ops on the device"""
+    import numpy as np
+    from projects.mmdet3d_plugin import native_img as NI
+    from projects.mmdet3d_plugin import native_imgaug as NIA
+    first = len(lines)
+    conf = dict(resize_lim=(0.94, 1.25), final_dim=(640, 1600), bot_pct_lim=(0.0, 0.0), rot_lim=(0.0, 0.0), H=900, W=1600,
+                rand_flip=False)
+    Hs, Ws, K, m = 1200, 1920, 32, 0.5
+    rs = np.random.RandomState(args.seed)
+    plans = NIA.sample_images_plan(conf, rs, 3) + NIA.sample_images_plan(conf, rs, 1)   # infrastructure, then vehicle
+    grid = None
+    while grid is None:
+        grid = NIA.sample_grid_mask(NIA.DETECTOR_GRID_MASK, 640, rs)
+    g = np.random.default_rng(args.seed + 9)
+    frames = torch.from_numpy(g.integers(0, 256, (4, Hs, Ws, 3), dtype=np.uint8)).to(dev)
+    patches = [g.integers(0, 256, (int(g.integers(30, 200)), int(g.integers(30, 200)), 3), dtype=np.uint8) for _ in range(K // 2)]
+    lists = []
+    for _ in range(4):
+        rows = []
+        for i in range(K):
+            w, h = int(g.integers(40, 300)), int(g.integers(40, 300))
+            x0, y0 = int(g.integers(0, Ws - w)), int(g.integers(0, Hs - h))
+            rows.append([x0, y0, x0 + w, y0 + h, i // 2 if i % 2 else -1])
+        lists.append(np.array(rows, np.int32))
+    say(f"--- {torch.cuda.get_device_name(0)}: the image side of one coop training sample, [4, {Hs}, {Ws}, 3] uint8 -> "
+        f"[4, 3, 640, 1600] fp32: {K} paste boxes per camera (half raw, half sampled, mixup {m}), resize to "
+        f"{[p['resize_dims'] for p in plans[::3]]}, crop, normalise, pad, GridMask d = {grid['d']}: (a) paste_images + "
+        f"augment_images and (b) torch ops on the device in alternating windows of {args.iters} samples, median of "
+        f"{args.repeats} (min .. max) after {args.warmup} warm-up samples, device events, ms per sample")
+    work_n, work_t = frames.clone(), frames.clone()
+    out = torch.empty((4, 3, 640, 1600), dtype=torch.float32, device=dev)
+    mean32, inv32 = NI.norm_constants(NI.IMG_MEAN, NI.IMG_STD)
+    mean_t = torch.from_numpy(mean32).to(dev).view(1, 3, 1, 1)
+    inv_t = torch.from_numpy(inv32).to(dev).view(1, 3, 1, 1)
+
+    def native_paste(buf):
+        return NIA.paste_images(buf, lists, patches, mixup_rate=m)
+
+    def native_aug(buf):
+        return NIA.augment_images(buf, plans, grid_mask=grid, out=out)
+
+    def native_fn():
+        return native_aug(native_paste(work_n))
+
+    def torch_mask():
+        h, w, d, l = 640, 1600, grid["d"], grid["l"]
+        hh, ww = int(1.5 * h), int(1.5 * w)
+        mask = np.ones((hh, ww), np.float32)
+        for i in range(hh // d):
+            mask[d * i + grid["st_h"]:min(d * i + grid["st_h"] + l, hh), :] *= 0
+        for i in range(ww // d):
+            mask[:, d * i + grid["st_w"]:min(d * i + grid["st_w"] + l, ww)] *= 0
+        mask = mask[(hh - h) // 2:(hh - h) // 2 + h, (ww - w) // 2:(ww - w) // 2 + w]
+        return 1 - torch.from_numpy(np.ascontiguousarray(mask)).to(dev)
+
+    def torch_fn(buf=None):
+        buf = work_t if buf is None else buf
+        dev_patches = [torch.from_numpy(p).to(dev).permute(2, 0, 1)[None].float() for p in patches]
+        for n in range(4):
+            for x0, y0, x1, y1, crop in lists[n].tolist():
+                reg = buf[n, y0:y1, x0:x1]
+                v = reg.float()
+                if crop < 0:
+                    reg.copy_((v * (1 - m) + v * m).to(torch.uint8))
+                else:
+                    c = F.interpolate(dev_patches[crop], size=(y1 - y0, x1 - x0), mode="bilinear", align_corners=False)
+                    reg.copy_((v * (1 - m) + c[0].permute(1, 2, 0) * m).to(torch.uint8))
+        res = torch.zeros((4, 3, 640, 1600), dtype=torch.float32, device=dev)
+        for lo, hi in ((0, 3), (3, 4)):
+            pl = plans[lo]
+            Wr, Hr = pl["resize_dims"]
+            x0, y0, x1, y1 = pl["crop"]
+            r = F.interpolate(buf[lo:hi].permute(0, 3, 1, 2).float(), size=(Hr, Wr), mode="bilinear", align_corners=False)
+            sx0, sy0, sx1, sy1 = max(x0, 0), max(y0, 0), min(x1, Wr), min(y1, Hr)
+            cropped = torch.zeros((hi - lo, 3, y1 - y0, x1 - x0), dtype=torch.float32, device=dev)
+            cropped[:, :, sy0 - y0:sy1 - y0, sx0 - x0:sx1 - x0] = r[:, :, sy0:sy1, sx0:sx1]
+            res[lo:hi, :, :y1 - y0, :x1 - x0] = (cropped - mean_t) * inv_t
+        return res * torch_mask()
+
+    a = native_aug(native_paste(frames.clone())).clone()
+    b = torch_fn(frames.clone())
+    diff = (a - b).abs()
+    for fn in (native_fn, torch_fn):
+        for _ in range(args.warmup):
+            fn()
+    torch.cuda.synchronize()
+    tn, tt, tp, ta = [], [], [], []
+    for _ in range(args.repeats):
+        tn.append(event_ms(lambda: [native_fn() for _ in range(args.iters)]) / args.iters)
+        tt.append(event_ms(lambda: [torch_fn() for _ in range(args.iters)]) / args.iters)
+    for _ in range(args.repeats):
+        tp.append(event_ms(lambda: [native_paste(work_n) for _ in range(args.iters)]) / args.iters)
+        ta.append(event_ms(lambda: [native_aug(work_n) for _ in range(args.iters)]) / args.iters)
+    tn, tt, tp, ta = med(tn), med(tt), med(tp), med(ta)
+    nbytes = 4 * 640 * 1600 * 3 * 4
+    say(f"largest |native - torch| of the two results {float(diff.max()):.4f} (normalised units, one grey level is "
+        f"{float(inv32.max()):.4f}; torch resamples in float32 and blends in float32), mean {float(diff.mean()):.2e}")
+    say(f"{'(a) paste + augment':>26} {fmt(tn)}   2 launches, 3 small uploads (rectangles, patch table, patch bytes)")
+    say(f"{'    paste_images alone':>26} {fmt(tp)}   pack + upload + cmt_img_paste over the lists' bounding rectangles")
+    say(f"{'    augment_images alone':>26} {fmt(ta)}   cmt_img_augment: {nbytes * 1e-6:.1f} MB written -> "
+        f"{nbytes / (ta[0] * 1e-3) * 1e-12:.2f} TB/s of stores")
+    say(f"{'(b) torch ops, device':>26} {fmt(tt)}   (a) / (b) {tn[0] / tt[0]:.3f}; {4 * K} rectangle blends, 2 "
+        "interpolations of the frames, crop, normalise, pad, mask build on the host + upload + multiply")
+    say("bench.py's headline (the inference frame) does not run this code")
+    for path, text in ((args.out, lines), (args.img_augment_out, lines[first:])):
         if path:
             os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
             with open(path, "w") as f:

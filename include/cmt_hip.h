@@ -1216,6 +1216,146 @@ typedef struct cmt_img_resize_args {
 int64_t cmt_img_resize_args_size(void);
 int cmt_img_resize_prepare(const cmt_img_resize_args* args, void* stream);
 
+/* ---- the training-side image pipeline (imgaug.hip; additive to ABI 25) ----------------------------
+ * THIS TEXT is the contract of the three entry points below: a restatement of the reference's host
+ * pipeline in which every rounding is fixed.  The parts that restate OpenCV (cv2.warpAffine,
+ * cv2.getRotationMatrix2D, cv2.resize) and PIL (Image.rotate by 0 degrees, taken as the identity) are
+ * written from memory; agreement with a real OpenCV or PIL has NOT been verified.  Every CMT_EINVAL
+ * condition is checked before any device work; no call synchronises with the host or allocates.
+ *
+ * cmt_img_augment: ResizeCropFlipImage[Coop](training=True) fused with NormalizeMultiviewImage and
+ * PadMultiViewImage, optionally with GridMask and the image branch of ModalMask3D, in one launch.
+ *   src: uint8 [N][Hs][Ws][3], contiguous (any byte alignment).  dst: fp32 [N][3][Hp][Wp], contiguous,
+ *   4-byte aligned (16-byte stores when Wp % 4 == 0 and dst is 16-byte aligned, scalar stores
+ *   otherwise); every element is written.  The crop size (w, h) is shared (final_dim); image n carries
+ *   img[n] = (Hr, Wr, x0, y0, flip, zero, iM[6]): the size it is resized to, the origin of its crop
+ *   window in resized pixels, the horizontal flip, ModalMask3D's "0. * img", and the inverse affine
+ *   map of the rotation (destination pixel -> pixel of the flipped crop), row-major 2 x 3.
+ *   For y < h and x < w the value before normalisation is
+ *     AX = rint(iM[0] * x * 1024)            AY = rint(iM[3] * x * 1024)
+ *     BX = rint((iM[1] * y + iM[2]) * 1024) + 16
+ *     BY = rint((iM[4] * y + iM[5]) * 1024) + 16
+ *          float64 products and sums, each rounded on its own (no FMA), rint = round-half-even
+ *     X = (BX + AX) >> 5,  Y = (BY + AY) >> 5     arithmetic shifts
+ *     ix = X >> 5, fx = X & 31, iy = Y >> 5, fy = Y & 31
+ *     val = ((32-fx)(32-fy) T(iy,ix) + fx(32-fy) T(iy,ix+1) + (32-fx)fy T(iy+1,ix) + fx fy T(iy+1,ix+1)) / 1024
+ *   (cv2.warpAffine(crop, M, (w, h)), INTER_LINEAR, constant border 0, on the float64 crop the reference
+ *   builds: positions quantised to 1/32 pixel, exact weights).  The integers are evaluated in 64 bits:
+ *   with |iM[k]| < 2^20 and w, h < 2^30 none exceeds 2^61, so nothing wraps.  val is a multiple of
+ *   1/1024 below 256 and its float32 form is exact.  The identity iM = {1,0,0, 0,1,0} gives fx = fy = 0,
+ *   ix = x, iy = y: an exact pass-through.
+ *   The caller's iM for a rotation by a degrees about (cx, cy) = (w / 2, h / 2) (native_imgaug.warp_inverse;
+ *   cv2.getRotationMatrix2D((cx, cy), a, 1), then cv2.warpAffine's own inversion), all in float64, in this
+ *   order of operations:
+ *     r = a * (pi / 180);  al = cos(r);  be = sin(r)
+ *     M = { al, be, (1 - al) * cx - be * cy,   -be, al, be * cx + (1 - al) * cy }
+ *     D = M[0] * M[4] - M[1] * M[3];  D = (D != 0) ? 1 / D : 0
+ *     A11 = M[4] * D;  A22 = M[0] * D;  M[0] = A11;  M[1] *= -D;  M[3] *= -D;  M[4] = A22
+ *     b1 = -M[0] * M[2] - M[1] * M[5];  b2 = -M[3] * M[2] - M[4] * M[5];  M[2] = b1;  M[5] = b2;  iM = M
+ *   (b1 and b2 use the updated M[0], M[1], M[3], M[4]).  a == 0 passes the identity itself, not this sequence.
+ *   Tap T(ty, tx): 0 outside [0, h) x [0, w).  Otherwise, with tx' = flip ? w - 1 - tx : tx, the resized
+ *   pixel (y0 + ty, x0 + tx'): 0 outside [0, Hr) x [0, Wr), else the byte of cmt_img_resize_prepare's
+ *   8-bit bilinear (source Hs x Ws resized to Hr x Wr) at that pixel, channel (to_rgb ? 2 - c : c).
+ *   With zero set every tap is 0.
+ *     dst[n][c][y][x] = fl32(fl32(val - mean[c]) * inv_std[c]);   0 for y >= h or x >= w.
+ *   GridMask: with grid.d > 0 every element of dst, the pad included, is then multiplied by
+ *   m(y, x) in {0.f, 1.f} and the float32 product is stored (a masked negative value stores -0.f):
+ *     hh = (int)(1.5 * Hp), ww = (int)(1.5 * Wp)    float64 product, truncated
+ *     Y = y + (hh - Hp) / 2, X = x + (ww - Wp) / 2  integer division
+ *     rowband = Y >= st_h && (Y - st_h) / d < hh / d && (Y - st_h) % d < l
+ *     colband = X >= st_w && (X - st_w) / d < ww / d && (X - st_w) % d < l
+ *     base = !((use_h && rowband) || (use_w && colband));   m = (mode == 1) ? !base : base
+ *   the reference's GridMask.forward for rotate == 1 (its only value in the configs: r = 0) and
+ *   offset == False; the mask is shared by the N images.  grid.d == 0: no mask.
+ *   CMT_EINVAL: a null struct, src or dst; N outside 1..CMT_IMG_AUG_MAX; Hs, Ws, w, h <= 0; Hp < h;
+ *   Wp < w; Hs, Ws, w, h, Hp, Wp >= 2^30; Hp * ceil(Wp / 4) >= 2^31; dst not 4-byte aligned; a NaN
+ *   mean or inv_std; per image Hr, Wr <= 0 or >= 2^30, |x0| or |y0| >= 2^30, a non-finite iM[k] or
+ *   |iM[k]| >= 2^20; grid.d < 0, or with grid.d > 0: d < 2, d >= 2^30, l < 1, l >= d, st_h or st_w
+ *   outside [0, d).
+ *
+ * cmt_grid_mask: the same predicate (Hp = h, Wp = w) applied in place to fp32 [planes][h][w]
+ *   (planes = n * c of a prepared batch): x[p][y][x] = fl32(x[p][y][x] * m(y, x)).  16-byte accesses
+ *   when w % 4 == 0 and x is 16-byte aligned, scalar ones otherwise.
+ *   CMT_EINVAL: a null struct or x; x not 4-byte aligned; planes, h or w <= 0; h, w >= 2^30;
+ *   planes * h * ceil(w / 4) >= 2^31; the grid conditions above with d > 0 required.
+ *
+ * cmt_img_paste: the pixel part of unified_sample (sample_2d=True) in place on uint8 frames
+ *   [N][Hs][Ws][3], before cmt_img_augment.  Camera n has an ordered list of count[n] rectangles
+ *   (x0, y0, x1, y1, crop), half-open as the reference's slices are, 0 <= x0 <= x1 <= Ws and
+ *   0 <= y0 <= y1 <= Hs; crop = -1 marks a box of the frame's own ground truth, crop >= 0 indexes the
+ *   patch table (offset, hc, wc): patch bytes [hc][wc][3] at patch_bytes + offset.  The tables are given
+ *   twice: rects / patches in HOST memory (rects is [N][CMT_PASTE_MAX_RECTS], only the first count[n]
+ *   of a row are read), which the entry validates and from which it takes each camera's bounding
+ *   rectangle, and rects_dev / patches_dev, the caller's device copies of the same bytes, which the
+ *   kernel reads.  The kernel writes only inside the bounding rectangle taken from the host table and
+ *   skips a device entry that fails the host-side conditions, so a stale device copy cannot make it
+ *   touch memory outside the frames and the patch buffer.
+ *   For every pixel, with v its 3 bytes, walk the camera's list in order over the rectangles that
+ *   contain it; m = mixup, om = 1 - m in float64, computed once on the host:
+ *     raw box (crop == -1):  m < 0: v unchanged;  m >= 0: v = trunc(fl64(v * om) + fl64(v * m)).
+ *       (The reference's saved crops are numpy VIEWS of the frame, not copies, so its "restitching"
+ *       reads the current pixel, whatever was pasted over it before; this is what the line above says.)
+ *     sampled box, patch not empty (hc > 0 and wc > 0): c = the patch resized to (x1 - x0) x (y1 - y0)
+ *       by the 8-bit bilinear of cmt_img_resize_prepare (S = wc / hc, R = x1 - x0 / y1 - y0), sampled
+ *       at (x - x0, y - y0);  m < 0: v = c;  m >= 0: v = trunc(fl64(v * om) + fl64(c * m)).
+ *     sampled box with an empty patch: skipped.
+ *   Products and the sum are separate float64 roundings (no FMA), per channel; trunc is the conversion
+ *   to uint8 of a value in [0, 255].  Pixels outside every rectangle are not written.  Each pixel is
+ *   read and written by one thread only, so the update in place is safe.
+ *   CMT_EINVAL: a null struct or frames; N outside 1..CMT_IMG_AUG_MAX; Hs, Ws <= 0 or >= 2^30; a
+ *   count[n] outside [0, CMT_PASTE_MAX_RECTS]; with any rectangle: null rects, rects_dev; a rectangle
+ *   outside the frame or with x1 < x0 or y1 < y0; crop < -1 or >= n_patches; n_patches < 0; with
+ *   n_patches > 0: null patches, patches_dev or patch_bytes; a patch with hc < 0, wc < 0, hc or wc
+ *   >= 2^15, offset < 0 or offset + 3 * hc * wc > patch_bytes_size; mixup NaN or > 1 (mixup < 0: plain
+ *   paste); a camera's bounding rectangle of 2^31 or more 64 x 4 pixel tiles. */
+#define CMT_IMG_AUG_MAX 16
+#define CMT_PASTE_MAX_RECTS 256
+typedef struct cmt_grid_params {
+    int d, l, st_h, st_w;                         /* d == 0: no mask (cmt_img_augment only) */
+    int use_h, use_w, mode, reserved;
+} cmt_grid_params;
+typedef struct cmt_img_aug_image {
+    int Hr, Wr;                                   /* the size this frame is resized to */
+    int x0, y0;                                   /* crop origin in pixels of the resized frame */
+    int flip, zero;
+    double iM[6];                                 /* inverse affine map of the rotation, row-major 2 x 3 */
+} cmt_img_aug_image;
+typedef struct cmt_img_augment_args {
+    int N, Hs, Ws, to_rgb;
+    int w, h, Hp, Wp;                             /* shared crop size and padded size */
+    float mean[3], inv_std[3];                    /* by destination channel */
+    cmt_grid_params grid;
+    cmt_img_aug_image img[CMT_IMG_AUG_MAX];
+    const void* src;
+    void* dst;
+} cmt_img_augment_args;
+typedef struct cmt_grid_mask_args {
+    int64_t planes;
+    int h, w;
+    cmt_grid_params grid;
+    void* x;
+} cmt_grid_mask_args;
+typedef struct cmt_paste_rect { int x0, y0, x1, y1, crop; } cmt_paste_rect;
+typedef struct cmt_paste_patch { int64_t offset; int hc, wc; } cmt_paste_patch;
+typedef struct cmt_img_paste_args {
+    int N, Hs, Ws, n_patches;
+    int count[CMT_IMG_AUG_MAX];                   /* rectangles per camera */
+    double mixup;                                 /* < 0: plain paste */
+    const cmt_paste_rect* rects;                  /* host [N][CMT_PASTE_MAX_RECTS] */
+    const cmt_paste_patch* patches;               /* host [n_patches] */
+    const void* rects_dev;                        /* device copy of rects */
+    const void* patches_dev;                      /* device copy of patches */
+    const void* patch_bytes;                      /* device, packed uint8 patches */
+    int64_t patch_bytes_size;
+    void* frames;                                 /* device uint8 [N][Hs][Ws][3], updated in place */
+} cmt_img_paste_args;
+int64_t cmt_img_augment_args_size(void);
+int64_t cmt_grid_mask_args_size(void);
+int64_t cmt_img_paste_args_size(void);
+int cmt_img_augment(const cmt_img_augment_args* args, void* stream);
+int cmt_grid_mask(const cmt_grid_mask_args* args, void* stream);
+int cmt_img_paste(const cmt_img_paste_args* args, void* stream);
+
 /* ---- raw LiDAR sweeps -> the detector's points (ptsprep.hip; additive to ABI 25) -------------------
  * cmt_pts_prepare: the point side of the reference's test pipeline for ONE cloud (one agent's key frame
  * plus its sweeps): LoadPointsFromMultiSweeps[Coop] (remove_close, sweep -> key-frame transform, time
