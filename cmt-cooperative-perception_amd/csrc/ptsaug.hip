@@ -17,38 +17,9 @@
 // The boxes are staged in LDS as centre, half extents and one sinf / cosf pair each: both launches of
 // cmt_pts_augment compute them with the same instructions, so a point near a face falls on the same side in both.
 // Contraction is off for the row functions (and for the file, see the Makefile): the contract's products and
-// sums are separate roundings.
-#include "cmt_common.h"
-
-#include <cmath>
-
-constexpr int AUG_T = 1024;           // slots (points) per tile
-constexpr int AUG_THREADS = 256;
-constexpr int AUG_R = AUG_T / AUG_THREADS;
-constexpr int AUG_CHUNKS = AUG_T / 64;
-constexpr int PIB_CB = 64;            // boxes staged per pass of cmt_points_in_boxes
-
-struct aug_box {
-    float cx, cy, zb, hx, hy, dz, c, s;
-};
-
-__device__ __forceinline__ aug_box aug_stage(const float* b) {
-#pragma clang fp contract(off)
-    aug_box o;
-    o.cx = b[0], o.cy = b[1], o.zb = b[2];
-    o.hx = b[3] * 0.5f, o.hy = b[4] * 0.5f, o.dz = b[5];
-    o.c = cosf(b[6]), o.s = sinf(b[6]);
-    return o;
-}
-
-// every comparison is false for a NaN operand: a NaN in the point or the box gives "outside"
-__device__ __forceinline__ bool aug_inside(const aug_box& b, float x, float y, float z) {
-#pragma clang fp contract(off)
-    const float ex = x - b.cx, ey = y - b.cy, ez = z - b.zb;
-    const float lx = ex * b.c + ey * b.s;
-    const float ly = ey * b.c - ex * b.s;
-    return __builtin_fabsf(lx) < b.hx && __builtin_fabsf(ly) < b.hy && ez > 0.f && ez < b.dz;
-}
+// sums are separate roundings.  The tile constants, aug_stage / aug_inside and the wave helpers are aug_inside.h,
+// which gtdb.hip includes too: its extraction puts a point near a face on the same side as the calls here.
+#include "aug_inside.h"
 
 // rotation, scale, translation and flips on v[0..2]
 __device__ __forceinline__ void aug_xform_point(const cmt_aug_xform& t, float* v) {
@@ -71,18 +42,6 @@ __device__ __forceinline__ void aug_xform_point(const cmt_aug_xform& t, float* v
     }
     if (t.flip_h) v[1] = -v[1];
     if (t.flip_v) v[0] = -v[0];
-}
-
-__device__ __forceinline__ int aug_wave_sum(int v) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
-__device__ __forceinline__ int aug_clamped(const int* word, unsigned n) {
-    if (!word) return (int)n;
-    const int c = *word;
-    return c < 0 ? 0 : ((unsigned)c > n ? (int)n : c);
 }
 
 // ---- cmt_points_in_boxes ------------------------------------------------------------------------------------
@@ -391,8 +350,6 @@ static const char* aug_xform_error(const cmt_aug_xform& t) {
     }
     return nullptr;
 }
-
-static inline bool aug_aligned(const void* q, uintptr_t a) { return (((uintptr_t)q) & (a - 1)) == 0; }
 
 extern "C" int64_t cmt_points_in_boxes_args_size(void) { return (int64_t)sizeof(cmt_points_in_boxes_args); }
 extern "C" int64_t cmt_pts_augment_args_size(void) { return (int64_t)sizeof(cmt_pts_augment_args); }

@@ -343,6 +343,27 @@ class BoxesAugmentArgs(ctypes.Structure):
                 ("boxes", _vp), ("labels", _vp), ("out_boxes", _vp), ("out_labels", _vp), ("count", _vp)]
 
 
+GTDB_MAX_BOXES = 1024     # cmt_hip.h CMT_GTDB_MAX_BOXES
+GTDB_MAX_COLLIDE = 512    # cmt_hip.h CMT_GTDB_MAX_COLLIDE
+
+
+class GtdbExtractArgs(ctypes.Structure):
+    _fields_ = [("N", _i64), ("cap", _i64), ("M", _int), ("F", _int), ("D", _int), ("reserved", _int),
+                ("points", _vp), ("count_in", _vp), ("boxes", _vp), ("rows", _vp), ("offsets", _vp),
+                ("workspace", _vp), ("workspace_bytes", _i64)]
+
+
+class GtdbGatherArgs(ctypes.Structure):
+    _fields_ = [("n_rows", _i64), ("n_dst", _i64), ("K", _int), ("F", _int),
+                ("rows", _vp), ("seg_offset", _vp), ("seg_len", _vp), ("dst_offset", _vp), ("centre", _vp),
+                ("dst", _vp)]
+
+
+class GtdbCollideArgs(ctypes.Structure):
+    _fields_ = [("n_gt", _int), ("n_s", _int), ("D", _int), ("reserved", _int),
+                ("boxes", _vp), ("group", _vp), ("keep", _vp), ("count", _vp)]
+
+
 STRUCTS = {"gemm": GemmArgs, "attn": AttnArgs, "ln": LnArgs, "chain": ChainArgs, "gemm_ex": GemmExArgs,
            "attn_train": AttnTrainArgs, "ln_train": LnTrainArgs, "bn": BnArgs, "det_loss": DetLossArgs,
            "match_cost": MatchCostArgs, "adamw": AdamwArgs, "mlp2": Mlp2Args, "mlp2_affine": Mlp2AffineArgs, "lsap": LsapArgs,
@@ -353,7 +374,8 @@ STRUCTS = {"gemm": GemmArgs, "attn": AttnArgs, "ln": LnArgs, "chain": ChainArgs,
            "img_apply": ImgApplyArgs, "img_pool": ImgPoolArgs, "img_prepare": ImgPrepareArgs,
            "img_resize": ImgResizeArgs, "img_augment": ImgAugmentArgs, "grid_mask": GridMaskArgs,
            "img_paste": ImgPasteArgs, "pts_prepare": PtsPrepareArgs,
-           "points_in_boxes": PointsInBoxesArgs, "pts_augment": PtsAugmentArgs, "boxes_augment": BoxesAugmentArgs}
+           "points_in_boxes": PointsInBoxesArgs, "pts_augment": PtsAugmentArgs, "boxes_augment": BoxesAugmentArgs,
+           "gtdb_extract": GtdbExtractArgs, "gtdb_gather": GtdbGatherArgs, "gtdb_collide": GtdbCollideArgs}
 
 _LIB = None
 
@@ -500,6 +522,13 @@ def _load():
         "cmt_points_in_boxes": ([P(PointsInBoxesArgs), _vp], _int),
         "cmt_pts_augment": ([P(PtsAugmentArgs), _vp], _int),
         "cmt_boxes_augment": ([P(BoxesAugmentArgs), _vp], _int),
+        "cmt_gtdb_extract_args_size": ([], _i64),
+        "cmt_gtdb_gather_args_size": ([], _i64),
+        "cmt_gtdb_collide_args_size": ([], _i64),
+        "cmt_gtdb_extract_workspace_bytes": ([_i64, _int], _i64),
+        "cmt_gtdb_extract": ([P(GtdbExtractArgs), _vp], _int),
+        "cmt_gtdb_gather": ([P(GtdbGatherArgs), _vp], _int),
+        "cmt_gtdb_collide": ([P(GtdbCollideArgs), _vp], _int),
         "cmt_adamw_step": ([P(AdamwArgs), _vp], _int),
     }
     for name, (args, res) in sig.items():

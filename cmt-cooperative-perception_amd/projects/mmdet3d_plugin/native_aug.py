@@ -10,8 +10,9 @@ PointsRangeFilter[Coop] and PointShuffle[Coop] in two launches with no host read
 limit_yaw) and can write the head's gravity-centre layout for ``head.forward_train``.  ``points_in_boxes`` is the
 inside test on its own; it gives the evaluator its ``gt_num_pts``.
 
-The database sampler itself (its collision test and its files) stays with the caller; ``unified_sample``'s image
-pasting and the image side of the training pipeline are native_imgaug.py.
+The database sampler (the in-memory database, its collision test and the gather of the chosen objects) is
+native_gtdb.py; its files stay with the caller.  ``unified_sample``'s image pasting and the image side of the
+training pipeline are native_imgaug.py.
 
 Like native_pts.py: argument checks raise ValueError before the device check, tensors must live on a HIP device,
 there is no CPU fallback and no wrapper synchronises with the host.

@@ -45,12 +45,17 @@ mixup 0.5, GridMask on): ``native_imgaug.paste_images`` + ``augment_images`` aga
 device (per-rectangle ``F.interpolate`` and blend, ``F.interpolate`` of the frames, crop, normalise, pad, the mask built
 in numpy and uploaded as the reference does), in alternating windows of --iters samples.
 
+``--only gtdb`` (``--gtdb-out FILE``) times the ground-truth database (native_gtdb.py) in alternating windows of --iters
+calls: ``GtDatabase.add_frame`` on one cloud of --points rows with 64 boxes against a boolean-mask chain per box and
+``torch.cat``; and ``UnifiedDataBaseSampler.sample_all`` + ``augment_points`` on a database of 320 objects against the
+same draws and collision test followed by torch ops per object and per paste box.
+
 ``--img-precision`` (default ``ref``) is the image backbone's arithmetic (native_img.set_img_precision): ``fp16``
 runs VoVNet on the one-pass fp16 kernels; everything else is unchanged.
 
     python dev/detector_probe.py [--img-precision ref|fp16] [--points 300000] [--repeats 20] [--warmup 3]
-                                 [--iters 20] [--seed 0] [--out FILE] [--only resize|points|eval|augment|img-augment]
-                                 [--resize-out FILE] [--augment-out FILE] [--img-augment-out FILE]
+                                 [--iters 20] [--seed 0] [--out FILE] [--only resize|points|eval|augment|img-augment|gtdb]
+                                 [--gtdb-out FILE] [--resize-out FILE] [--augment-out FILE] [--img-augment-out FILE]
                                  [--points-out FILE] [--sweep-points 27000] [--sweeps K] [--eval-out FILE]
                                  [--eval-frames 800]
 
@@ -101,8 +106,9 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--img-precision", choices=("ref", "fp16"), default="ref")
     ap.add_argument("--out", default=None)
-    ap.add_argument("--only", choices=("resize", "points", "eval", "augment", "img-augment"), default=None,
+    ap.add_argument("--only", choices=("resize", "points", "eval", "augment", "img-augment", "gtdb"), default=None,
                     help="run this section alone")
+    ap.add_argument("--gtdb-out", default=None, help="write the ground-truth database section to this file")
     ap.add_argument("--img-augment-out", default=None, help="write the cmt_img_augment section to this file")
     ap.add_argument("--augment-out", default=None, help="write the cmt_pts_augment section to this file")
     ap.add_argument("--eval-out", default=None, help="write the detection-evaluation section to this file")
@@ -276,6 +282,9 @@ def main():
         return
     if args.only == "img-augment":
         img_augment_section(args, dev, say, lines)
+        return
+    if args.only == "gtdb":
+        gtdb_section(args, dev, say, lines)
         return
     frames = frame("cmt_fusion_nus")
     frame("cmtcoop_fusion_tumtraf")
@@ -617,6 +626,161 @@ def augment_section(args, dev, say, lines):
         "range mask and the permuted gather")
     say(f"peak device memory {torch.cuda.max_memory_allocated() / 2 ** 20:.0f} MiB")
     for path, text in ((args.out, lines), (args.augment_out, lines[first:])):
+        if path:
+            os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+            with open(path, "w") as f:
+                f.write("\n".join(text) + "\n")
+
+
+def gtdb_section(args, dev, say, lines):
+    """the ground-truth database: add_frame, and sample_all + augment_points, against torch ops on the device"""
+    import math
+    import numpy as np
+    from projects.mmdet3d_plugin import native_aug as NA
+    from projects.mmdet3d_plugin import native_gtdb as NG
+    from projects.mmdet3d_plugin import synthetic as S
+    first = len(lines)
+    N, M, FR = args.points, 64, 5
+    pcr = [-54.0, -54.0, -5.0, 54.0, 54.0, 3.0]
+    classes = ["car", "truck", "construction_vehicle", "bus", "trailer", "barrier", "motorcycle", "bicycle", "pedestrian",
+               "traffic_cone"]
+    groups = dict(car=2, truck=3, construction_vehicle=7, bus=4, trailer=6, barrier=2, motorcycle=6, bicycle=6,
+                  pedestrian=2, traffic_cone=2)
+    say(f"--- {torch.cuda.get_device_name(0)}: ground-truth database (cmt_gtdb_extract / _collide / _gather), clouds of {N} "
+        f"rows (F = 5), {M} boxes a frame; (a) native and (b) torch ops on the device in alternating windows of "
+        f"{args.iters} calls, median of {args.repeats} (min .. max) after {args.warmup} warm-up calls, device events "
+        "(they span the calls' host time and host reads), ms per call")
+    rs = np.random.RandomState(args.seed)
+
+    def boxes_of(n):
+        b = np.zeros((n, 7), np.float32)
+        b[:, :2] = rs.uniform(-45, 45, (n, 2))
+        b[:, 2] = rs.uniform(-4.5, -3.5, n)
+        b[:, 3:6] = rs.uniform(1.5, 5.0, (n, 3))
+        b[:, 6] = rs.uniform(-math.pi, math.pi, n)
+        return b
+
+    clouds = [S.synthetic_points(N, pcr, seed=args.seed + i, device=dev, margin=2.0) for i in range(FR)]
+    frames = [(boxes_of(M), [classes[(i + f) % len(classes)] for i in range(M)]) for f in range(FR)]
+    db = NG.GtDatabase(classes, 5, dev, capacity_rows=N)
+
+    def reset():
+        db.used_rows, db.db_infos, db._group_counter, db._frames = 0, {}, 0, 0
+
+    def native_add():
+        reset()
+        return db.add_frame(clouds[0], frames[0][0], frames[0][1])
+
+    def inside_mask(pts, b):
+        d = pts[:, :3] - b[:3]
+        c, s_ = torch.cos(b[6]), torch.sin(b[6])
+        lx, ly = d[:, 0] * c + d[:, 1] * s_, d[:, 1] * c - d[:, 0] * s_
+        return (lx.abs() < b[3] * 0.5) & (ly.abs() < b[4] * 0.5) & (d[:, 2] > 0) & (d[:, 2] < b[5])
+
+    dev_boxes0 = torch.from_numpy(frames[0][0]).to(dev)
+
+    def torch_add():
+        segs = []
+        for b in dev_boxes0:
+            seg = clouds[0][inside_mask(clouds[0], b)]            # the index is a host read, once per box
+            seg[:, :3] -= b[:3]
+            segs.append(seg)
+        return torch.cat(segs), [int(s_.shape[0]) for s_ in segs]
+
+    added = native_add()
+    rows_t, lens_t = torch_add()
+    same = [a["num_points_in_gt"] for a in added] == lens_t and torch.equal(db.rows[:db.used_rows], rows_t)
+    for fn in (native_add, torch_add):
+        for _ in range(args.warmup):
+            fn()
+    torch.cuda.synchronize()
+    ta, tb = [], []
+    for _ in range(args.repeats):
+        ta.append(event_ms(lambda: [native_add() for _ in range(args.iters)]) / args.iters)
+        tb.append(event_ms(lambda: [torch_add() for _ in range(args.iters)]) / args.iters)
+    ta, tb = med(ta), med(tb)
+    say(f"add_frame: {sum(lens_t)} rows in {M} segments; the two results are "
+        f"{'bit-equal' if same else 'not bit-equal (torch rounds the inside test differently for a point at a face)'}")
+    say(f"{'(a) GtDatabase.add_frame':>34} {fmt(ta)}   box upload, 3 launches, one read of offsets, {M} host records")
+    say(f"{'(b) mask chain per box, cat':>34} {fmt(tb)}   (a) / (b) {ta[0] / tb[0]:.3f}; {M} boolean indexings (a host read "
+        "each), the subtraction, one cat")
+
+    # the sampler: a database of FR frames, one scene of 20 ground-truth boxes
+    reset()
+    for f in range(FR):
+        db.add_frame(clouds[f], frames[f][0], frames[f][1])
+    gt, gt_labels = boxes_of(20), rs.randint(0, len(classes), 20)
+    scene = S.synthetic_points(N, pcr, seed=args.seed + 50, device=dev, margin=2.0)
+    params = dict(angle=0.31, scale=1.04, trans=np.array([0.4, -0.3, 0.1]), flip_h=True, flip_v=True)
+    prepare = dict(filter_by_difficulty=[-1], filter_by_min_points={k: 5 for k in classes})
+    out = torch.empty((N + db.used_rows, 5), dtype=torch.float32, device=dev)
+    ws = NA.PointsWorkspace()
+    rT = torch.from_numpy(NA.rotation_matrix(params["angle"]).T.astype(np.float32)).to(dev)
+    t32 = torch.from_numpy(params["trans"].astype(np.float32)).to(dev)
+    lo, hi = torch.tensor(pcr[:3], device=dev), torch.tensor(pcr[3:], device=dev)
+    seg_list = {id(i): db.rows[i["segment"][0]:i["segment"][0] + i["segment"][1]] for v in db.db_infos.values() for i in v}
+    sampler = {}
+
+    def fresh():
+        for k in ("a", "b"):
+            sampler[k] = NG.UnifiedDataBaseSampler(db, 1.0, prepare, groups, classes, np.random.RandomState(args.seed + 7))
+
+    def native_sample():
+        ret = sampler["a"].sample_all(gt, gt_labels)
+        if ret is None:
+            return NA.augment_points(scene, params, point_cloud_range=pcr, out=out[:N], workspace=ws)
+        n_in = N + ret["points"].shape[0]
+        return NA.augment_points(scene, params, paste_points=ret["points"], paste_boxes=ret["gt_bboxes_3d"],
+                                 point_cloud_range=pcr, out=out[:n_in], workspace=ws)
+
+    def torch_sample():
+        s_ = sampler["b"]
+        cand, group = [], []
+        for g, (name, num) in enumerate(zip(s_.sample_classes, s_.sample_counts(gt_labels))):
+            if num > 0:
+                drawn = s_.sampler_dict[name].sample(num)
+                cand += drawn
+                group += [g] * len(drawn)
+        sp = np.stack([c["box3d_lidar"] for c in cand])
+        keep, _ = NG.collide(torch.from_numpy(np.concatenate([gt, sp])).to(dev), len(gt), group)
+        kept = np.nonzero(keep.cpu().numpy())[0]
+        parts, alive = [], torch.ones(N, dtype=torch.bool, device=dev)
+        for i in kept:
+            b = torch.from_numpy(sp[i]).to(dev)
+            seg = seg_list[id(cand[i])].clone()
+            seg[:, :3] += b[:3]
+            parts.append(seg)
+            alive &= ~inside_mask(scene, b)
+        pts = torch.cat([scene[alive]] + parts)
+        pts[:, :3] = pts[:, :3] @ rT
+        pts[:, :3] *= params["scale"]
+        pts[:, :3] += t32
+        pts[:, 1] = -pts[:, 1]
+        pts[:, 0] = -pts[:, 0]
+        return pts[((pts[:, :3] > lo) & (pts[:, :3] < hi)).all(1)]
+
+    fresh()
+    padded, count = native_sample()
+    k = int(count.item())
+    tor = torch_sample()
+    diff = float((padded[:k] - tor).abs().max()) if tor.shape[0] == k else float("nan")
+    for _ in range(args.warmup):
+        native_sample(), torch_sample()
+    torch.cuda.synchronize()
+    tn, tt = [], []
+    for _ in range(args.repeats):
+        tn.append(event_ms(lambda: [native_sample() for _ in range(args.iters)]) / args.iters)
+        tt.append(event_ms(lambda: [torch_sample() for _ in range(args.iters)]) / args.iters)
+    tn, tt = med(tn), med(tt)
+    say(f"sample_all + augment_points: database of {len(db)} objects in {db.used_rows} rows, {len(gt)} ground-truth boxes, "
+        f"sample_groups of the nuScenes configs; first call kept {k} rows, the torch chain {tor.shape[0]}, largest "
+        f"coordinate distance {diff:.2e} m (the torch matmul fixes no order of its sums); both sides draw the same "
+        "candidates from their own sampler and run cmt_gtdb_collide with one read of keep")
+    say(f"{'(a) sample_all + augment_points':>34} {fmt(tn)}   collide, read keep, table upload, gather, 2 augment launches")
+    say(f"{'(b) torch ops per object and box':>34} {fmt(tt)}   (a) / (b) {tn[0] / tt[0]:.3f}; clone + add per object, a "
+        "mask chain per paste box, one boolean indexing, cat, matmul, 4 in-place passes, the range mask")
+    say(f"peak device memory {torch.cuda.max_memory_allocated() / 2 ** 20:.0f} MiB")
+    for path, text in ((args.out, lines), (args.gtdb_out, lines[first:])):
         if path:
             os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
             with open(path, "w") as f:

@@ -1651,6 +1651,119 @@ int cmt_points_in_boxes(const cmt_points_in_boxes_args* args, void* stream);
 int cmt_pts_augment(const cmt_pts_augment_args* args, void* stream);
 int cmt_boxes_augment(const cmt_boxes_augment_args* args, void* stream);
 
+/* ---- ground-truth database (gtdb.hip; additive to ABI 25) ---------------------------------------------
+ * What create_groundtruth_database builds and UnifiedDataBaseSampler / sample_class_v2 do with it, without
+ * the files: the points of every annotated box as a segment of one device buffer, the BEV collision test
+ * with its greedy loop, and the gather of the chosen segments into the paste rows of cmt_pts_augment.
+ * THIS TEXT is the contract.  The conventions are mmdet3d v1.0.0rc6's as the reference calls them
+ * (box_np_ops.points_in_rbbox, box_np_ops.center_to_corner_box2d, data_augment_utils.box_collision_test,
+ * dbsampler.BatchSampler); they are not compared with an installed mmdet3d.
+ * fl32 = one rounding to float32; no operation below is fused with another.
+ * All three calls: caller-owned buffers, stream-ordered, no allocation, no host synchronisation, no
+ * workgroup waits for another: graph-capturable.  Every output element has exactly one writer and there are
+ * no atomics: results are bitwise repeatable.  Inputs and outputs must not overlap.
+ *
+ * cmt_gtdb_extract: one frame.  points fp32 [N][F], F 3..8; count_in null or a device int32 clamped to
+ *   [0, N] (rows at or beyond it belong to no box); boxes fp32 [M][D], D 7 or 9, M <= CMT_GTDB_MAX_BOXES,
+ *   N < 2^31 and N * M < 2^31.  rows fp32 [cap][F], offsets int32 [M + 1].
+ *   Row i of the cloud belongs to segment b iff the inside test of the section above holds for point i and
+ *   box b, evaluated with the instructions of cmt_points_in_boxes: it binds only points farther than
+ *   1e-4 * (1 + max |coordinate|) metres from every face plane of every box (max over the point and the box
+ *   centre); nearer ones may fall on either side, the same side as in cmt_points_in_boxes and in every launch
+ *   of this call.  A NaN in the point or the box, or dx, dy or dz <= 0, gives "outside".  A point inside
+ *   several boxes appears in each of them (points[point_indices[:, b]]).
+ *   offsets[b] = the number of (point, box) hits of the boxes < b; offsets[M] = the total, never capped.
+ *   Segment b is rows [offsets[b], offsets[b + 1]) in cloud order.  Columns 0..2 of a row are
+ *   fl32(p_k - box_k), k = 0, 1, 2, with box_2 = z_bottom (gt_points[:, :3] -= gt_boxes_3d[b, :3]); columns 3
+ *   and beyond are copied bit for bit.  A destination row at or beyond cap is not written; nothing outside
+ *   rows [0, min(total, cap)) is touched, and cap == 0 (rows may be null) gives the offsets alone.
+ *   Three launches: the hits of every (tile, box) pair over tiles of cmt_pts_augment_tile_rows() points,
+ *   boxes staged cmt_points_in_boxes_chunk() at a time; one workgroup that scans them; a scatter that
+ *   evaluates the same function again and skips every (tile, box chunk) pair without a hit.  The workspace
+ *   (cmt_gtdb_extract_workspace_bytes(N, M) bytes, 4-byte aligned) is rewritten by every call before it is read.
+ *   CMT_EINVAL before any device work: N, N * M, M, F, D or cap (outside [0, 2^31)) out of range; points
+ *   null or misaligned with N > 0; boxes null or misaligned with M > 0; offsets null or misaligned; a
+ *   misaligned count_in or rows; rows null with cap > 0; with N, M > 0 a null or misaligned workspace or
+ *   workspace_bytes below cmt_gtdb_extract_workspace_bytes(N, M).
+ *
+ * cmt_gtdb_gather: K <= CMT_AUG_MAX_BOXES segments in one launch.  rows fp32 [n_rows][F] (segments as
+ *   cmt_gtdb_extract writes them), device int32 tables seg_offset, seg_len, dst_offset [K], centre fp32 [K][3],
+ *   dst fp32 [n_dst][F].  For k < K and i < seg_len[k]: dst[dst_offset[k] + i] = rows[seg_offset[k] + i] with
+ *   columns 0..2 fl32(v + centre[k][c]) (s_points.translate(info['box3d_lidar'][:3])) and the rest copied bit
+ *   for bit.  The segments must not overlap in dst (one writer per row).  A source row outside [0, n_rows)
+ *   or a destination row outside [0, n_dst) moves nothing.
+ *   CMT_EINVAL before any device work: K, F, n_rows or n_dst out of range; a misaligned buffer; with K > 0
+ *   a null table or centre; with K, n_rows, n_dst > 0 a null rows or dst.
+ *
+ * cmt_gtdb_collide: boxes fp32 [n][D], n = n_gt + n_s <= CMT_GTDB_MAX_COLLIDE: n_gt boxes to avoid, then n_s
+ *   candidates.  group: a HOST int32 [n_s], non-decreasing, read before the call returns: the sample_class_v2
+ *   call (the class) each candidate belongs to.  keep int32 [n_s] (0 / 1) and count (device int32) are written.
+ *   Corners (center_to_corner_box2d, origin 0.5), float32, one sinf / cosf pair (s, c) per box, for k = 0..3
+ *   with (sx, sy) = (-,-), (-,+), (+,+), (+,-):  lx = sx * fl32(dx * 0.5f),  ly = sy * fl32(dy * 0.5f),
+ *     X_k = fl32(fl32(fl32(lx * c) - fl32(ly * s)) + x),   Y_k = fl32(fl32(fl32(lx * s) + fl32(ly * c)) + y)
+ *   (counter-clockwise by yaw, the rotation sense of the inside test).  The stand-up rectangle of a box is
+ *   the min and max of its X_k and of its Y_k.
+ *   collide(P, Q) is box_collision_test(..., clockwise=True) for the pair, every difference, product and
+ *   comparison in float32:
+ *     iw = fl32(min(P.xmax, Q.xmax) - max(P.xmin, Q.xmin)); not iw > 0: no.  ih likewise in y; not ih > 0: no.
+ *     For the edges (A, B) = (P_k, P_k+1) and (C, D) = (Q_l, Q_l+1), k and l 0..3 (indices mod 4), k outer:
+ *       acd = (D.y - A.y) * (C.x - A.x) > (C.y - A.y) * (D.x - A.x)
+ *       bcd = (D.y - B.y) * (C.x - B.x) > (C.y - B.y) * (D.x - B.x)
+ *       abc = (C.y - A.y) * (B.x - A.x) > (B.y - A.y) * (C.x - A.x)
+ *       abd = (D.y - A.y) * (B.x - A.x) > (B.y - A.y) * (D.x - A.x)
+ *       acd != bcd && abc != abd: yes (the edges cross).
+ *     Otherwise yes iff P contains Q or, failing that, Q contains P.  "P contains Q": for every corner Q_l and
+ *     every edge k of P, with v = P_k+1 - P_k:
+ *       cross = fl32(fl32(v.y * (P_k.x - Q_l.x)) - fl32(v.x * (P_k.y - Q_l.y))) < 0   (cross >= 0 ends it)
+ *   The greedy loop takes the candidates in order.  Candidate i is rejected iff collide(i, j) for a live box
+ *   j != i, and then leaves the live set at once (the reference clears its row and column); otherwise it is
+ *   kept.  Live are: every box to avoid; a kept candidate of an earlier group; a candidate of i's own group
+ *   that has not been rejected yet, later ones included.  count = the number kept.
+ *   The contract binds only scenes in which every comparison the sequential evaluation above makes (with its
+ *   early exits) has |lhs - rhs| > tol = 2^-16 * (1 + Cmax) * (1 + Emax), Cmax the largest |corner
+ *   coordinate| and Emax the largest box diagonal of the scene; boxes must be finite.  One workgroup; the
+ *   matrix collide(candidate, any box) is kept as bits in LDS (32 KB at n = 512) and one wave runs the loop.
+ *   CMT_EINVAL before any device work: n_gt or n_s negative or n_gt + n_s > CMT_GTDB_MAX_COLLIDE; D not 7 or
+ *   9; with n_s > 0 a null group or one that decreases; count null or misaligned; boxes null or misaligned
+ *   with n > 0; keep null or misaligned with n_s > 0. */
+#define CMT_GTDB_MAX_BOXES 1024
+#define CMT_GTDB_MAX_COLLIDE 512
+typedef struct cmt_gtdb_extract_args {
+    int64_t N, cap;
+    int M, F, D, reserved;
+    const void* points;
+    const int* count_in;
+    const void* boxes;
+    void* rows;
+    int* offsets;
+    void* workspace;
+    int64_t workspace_bytes;
+} cmt_gtdb_extract_args;
+typedef struct cmt_gtdb_gather_args {
+    int64_t n_rows, n_dst;
+    int K, F;
+    const void* rows;
+    const int* seg_offset;
+    const int* seg_len;
+    const int* dst_offset;
+    const void* centre;
+    void* dst;
+} cmt_gtdb_gather_args;
+typedef struct cmt_gtdb_collide_args {
+    int n_gt, n_s, D, reserved;
+    const void* boxes;
+    const int* group;   /* host */
+    int* keep;
+    int* count;
+} cmt_gtdb_collide_args;
+int64_t cmt_gtdb_extract_args_size(void);
+int64_t cmt_gtdb_gather_args_size(void);
+int64_t cmt_gtdb_collide_args_size(void);
+int64_t cmt_gtdb_extract_workspace_bytes(int64_t N, int M);   /* 0 for N <= 0 or M <= 0 */
+int cmt_gtdb_extract(const cmt_gtdb_extract_args* args, void* stream);
+int cmt_gtdb_gather(const cmt_gtdb_gather_args* args, void* stream);
+int cmt_gtdb_collide(const cmt_gtdb_collide_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
