@@ -33,10 +33,16 @@ from typing import Any, List, Optional, Tuple
 import numpy as np
 
 __all__ = ["box_corners", "Detection", "detections_to_openlabel", "boxes_to_detections", "points_in_box",
-           "yaw_quaternion", "DEFAULT_SENSOR_ID"]
+           "yaw_quaternion", "DEFAULT_SENSOR_ID", "reset_track_uuids"]
 
 DEFAULT_SENSOR_ID = "s110_lidar_ouster_south"   # inference_to_openlabel_coop.py:491
 _next_detection_id = [0]
+_track_uuids = {}   # track id -> uuid of this run (boxes_to_detections with track_ids and no uuid_for_track)
+
+
+def reset_track_uuids():
+    """forget the uuids given to track ids so far (a new sequence)"""
+    _track_uuids.clear()
 
 
 def box_corners(yaw: float, width: float, length: float, position: np.ndarray) -> np.ndarray:
@@ -168,24 +174,47 @@ def points_in_box(points_xyz: np.ndarray, center, extent, yaw: float) -> int:
 
 
 def boxes_to_detections(bboxes, scores, labels, class_names, points_xyz=None, bbox_classes=None, bbox_score=None,
-                        sensor_id=DEFAULT_SENSOR_ID, uuid_fn=None) -> List[Detection]:
+                        sensor_id=DEFAULT_SENSOR_ID, uuid_fn=None, track_ids=None, histories=None,
+                        uuid_for_track=None) -> List[Detection]:
     """The per-frame loop of inference_to_openlabel_coop.py:452-494 on decoded
     boxes ``[n, >= 7]`` (x, y, z_bottom, dx, dy, dz, yaw, ...), scores [n] and
-    labels [n] (tensors or arrays).  ``uuid_fn``: uuid source (default uuid4)."""
+    labels [n] (tensors or arrays).  ``uuid_fn``: uuid source (default uuid4).
+
+    ``track_ids`` [n] (native_track.Tracker.step's ids of the rows, -1: no track): a box with track id k >= 0 gets
+    ``uuid_for_track(k)`` as its uuid and k as its ``id``, so an object keeps its key from frame to frame; the
+    default ``uuid_for_track`` calls ``uuid_fn`` once per id and remembers the answer for the run
+    (``reset_track_uuids`` forgets).  ``histories``: {track id: positions [m, 3], oldest first}
+    (``Tracker.tracks()``), the ``pos_history`` of such a box.  Without ``track_ids`` nothing changes."""
     to_np = lambda t: t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)  # noqa: E731
     b, s, lab = to_np(bboxes), to_np(scores), to_np(labels)
+    tid = None if track_ids is None else to_np(track_ids).reshape(-1)
+    if tid is not None and len(tid) != len(b):
+        raise ValueError(f"track_ids has {len(tid)} entries for {len(b)} boxes")
     if bbox_classes is not None:
         keep = np.isin(lab, bbox_classes)
-        b, s, lab = b[keep], s[keep], lab[keep]
+        b, s, lab, tid = b[keep], s[keep], lab[keep], None if tid is None else tid[keep]
     if bbox_score is not None:
         keep = s >= bbox_score
-        b, s, lab = b[keep], s[keep], lab[keep]
+        b, s, lab, tid = b[keep], s[keep], lab[keep], None if tid is None else tid[keep]
     uuid_fn = uuid_fn or (lambda: str(_uuid.uuid4()))
+    if uuid_for_track is None:
+        def uuid_for_track(k):
+            if k not in _track_uuids:
+                _track_uuids[k] = uuid_fn()
+            return _track_uuids[k]
     dets = []
     for i, box in enumerate(b):
         loc = np.asarray([[box[0]], [box[1]], [box[2] + 0.5 * box[5]]], dtype=float)
         npts = 0 if points_xyz is None else points_in_box(points_xyz, box[:3], box[3:6], float(box[6]))
-        dets.append(Detection(uuid=uuid_fn(), category=class_names[int(lab[i])], location=loc,
+        extra = {}
+        if tid is not None and int(tid[i]) >= 0:
+            k = int(tid[i])
+            extra = dict(uuid=uuid_for_track(k), id=k)
+            if histories is not None and k in histories:
+                extra["pos_history"] = [np.asarray(q, dtype=float) for q in histories[k]]
+        else:
+            extra = dict(uuid=uuid_fn())
+        dets.append(Detection(category=class_names[int(lab[i])], location=loc,
                               dimensions=(float(box[3]), float(box[4]), float(box[5])), yaw=-float(box[6]),
-                              num_lidar_points=npts, score=float(s[i]), sensor_id=sensor_id))
+                              num_lidar_points=npts, score=float(s[i]), sensor_id=sensor_id, **extra))
     return dets

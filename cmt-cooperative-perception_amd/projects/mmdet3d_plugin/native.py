@@ -364,6 +364,27 @@ class GtdbCollideArgs(ctypes.Structure):
                 ("boxes", _vp), ("group", _vp), ("keep", _vp), ("count", _vp)]
 
 
+TRACK_MAX_TRACKS, TRACK_MAX_DETS, TRACK_MAX_HISTORY, TRACK_MAX_CLASSES = 512, 1024, 32, 32   # cmt_hip.h CMT_TRACK_MAX_*
+TRACK_BIG = 1.0e6                                                                        # cmt_hip.h CMT_TRACK_BIG
+
+
+class TrackPredictArgs(ctypes.Structure):
+    _fields_ = [("T", _int), ("D", _int), ("ld", _int), ("ncls", _int), ("has_pose", _int), ("reserved", _int),
+                ("dt", _flt), ("q_pos", _flt), ("q_vel", _flt), ("score_thr", _flt),
+                ("pose", _flt * 12), ("pose_yaw", _flt), ("reserved_f", _flt),
+                ("trk_f", _vp), ("trk_i", _vp), ("det", _vp), ("scores", _vp), ("labels", _vp), ("count", _vp),
+                ("gate2", _vp), ("det_w", _vp), ("det_ok", _vp), ("live", _vp), ("cost", _vp), ("lsap_desc", _vp)]
+
+
+class TrackUpdateArgs(ctypes.Structure):
+    _fields_ = [("T", _int), ("D", _int), ("H", _int), ("use_velocity", _int), ("max_age", _int), ("reserved", _int),
+                ("r_pos", _flt), ("r_vel", _flt), ("p0_pos", _flt), ("p0_vel", _flt), ("birth_thr", _flt),
+                ("reserved_f", _flt),
+                ("trk_f", _vp), ("trk_i", _vp), ("hist", _vp), ("counters", _vp), ("live", _vp), ("lsap_desc", _vp),
+                ("cost", _vp), ("match_g", _vp), ("match_q", _vp), ("det_w", _vp), ("scores", _vp), ("labels", _vp),
+                ("det_ok", _vp), ("det_track", _vp), ("det_slot", _vp)]
+
+
 STRUCTS = {"gemm": GemmArgs, "attn": AttnArgs, "ln": LnArgs, "chain": ChainArgs, "gemm_ex": GemmExArgs,
            "attn_train": AttnTrainArgs, "ln_train": LnTrainArgs, "bn": BnArgs, "det_loss": DetLossArgs,
            "match_cost": MatchCostArgs, "adamw": AdamwArgs, "mlp2": Mlp2Args, "mlp2_affine": Mlp2AffineArgs, "lsap": LsapArgs,
@@ -375,7 +396,8 @@ STRUCTS = {"gemm": GemmArgs, "attn": AttnArgs, "ln": LnArgs, "chain": ChainArgs,
            "img_resize": ImgResizeArgs, "img_augment": ImgAugmentArgs, "grid_mask": GridMaskArgs,
            "img_paste": ImgPasteArgs, "pts_prepare": PtsPrepareArgs,
            "points_in_boxes": PointsInBoxesArgs, "pts_augment": PtsAugmentArgs, "boxes_augment": BoxesAugmentArgs,
-           "gtdb_extract": GtdbExtractArgs, "gtdb_gather": GtdbGatherArgs, "gtdb_collide": GtdbCollideArgs}
+           "gtdb_extract": GtdbExtractArgs, "gtdb_gather": GtdbGatherArgs, "gtdb_collide": GtdbCollideArgs,
+           "track_predict": TrackPredictArgs, "track_update": TrackUpdateArgs}
 
 _LIB = None
 
@@ -529,6 +551,10 @@ def _load():
         "cmt_gtdb_extract": ([P(GtdbExtractArgs), _vp], _int),
         "cmt_gtdb_gather": ([P(GtdbGatherArgs), _vp], _int),
         "cmt_gtdb_collide": ([P(GtdbCollideArgs), _vp], _int),
+        "cmt_track_predict_args_size": ([], _i64),
+        "cmt_track_update_args_size": ([], _i64),
+        "cmt_track_predict": ([P(TrackPredictArgs), _vp], _int),
+        "cmt_track_update": ([P(TrackUpdateArgs), _vp], _int),
         "cmt_adamw_step": ([P(AdamwArgs), _vp], _int),
     }
     for name, (args, res) in sig.items():

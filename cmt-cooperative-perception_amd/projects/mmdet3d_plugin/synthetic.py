@@ -263,3 +263,63 @@ def synthetic_vehicle2infrastructure(seed=0):
     m = np.eye(4)
     m[:3, :3], m[:3, 3] = rot, trans
     return m
+
+
+def moving_scene(seed, n_objects=12, frames=30, dt=0.1, grid_cols=4, spacing=10.0, max_speed=1.0, noise=0.2,
+                 p_drop=0.1, max_drop_run=2, n_false=2, false_margin=5.0, num_classes=3, pad_to=None):
+    """A seeded scene of moving boxes for the tracker (native_track.Tracker), as numpy on the host.
+
+    ``n_objects`` objects start on a grid of ``grid_cols`` columns ``spacing`` metres apart and move with constant
+    velocities of at most ``max_speed`` m/s in random directions.  Per frame (``dt`` seconds apart): a detection
+    of every object whose position is within +-``noise`` metres (uniform, per axis) of the truth, dropped with
+    probability ``p_drop`` but never more than ``max_drop_run`` frames running; ``n_false`` false boxes at least
+    ``false_margin`` metres from every object; the rows shuffled.  Scores of the objects' boxes lie in
+    [0.5, 0.9], of the false ones in [0.35, 0.5].
+    -> a list of dicts: ``boxes`` fp32 [n, 9] (x y z dx dy dz yaw vx vy), ``scores`` fp32 [n], ``labels`` int32 [n],
+    ``object`` int32 [n] (the object of a row, -1 for a false box), ``timestamp`` (seconds, float).  With
+    ``pad_to`` every array has ``pad_to`` rows (zeros beyond ``count``, ``object`` -1) and ``count`` is n."""
+    rng = np.random.RandomState(seed)
+    idx = np.arange(n_objects)
+    pos0 = np.stack([(idx % grid_cols) * spacing, (idx // grid_cols) * spacing, np.zeros(n_objects)], 1)
+    ang, speed = rng.uniform(-math.pi, math.pi, n_objects), rng.uniform(0.0, max_speed, n_objects)
+    vel = np.stack([speed * np.cos(ang), speed * np.sin(ang)], 1)
+    size = rng.uniform([3.5, 1.6, 1.4], [5.0, 2.1, 1.9], (n_objects, 3))
+    label = (idx % num_classes).astype(np.int32)
+    lo, hi = pos0[:, :2].min(0) - 3 * false_margin, pos0[:, :2].max(0) + 3 * false_margin
+    run = np.zeros(n_objects, np.int64)
+    out = []
+    for t in range(frames):
+        truth = pos0.copy()
+        truth[:, :2] += vel * (t * dt)
+        drop = rng.uniform(size=n_objects) < p_drop
+        drop &= run < max_drop_run
+        run = np.where(drop, run + 1, 0)
+        keep = np.nonzero(~drop)[0]
+        b = np.zeros((len(keep) + n_false, 9))
+        b[:len(keep), :3] = truth[keep]
+        b[:len(keep), :2] += rng.uniform(-noise, noise, (len(keep), 2))
+        b[:len(keep), 3:6] = size[keep]
+        b[:len(keep), 6] = np.arctan2(vel[keep, 1], vel[keep, 0])
+        b[:len(keep), 7:9] = vel[keep]
+        s = np.concatenate([rng.uniform(0.5, 0.9, len(keep)), rng.uniform(0.35, 0.5, n_false)])
+        lab = np.concatenate([label[keep], rng.randint(0, num_classes, n_false).astype(np.int32)])
+        obj = np.concatenate([keep, np.full(n_false, -1)]).astype(np.int32)
+        for k in range(n_false):
+            for _ in range(1000):   # bounded rejection sampling; the area is mostly free
+                c = rng.uniform(lo, hi)
+                if np.hypot(*(truth[:, :2] - c).T).min() >= false_margin:
+                    break
+            b[len(keep) + k] = [c[0], c[1], 0.0, 4.0, 1.8, 1.6, rng.uniform(-math.pi, math.pi), 0.0, 0.0]
+        order = rng.permutation(len(b))
+        b, s, lab, obj = b[order].astype(np.float32), s[order].astype(np.float32), lab[order], obj[order]
+        n = len(b)
+        if pad_to is not None:
+            if pad_to < n:
+                raise ValueError(f"pad_to {pad_to} below the frame's {n} rows")
+            pad = pad_to - n
+            b = np.concatenate([b, np.zeros((pad, 9), np.float32)])
+            s = np.concatenate([s, np.zeros(pad, np.float32)])
+            lab = np.concatenate([lab, np.zeros(pad, np.int32)])
+            obj = np.concatenate([obj, np.full(pad, -1, np.int32)])
+        out.append(dict(boxes=b, scores=s, labels=lab.astype(np.int32), object=obj, count=n, timestamp=t * dt))
+    return out

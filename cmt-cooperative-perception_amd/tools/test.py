@@ -49,6 +49,13 @@ buffer (kept rows, then NaN) as it is; the vehicle cameras' ``lidar2img`` follow
 the evaluator as ``gt_num_pts``: ground truth without a point is dropped, as the reference's dataset does.  The nds
 line then also carries ``gt_without_points``.  Not with ``--launcher pytorch`` (rank 0 holds no clouds).
 
+``--track`` (with or without ``--detector``) runs every frame's boxes, in frame order, through one
+``native_track.Tracker`` over the config's class names with its default settings, the frames 0.1 s apart: the JSON
+frames gain ``track_ids`` (one id per box, -1 for a box that belongs to no track), and ``--format-only`` keys an
+object by its track's uuid from frame to frame and writes the track's positions as ``track_history``.  The synthetic
+frames are independent draws, so the ids say nothing about a scene; the path is the one a sequence would take.  Not
+with ``--launcher pytorch`` (the frames are sharded over ranks).
+
 Config 1 of BASELINE.json: ``python cmt-cooperative-perception_amd/tools/test.py
 cmt_lidar_nus --synthetic --num-query 32 --num-layers 1 --points 1000 --eval bbox``.
 The head runs on a HIP device only -- there is no CPU path; without a GPU the
@@ -108,6 +115,9 @@ def parse_args(argv=None):
                         "default: the process setting (CMT_IMG_PRECISION, else ref)")
     p.add_argument("--bbox-classes", nargs="+", type=int, default=None, help="keep these labels (OpenLABEL)")
     p.add_argument("--bbox-score", type=float, default=None, help="minimum score (OpenLABEL)")
+    p.add_argument("--track", action="store_true",
+                   help="run every frame's boxes through one native_track.Tracker (frames 0.1 s apart): the JSON frames "
+                        "gain track_ids, --format-only writes stable object keys and track_history")
     p.add_argument("--seed", type=int, default=0, help="random seed")
     p.add_argument("--cfg-options", nargs="+", default=None, metavar="KEY=VALUE",
                    help="override head config entries (dotted keys into pts_bbox_head, Python literals)")
@@ -311,6 +321,29 @@ def gt_point_counts(gt_boxes, points):
     return total
 
 
+TRACK_FRAME_SECONDS = 0.1   # --track: the synthetic frames are this far apart
+
+
+def track_frame(tracker, frame, boxes, scores, labels, device, want_history):
+    """One frame's boxes ([n, 9], scores [n], labels [n], on either side) through the tracker -> dict(track_ids [n]
+    as a list, and with ``want_history`` track_history {id: positions, oldest first})."""
+    import torch
+    n, D = int(scores.shape[0]), tracker.max_dets
+    if n > D:
+        raise SystemExit(f"--track: a frame has {n} boxes, the tracker takes {D}")
+    b = torch.zeros((D, 9), dtype=torch.float32, device=device)
+    s = torch.zeros(D, dtype=torch.float32, device=device)
+    lab = torch.zeros(D, dtype=torch.int32, device=device)
+    b[:n], s[:n], lab[:n] = boxes.float().to(device)[:, :9], scores.float().to(device), labels.to(device).to(torch.int32)
+    count = torch.full((1,), n, dtype=torch.int32, device=device)
+    ids = tracker.step(b, s, lab, count, timestamp=frame * TRACK_FRAME_SECONDS)[:n].cpu().tolist()
+    out = dict(track_ids=ids)
+    if want_history:
+        t = tracker.tracks(confirmed=False)
+        out["track_history"] = {int(k): h.tolist() for k, h in zip(t["ids"], t["history"])}
+    return out
+
+
 def eval_config(class_names):
     """TUMTraf constants for TUMTraf class names, the nuScenes detection constants otherwise"""
     from projects.mmdet3d_plugin.core import evaluation as E
@@ -389,6 +422,13 @@ def _run(args, name, device, rank, world, distributed):
         if rank == 0:
             evaluator = DetectionEvaluator(eval_config(class_names), max(args.frames, 1), device)
 
+    tracker = None
+    if args.track:
+        if distributed:
+            raise SystemExit("--track follows the frames in order: run it without a launcher")
+        from projects.mmdet3d_plugin import native_track as NT
+        tracker = NT.Tracker(class_names, device, max_dets=NT.MAX_DETS)
+
     empty_gt = []   # per frame, a device count of the ground truth without points (--count-gt-points)
 
     def feed(frame, boxes, scores, labels, points=None):
@@ -422,7 +462,10 @@ def _run(args, name, device, rank, world, distributed):
                 boxes, scores, labels = run_frame(head, name, feats, metas)
             if want_nds and not distributed:   # the boxes as tensors: no lists, no JSON
                 feed(f, boxes.float(), scores.float(), labels, points if args.count_gt_points else None)
-            results.append(dict(frame=f, voxels=vox_stats,
+            track = {}
+            if tracker is not None:
+                track = track_frame(tracker, f, boxes, scores, labels, device, args.format_only)
+            results.append(dict(frame=f, voxels=vox_stats, **track,
                                 boxes_3d=boxes.float().cpu().tolist(), scores_3d=scores.float().cpu().tolist(),
                                 labels_3d=labels.cpu().tolist(),
                                 points_xyz=torch.cat([p[:, :3][torch.isfinite(p[:, :3]).all(1)] for p in points]).cpu().tolist()
@@ -440,16 +483,19 @@ def _run(args, name, device, rank, world, distributed):
     if args.out:
         with open(args.out, "w") as fh:
             json.dump(dict(config=name, class_names=class_names,
-                           frames=[{k: v for k, v in r.items() if k != "points_xyz"} for r in results]), fh)
+                           frames=[{k: v for k, v in r.items() if k not in ("points_xyz", "track_history")}
+                                   for r in results]), fh)
         print(f"writing results to {args.out}")
     if args.format_only:
         import numpy as np
-        from projects.mmdet3d_plugin.core.openlabel import boxes_to_detections, detections_to_openlabel
+        from projects.mmdet3d_plugin.core.openlabel import boxes_to_detections, detections_to_openlabel, reset_track_uuids
+        reset_track_uuids()   # a run's track ids start at 0: no uuid of an earlier run in this process
         for r in results:
             dets = boxes_to_detections(np.asarray(r["boxes_3d"]).reshape(-1, 9), np.asarray(r["scores_3d"]),
                                        np.asarray(r["labels_3d"]), class_names,
                                        points_xyz=np.asarray(r["points_xyz"]), bbox_classes=args.bbox_classes,
-                                       bbox_score=args.bbox_score)
+                                       bbox_score=args.bbox_score, track_ids=r.get("track_ids"),
+                                       histories=r.get("track_history"))
             detections_to_openlabel(dets, filename=f"frame_{r['frame']:06d}.json",
                                     output_folder_path=args.openlabel_dir, frame_id=r["frame"])
         print(f"wrote {len(results)} OpenLABEL file(s) to {args.openlabel_dir}")

@@ -45,6 +45,10 @@ mixup 0.5, GridMask on): ``native_imgaug.paste_images`` + ``augment_images`` aga
 device (per-rectangle ``F.interpolate`` and blend, ``F.interpolate`` of the frames, crop, normalise, pad, the mask built
 in numpy and uploaded as the reference does), in alternating windows of --iters samples.
 
+``--only track`` (``--track-out FILE``) times ``native_track.Tracker.step`` on a 100-object moving scene with 300
+detection rows against the same algorithm as numpy + scipy on the host (with the copy of the boxes it needs), in
+alternating windows.
+
 ``--only gtdb`` (``--gtdb-out FILE``) times the ground-truth database (native_gtdb.py) in alternating windows of --iters
 calls: ``GtDatabase.add_frame`` on one cloud of --points rows with 64 boxes against a boolean-mask chain per box and
 ``torch.cat``; and ``UnifiedDataBaseSampler.sample_all`` + ``augment_points`` on a database of 320 objects against the
@@ -54,8 +58,8 @@ same draws and collision test followed by torch ops per object and per paste box
 runs VoVNet on the one-pass fp16 kernels; everything else is unchanged.
 
     python dev/detector_probe.py [--img-precision ref|fp16] [--points 300000] [--repeats 20] [--warmup 3]
-                                 [--iters 20] [--seed 0] [--out FILE] [--only resize|points|eval|augment|img-augment|gtdb]
-                                 [--gtdb-out FILE] [--resize-out FILE] [--augment-out FILE] [--img-augment-out FILE]
+                                 [--iters 20] [--seed 0] [--out FILE] [--only resize|points|eval|augment|img-augment|gtdb|track]
+                                 [--gtdb-out FILE] [--track-out FILE] [--resize-out FILE] [--augment-out FILE] [--img-augment-out FILE]
                                  [--points-out FILE] [--sweep-points 27000] [--sweeps K] [--eval-out FILE]
                                  [--eval-frames 800]
 
@@ -106,9 +110,10 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--img-precision", choices=("ref", "fp16"), default="ref")
     ap.add_argument("--out", default=None)
-    ap.add_argument("--only", choices=("resize", "points", "eval", "augment", "img-augment", "gtdb"), default=None,
+    ap.add_argument("--only", choices=("resize", "points", "eval", "augment", "img-augment", "gtdb", "track"), default=None,
                     help="run this section alone")
     ap.add_argument("--gtdb-out", default=None, help="write the ground-truth database section to this file")
+    ap.add_argument("--track-out", default=None, help="write the tracker section to this file")
     ap.add_argument("--img-augment-out", default=None, help="write the cmt_img_augment section to this file")
     ap.add_argument("--augment-out", default=None, help="write the cmt_pts_augment section to this file")
     ap.add_argument("--eval-out", default=None, help="write the detection-evaluation section to this file")
@@ -285,6 +290,9 @@ def main():
         return
     if args.only == "gtdb":
         gtdb_section(args, dev, say, lines)
+        return
+    if args.only == "track":
+        track_section(args, dev, say, lines)
         return
     frames = frame("cmt_fusion_nus")
     frame("cmtcoop_fusion_tumtraf")
@@ -952,6 +960,159 @@ def resize_section(args, dev, say, lines):
     say(f"{'torch ops':>22} {fmt(tt)}   native / torch {tn[0] / tt[0]:.2f}")
     say(f"peak device memory {torch.cuda.max_memory_allocated() / 2 ** 20:.0f} MiB")
     for path, text in ((args.out, lines), (args.resize_out, lines[first:])):
+        if path:
+            os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+            with open(path, "w") as f:
+                f.write("\n".join(text) + "\n")
+
+
+
+
+class HostTracker:
+    """the algorithm of native_track.Tracker as numpy + scipy.optimize.linear_sum_assignment on the host, float64,
+    vectorised: what a pipeline without the device tracker would run after copying the boxes back"""
+
+    def __init__(self, ncls, T, gate, score_thr, birth_thr, max_age, q_pos, q_vel, r_pos, p0_pos, p0_vel):
+        import numpy as np
+        self.np, self.T = np, T
+        self.gate2 = np.full(ncls, gate * gate)
+        self.p = (score_thr, birth_thr, max_age, q_pos, q_vel, r_pos, p0_pos, p0_vel)
+        self.reset()
+
+    def reset(self):
+        np = self.np
+        self.f, self.ids, self.lab = np.zeros((self.T, 16)), np.full(self.T, -1), np.zeros(self.T, int)
+        self.misses, self.next_id = np.zeros(self.T, int), 0
+
+    def step(self, boxes, scores, labels, n, dt):
+        from scipy.optimize import linear_sum_assignment
+        np, f = self.np, self.f
+        score_thr, birth_thr, max_age, q_pos, q_vel, r_pos, p0_pos, p0_vel = self.p
+        boxes, scores, labels = boxes[:n].astype(np.float64), scores[:n], labels[:n]
+        ok = np.isfinite(boxes).all(1) & (labels >= 0) & (labels < len(self.gate2)) & (scores >= score_thr)
+        live = np.nonzero(self.ids >= 0)[0]
+        for p_, v_, pp in ((0, 7, 10), (1, 8, 13)):
+            f[live, p_] += dt * f[live, v_]
+            t1 = f[live, pp + 1] + dt * f[live, pp + 2]
+            f[live, pp] += dt * (f[live, pp + 1] + t1) + q_pos * dt
+            f[live, pp + 1] = t1
+            f[live, pp + 2] += q_vel * dt
+        out, matched_t, matched_d = np.full(n, -1), np.zeros(len(live), bool), np.zeros(n, bool)
+        if len(live) and n:
+            d2 = (f[live, 0, None] - boxes[None, :, 0]) ** 2 + (f[live, 1, None] - boxes[None, :, 1]) ** 2
+            gated = ok[None] & (labels[None] == self.lab[live, None]) & (d2 < self.gate2[np.clip(labels, 0, None)][None])
+            cost = np.where(gated, d2, 1.0e6)
+            r, c = linear_sum_assignment(cost)
+            good = cost[r, c] < 1.0e6
+            r, c = r[good], c[good]
+            s = live[r]
+            for p_, v_, pp in ((0, 7, 10), (1, 8, 13)):
+                K0, K1 = f[s, pp] / (f[s, pp] + r_pos), f[s, pp + 1] / (f[s, pp] + r_pos)
+                y = boxes[c, p_] - f[s, p_]
+                f[s, p_] += K0 * y
+                f[s, v_] += K1 * y
+                f[s, pp + 2] -= K1 * f[s, pp + 1]
+                f[s, pp + 1] -= K0 * f[s, pp + 1]
+                f[s, pp] -= K0 * f[s, pp]
+            f[s, 2:7], f[s, 9] = boxes[c, 2:7], scores[c]
+            self.misses[s] = 0
+            out[c], matched_t[r], matched_d[c] = self.ids[s], True, True
+        lost = live[~matched_t]
+        self.misses[lost] += 1
+        self.ids[lost[self.misses[lost] > max_age]] = -1
+        born = np.nonzero(ok & ~matched_d & (scores >= birth_thr))[0]
+        free = np.nonzero(self.ids < 0)[0][:len(born)]
+        born = born[:len(free)]
+        f[free, :7], f[free, 7:9], f[free, 9] = boxes[born, :7], 0.0, scores[born]
+        f[free, 10:16] = (p0_pos, 0, p0_vel, p0_pos, 0, p0_vel)
+        self.ids[free] = self.next_id + np.arange(len(born))
+        self.lab[free], self.misses[free] = labels[born], 0
+        out[born] = self.ids[free]
+        self.next_id += len(born)
+        return out
+
+
+def track_section(args, dev, say, lines):
+    """Tracker.step against the same algorithm on the host, on a 100-object scene with 300 detection rows"""
+    import numpy as np
+    from projects.mmdet3d_plugin import native_track as NT
+    from projects.mmdet3d_plugin import synthetic as S
+    first = len(lines)
+    D, OBJ, FR = 300, 100, 30
+    scene = S.moving_scene(args.seed, n_objects=OBJ, frames=FR, grid_cols=10, pad_to=D)
+    names = ["a", "b", "c"]
+    trk = NT.Tracker(names, dev, max_tracks=256, max_dets=D)
+    host = HostTracker(len(names), 256, 2.0, trk.score_thr, trk.birth_thr, trk.max_age, trk.q_pos, trk.q_vel, trk.r_pos,
+                       trk.p0_pos, trk.p0_vel)
+    frames = [(torch.from_numpy(f["boxes"]).to(dev), torch.from_numpy(f["scores"]).to(dev), torch.from_numpy(f["labels"]).to(dev),
+               torch.tensor([f["count"]], dtype=torch.int32, device=dev)) for f in scene]
+    say(f"--- {torch.cuda.get_device_name(0)}: tracker, {OBJ} moving objects, {D} detection rows a frame "
+        f"({scene[0]['count']} valid in frame 0), 256 track slots, position-only filter; (a) Tracker.step and (b) numpy + scipy "
+        f"on the host in alternating windows of {args.iters} frames (a window starts from a fresh tracker and walks the "
+        f"scene), median of {args.repeats} (min .. max) after {args.warmup} warm-up windows, device events (they span the "
+        "calls' host time and, for (b), the copies), ms per frame")
+
+    def native_window(n, keep=None):
+        trk.reset()
+        for t in range(n):
+            ids = trk.step(*frames[t % FR], dt=0.1)
+            if keep is not None:
+                keep.append(ids.clone())
+
+    def host_window(n, keep=None):
+        host.reset()
+        for t in range(n):
+            b, s_, lab, cnt = frames[t % FR]
+            ids = host.step(b.cpu().numpy(), s_.cpu().numpy(), lab.cpu().numpy(), int(cnt.item()), 0.0 if t == 0 else 0.1)
+            if keep is not None:
+                keep.append(ids)
+
+    ka, kb = [], []
+    native_window(FR, ka), host_window(FR, kb)
+    ka = torch.stack(ka).cpu().numpy()
+    differ = sum(int((a[:len(b)] != b).sum()) for a, b in zip(ka, kb))
+    pure = {}
+    for f, a in zip(scene, ka):
+        for o, k in zip(f["object"][:f["count"]], a):
+            if o >= 0:
+                pure.setdefault(int(o), set()).add(int(k))
+    for _ in range(args.warmup):
+        native_window(args.iters), host_window(args.iters)
+    torch.cuda.synchronize()
+    ta, tb = [], []
+    for _ in range(args.repeats):
+        ta.append(event_ms(lambda: native_window(args.iters)) / args.iters)
+        tb.append(event_ms(lambda: host_window(args.iters)) / args.iters)
+    ta, tb = med(ta), med(tb)
+    cnt = trk.state["counters"].cpu().numpy()
+    say(f"one walk of the {FR} frames: {sum(len(v) == 1 for v in pure.values())} of {len(pure)} objects keep one id on the "
+        f"device; {differ} of {sum(f['count'] for f in scene)} row ids differ between (a) float32 on the device and (b) "
+        f"float64 on the host; ids issued {int(cnt[1])} in the last window")
+    say(f"{'(a) Tracker.step':>34} {fmt(ta)}   5 launches (predict, cost, cmt_lsap's two, update) and a 4-byte memset, no host read")
+    say(f"{'(b) numpy + scipy on the host':>34} {fmt(tb)}   (a) / (b) {ta[0] / tb[0]:.3f}; 4 device-to-host copies (boxes, "
+        "scores, labels, count), vectorised numpy, scipy.optimize.linear_sum_assignment; its ids stay on the host")
+    # where (a)'s time goes: the host side of a step without waiting for the device, and each call between events
+    import ctypes
+    import time
+    from projects.mmdet3d_plugin import native as N
+    L, th = N.lib(), []
+    for _ in range(args.repeats):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        native_window(args.iters)
+        th.append((time.perf_counter() - t0) * 1e3 / args.iters)
+        torch.cuda.synchronize()
+    stage = {"cmt_track_predict": [], "cmt_lsap": [], "cmt_track_update": []}
+    trk.reset()
+    for t in range(FR):
+        trk.step(*frames[t], dt=0.1)                     # fills the argument structs for frame t; the state moves on
+        for name, a in (("cmt_track_predict", trk._predict), ("cmt_lsap", trk._lsap), ("cmt_track_update", trk._update)):
+            stage[name].append(event_ms(lambda: getattr(L, name)(ctypes.byref(a), N._stream())))
+    say(f"{'host side of (a)':>34} {fmt(med(th))}   perf_counter over a window without waiting for the device")
+    for name, ts in stage.items():
+        say(f"{name:>34} {fmt(med(ts))}   one call between two events, over the {FR} frames (launch overhead included)")
+    say(f"peak device memory {torch.cuda.max_memory_allocated() / 2 ** 20:.0f} MiB")
+    for path, text in ((args.out, lines), (args.track_out, lines[first:])):
         if path:
             os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
             with open(path, "w") as f:

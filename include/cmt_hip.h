@@ -1764,6 +1764,144 @@ int cmt_gtdb_extract(const cmt_gtdb_extract_args* args, void* stream);
 int cmt_gtdb_gather(const cmt_gtdb_gather_args* args, void* stream);
 int cmt_gtdb_collide(const cmt_gtdb_collide_args* args, void* stream);
 
+/* ---- multi-object tracker (track.hip; additive to ABI 25) ----------------------------------------------
+ * Links the boxes of one frame (cmt_box_decode's rows) to tracks with stable ids: a constant-velocity
+ * Kalman filter per axis in the ground plane, a gated squared-distance cost matrix, cmt_lsap between the two
+ * calls below, and the tracks' life cycle.  A frame is cmt_track_predict -> cmt_lsap (P = 1, max_nq = T,
+ * max_ngt = D, cost_elems = T * D, both match_q [D] and match_g [T]) -> cmt_track_update: five small launches and
+ * cmt_lsap's memset of its status word, no host read, no synchronisation; the host knows only T and D, the live and detection counts travel in
+ * lsap_desc in device memory.  THIS TEXT is the contract.  fl32 = one rounding to float32; every sum,
+ * difference, product and quotient below is an IEEE single operation rounded on its own (none is fused), in
+ * the order the parentheses give, a + b + c meaning (a + b) + c; "a += b" is a = fl32(a + b).
+ * The assignment minimises the SUM OF SQUARED ground-plane distances over the gated pairs, not the sum of
+ * distances: a stated choice that keeps the contract free of a square root.
+ * Caller-owned buffers, stream-ordered, no allocation, no workgroup waits for another: graph-capturable.
+ * Every output element has one writer and there are no atomics: results are bitwise repeatable.  Buffers must
+ * not overlap.  Limits (CMT_ENOTSUP beyond): T <= CMT_TRACK_MAX_TRACKS, D <= CMT_TRACK_MAX_DETS, H <=
+ * CMT_TRACK_MAX_HISTORY, ncls <= CMT_TRACK_MAX_CLASSES.
+ *
+ * State, on the device, a slot is stable for the life of a track:
+ *   trk_f fp32 [T][16]: x y z dx dy dz yaw vx vy score Px_pp Px_pv Px_vv Py_pp Py_pv Py_vv
+ *   trk_i int32 [T][8]: id (-1: a free slot), label, hits, misses, age, det (the row matched or born from
+ *                        in the last update, else -1), hist_n (positions appended since birth), reserved 0
+ *   hist  fp32 [T][H][3]: a ring, a position goes to hist[s][hist_n % H]
+ *   counters int32 [4]:  n_alive, next_id, births dropped for lack of a slot (cumulative), frames
+ *   A fresh state has every id -1 and everything else zero.
+ *
+ * cmt_track_predict.  det fp32 [D][ld], ld >= 9, columns x y z dx dy dz yaw vx vy; scores fp32 [D]; labels
+ *   int32 [D]; count null (n_det = D) or a device int32 clamped to [0, D]; gate2 fp32 [ncls] on the device,
+ *   the squared gate per class (the caller keeps every entry below 1e5: the C side cannot read it); pose: with
+ *   has_pose != 0 twelve floats, row-major [R|t] (Rab = pose[4a + b], ta = pose[4a + 3]), and pose_yaw.  The
+ *   kernels call no trigonometric function.  In order:
+ *   1. n_det from count.
+ *   2. det_w fp32 [D][9], all D rows: the nine columns copied bit for bit without a pose; with one
+ *        x' = ((R00 * x + R01 * y) + R02 * z) + t0, y' and z' likewise with rows 1 and 2,
+ *        vx' = R00 * vx + R01 * vy,  vy' = R10 * vx + R11 * vy,  sizes unchanged,
+ *        yaw' = yaw + pose_yaw, then yaw' -= 6.2831855f if yaw' >= 3.1415927f, else yaw' += 6.2831855f if
+ *        yaw' < -3.1415927f (one conditional step).
+ *   3. det_ok int32 [D]: 1 iff j < n_det, the nine values of det_w[j] are finite, 0 <= labels[j] < ncls and
+ *      scores[j] >= score_thr (a NaN score gives 0); else 0.
+ *   4. every slot with id >= 0, per axis a in {x, y} with (p, v, Ppp, Ppv, Pvv) the axis' five values:
+ *        p += dt * v;  t1 = Ppv + dt * Pvv;  Ppp = (Ppp + dt * (Ppv + t1)) + q_pos * dt;  Ppv = t1;
+ *        Pvv = Pvv + q_vel * dt;  and age += 1.  Nothing else of the state is written.
+ *   5. live int32 [T]: live[r] = the r-th slot with id >= 0 in ascending slot order, r < n_live.
+ *   6. cost fp32, row stride D, for r < n_live and j < n_det only, s = live[r]:
+ *        d2 = (x_s - x_j) * (x_s - x_j) + (y_s - y_j) * (y_s - y_j)   (predicted state, det_w)
+ *        cost = d2 iff det_ok[j], labels[j] == label_s and d2 < gate2[labels[j]]; else CMT_TRACK_BIG.
+ *      A non-finite d2 fails the comparison: every cost is finite and cmt_lsap's status is 0.
+ *   7. lsap_desc int64 [4] = (0, n_live, n_det, D).
+ *   Two launches: one workgroup for 1..5 and 7 (the live list is a ballot / mbcnt scan per 64 slots and an LDS
+ *   table over them), then the cost matrix over tiles of 16 rows x 256 columns.
+ *   CMT_EINVAL before any device work: a null struct; T, D or ncls < 1; ld < 9; dt, q_pos or q_vel negative or
+ *   not finite; score_thr NaN; has_pose with a non-finite pose or pose_yaw; a null or misaligned (4 bytes,
+ *   lsap_desc 8) trk_f, trk_i, det, scores, labels, gate2, det_w, det_ok, live, cost or lsap_desc; a
+ *   misaligned count.
+ *
+ * cmt_track_update.  live, lsap_desc, cost, det_w, det_ok as cmt_track_predict wrote them, match_g int32 [T]
+ *   and match_q int32 [D] as cmt_lsap wrote them, the scores and labels of cmt_track_predict.  n_live and
+ *   n_det are read from lsap_desc and clamped to [0, T] and [0, D].  In order:
+ *   1. Row r < n_live with s = live[r] is matched to j iff s is the r-th slot with id >= 0 (the kernel scans
+ *      the ids again), j = match_g[r] is in [0, n_det), match_q[j] == r, det_ok[j] and cost[r][j] < CMT_TRACK_BIG.
+ *      Entries outside their ranges match nothing and move nothing: a corrupt table cannot write out of bounds,
+ *      two rows cannot claim one detection nor one slot.
+ *   2. A matched slot, per axis, measurement zp = det_w[j] x / y and zv = det_w[j] vx / vy, every right-hand
+ *      side reading the predicted values:
+ *      use_velocity != 0:
+ *        Spp = Ppp + r_pos, Spv = Ppv, Svv = Pvv + r_vel, det = Spp * Svv - Spv * Spv,
+ *        K00 = (Ppp * Svv - Ppv * Spv) / det,  K01 = (Ppv * Spp - Ppp * Spv) / det,
+ *        K10 = (Ppv * Svv - Pvv * Spv) / det,  K11 = (Pvv * Spp - Ppv * Spv) / det,
+ *        yp = zp - p, yv = zv - v,  p += K00 * yp + K01 * yv,  v += K10 * yp + K11 * yv,
+ *        Ppp' = Ppp - (K00 * Ppp + K01 * Ppv), Ppv' = Ppv - (K00 * Ppv + K01 * Pvv),
+ *        Pvv' = Pvv - (K10 * Ppv + K11 * Pvv)
+ *      use_velocity == 0 (position only):
+ *        S = Ppp + r_pos, K0 = Ppp / S, K1 = Ppv / S, y = zp - p,  p += K0 * y,  v += K1 * y,
+ *        Ppp' = Ppp - K0 * Ppp, Ppv' = Ppv - K0 * Ppv, Pvv' = Pvv - K1 * Ppv
+ *      then z, dx, dy, dz, yaw from det_w[j] and score from scores[j] bit for bit, hits += 1, misses = 0,
+ *      det = j, hist[s][hist_n % H] = the updated (x, y, z), hist_n += 1.
+ *   3. Every other slot with id >= 0: misses += 1, det = -1; with misses > max_age the slot is freed (id = -1,
+ *      nothing else of it changes).
+ *   4. Births: the k-th j in ascending order with j < n_det, det_ok[j], not matched and scores[j] >= birth_thr
+ *      takes the k-th free slot in ascending slot order, slots freed in step 3 included: id = next_id + k,
+ *      label = labels[j]; x y z dx dy dz yaw from det_w[j], (vx, vy) from det_w[j] with use_velocity, else 0;
+ *      score; P = (p0_pos, 0, p0_vel) per axis; hits 1, misses 0, age 0, det j, hist[s][0] = (x, y, z),
+ *      hist_n 1, reserved 0.  Births beyond the free slots are dropped, counted, and use no id.
+ *   5. counters: n_alive = the slots with id >= 0 now, next_id += the births placed, counters[2] += the
+ *      births dropped, frames += 1.
+ *   6. det_track int32 [D] and det_slot int32 [D], all D entries: the id and slot matched or born for j, else -1.
+ *   One launch, one workgroup: the free-slot list and the birth ranks are ballot / mbcnt scans per 64 entries
+ *   with an LDS table over them.
+ *   CMT_EINVAL before any device work: a null struct; T, D or H < 1; max_age < 0; r_pos or r_vel not finite or
+ *   <= 0; p0_pos or p0_vel not finite or negative; birth_thr NaN; a null or misaligned (4 bytes, lsap_desc 8)
+ *   pointer. */
+#define CMT_TRACK_MAX_TRACKS 512
+#define CMT_TRACK_MAX_DETS 1024
+#define CMT_TRACK_MAX_HISTORY 32
+#define CMT_TRACK_MAX_CLASSES 32
+#define CMT_TRACK_BIG 1.0e6f
+typedef struct cmt_track_predict_args {
+    int T, D, ld, ncls;
+    int has_pose, reserved;
+    float dt, q_pos, q_vel, score_thr;
+    float pose[12];
+    float pose_yaw, reserved_f;
+    void* trk_f;
+    int* trk_i;
+    const void* det;
+    const void* scores;
+    const int* labels;
+    const int* count;
+    const void* gate2;
+    void* det_w;
+    int* det_ok;
+    int* live;
+    void* cost;
+    int64_t* lsap_desc;
+} cmt_track_predict_args;
+typedef struct cmt_track_update_args {
+    int T, D, H, use_velocity;
+    int max_age, reserved;
+    float r_pos, r_vel, p0_pos, p0_vel, birth_thr, reserved_f;
+    void* trk_f;
+    int* trk_i;
+    void* hist;
+    int* counters;
+    const int* live;
+    const int64_t* lsap_desc;
+    const void* cost;
+    const int* match_g;
+    const int* match_q;
+    const void* det_w;
+    const void* scores;
+    const int* labels;
+    const int* det_ok;
+    int* det_track;
+    int* det_slot;
+} cmt_track_update_args;
+int64_t cmt_track_predict_args_size(void);
+int64_t cmt_track_update_args_size(void);
+int cmt_track_predict(const cmt_track_predict_args* args, void* stream);
+int cmt_track_update(const cmt_track_update_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
