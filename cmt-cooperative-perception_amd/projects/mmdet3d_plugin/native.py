@@ -385,6 +385,29 @@ class TrackUpdateArgs(ctypes.Structure):
                 ("det_ok", _vp), ("det_track", _vp), ("det_slot", _vp)]
 
 
+NMS_MAX, CONCAT_MAX = 2048, 8   # cmt_hip.h CMT_NMS_MAX, CMT_CONCAT_MAX
+
+
+class BoxIouArgs(ctypes.Structure):
+    _fields_ = [("N", _int), ("M", _int), ("lda", _int), ("ldb", _int), ("aligned", _int), ("reserved", _int),
+                ("z_origin", _flt), ("reserved_f", _flt), ("ldo", _i64),
+                ("a", _vp), ("b", _vp), ("n_a", _vp), ("n_b", _vp), ("bev", _vp), ("iou3d", _vp)]
+
+
+class BoxNmsArgs(ctypes.Structure):
+    _fields_ = [("N", _int), ("ld", _int), ("use_3d", _int), ("keep_dtype", _int),
+                ("iou_thr", _flt), ("score_thr", _flt), ("z_origin", _flt), ("reserved_f", _flt),
+                ("boxes", _vp), ("scores", _vp), ("labels", _vp), ("count", _vp), ("keep_idx", _vp), ("keep", _vp),
+                ("keep_count", _vp), ("workspace", _vp), ("workspace_bytes", _i64)]
+
+
+class BoxConcatArgs(ctypes.Structure):
+    _fields_ = [("K", _int), ("cols", _int), ("ld_out", _int), ("reserved", _int),
+                ("n", _int * 8), ("ld", _int * 8), ("has_transform", _int * 8), ("transform", (_flt * 12) * 8),
+                ("boxes", _vp * 8), ("scores", _vp * 8), ("labels", _vp * 8), ("count", _vp * 8),
+                ("out_boxes", _vp), ("out_scores", _vp), ("out_labels", _vp), ("out_source", _vp), ("out_count", _vp)]
+
+
 STRUCTS = {"gemm": GemmArgs, "attn": AttnArgs, "ln": LnArgs, "chain": ChainArgs, "gemm_ex": GemmExArgs,
            "attn_train": AttnTrainArgs, "ln_train": LnTrainArgs, "bn": BnArgs, "det_loss": DetLossArgs,
            "match_cost": MatchCostArgs, "adamw": AdamwArgs, "mlp2": Mlp2Args, "mlp2_affine": Mlp2AffineArgs, "lsap": LsapArgs,
@@ -397,7 +420,8 @@ STRUCTS = {"gemm": GemmArgs, "attn": AttnArgs, "ln": LnArgs, "chain": ChainArgs,
            "img_paste": ImgPasteArgs, "pts_prepare": PtsPrepareArgs,
            "points_in_boxes": PointsInBoxesArgs, "pts_augment": PtsAugmentArgs, "boxes_augment": BoxesAugmentArgs,
            "gtdb_extract": GtdbExtractArgs, "gtdb_gather": GtdbGatherArgs, "gtdb_collide": GtdbCollideArgs,
-           "track_predict": TrackPredictArgs, "track_update": TrackUpdateArgs}
+           "track_predict": TrackPredictArgs, "track_update": TrackUpdateArgs,
+           "box_iou": BoxIouArgs, "box_nms": BoxNmsArgs, "box_concat": BoxConcatArgs}
 
 _LIB = None
 
@@ -555,6 +579,13 @@ def _load():
         "cmt_track_update_args_size": ([], _i64),
         "cmt_track_predict": ([P(TrackPredictArgs), _vp], _int),
         "cmt_track_update": ([P(TrackUpdateArgs), _vp], _int),
+        "cmt_box_iou_args_size": ([], _i64),
+        "cmt_box_nms_args_size": ([], _i64),
+        "cmt_box_concat_args_size": ([], _i64),
+        "cmt_box_nms_workspace_bytes": ([_int], _i64),
+        "cmt_box_iou": ([P(BoxIouArgs), _vp], _int),
+        "cmt_box_nms": ([P(BoxNmsArgs), _vp], _int),
+        "cmt_box_concat": ([P(BoxConcatArgs), _vp], _int),
         "cmt_adamw_step": ([P(AdamwArgs), _vp], _int),
     }
     for name, (args, res) in sig.items():

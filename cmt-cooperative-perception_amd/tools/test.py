@@ -49,6 +49,11 @@ buffer (kept rows, then NaN) as it is; the vehicle cameras' ``lidar2img`` follow
 the evaluator as ``gt_num_pts``: ground truth without a point is dropped, as the reference's dataset does.  The nds
 line then also carries ``gt_without_points``.  Not with ``--launcher pytorch`` (rank 0 holds no clouds).
 
+``--nms rotate [--nms-thr X]`` (opt-in; the reference configs all say ``nms_type=None``) runs class-aware rotated
+NMS on every frame's boxes on the device (``native_iou.nms_rotated``, BEV IoU) before anything else sees them: the
+kept boxes, best first, are what ``--out``, ``--eval``, ``--track`` and ``--format-only`` get, and the JSON frames
+gain ``nms_kept``.  Without it nothing changes.
+
 ``--track`` (with or without ``--detector``) runs every frame's boxes, in frame order, through one
 ``native_track.Tracker`` over the config's class names with its default settings, the frames 0.1 s apart: the JSON
 frames gain ``track_ids`` (one id per box, -1 for a box that belongs to no track), and ``--format-only`` keys an
@@ -118,6 +123,11 @@ def parse_args(argv=None):
     p.add_argument("--track", action="store_true",
                    help="run every frame's boxes through one native_track.Tracker (frames 0.1 s apart): the JSON frames "
                         "gain track_ids, --format-only writes stable object keys and track_history")
+    p.add_argument("--nms", choices=["rotate"], default=None,
+                   help="class-aware rotated NMS (BEV IoU, on the device) of every frame's boxes before they are "
+                        "written, evaluated, tracked or formatted; the JSON frames gain nms_kept (default: off)")
+    p.add_argument("--nms-thr", type=float, default=None,
+                   help="IoU threshold of --nms (default: the config's test_cfg nms_thr, else 0.2)")
     p.add_argument("--seed", type=int, default=0, help="random seed")
     p.add_argument("--cfg-options", nargs="+", default=None, metavar="KEY=VALUE",
                    help="override head config entries (dotted keys into pts_bbox_head, Python literals)")
@@ -344,6 +354,22 @@ def track_frame(tracker, frame, boxes, scores, labels, device, want_history):
     return out
 
 
+def nms_frame(boxes, scores, labels, iou_thr, device):
+    """--nms rotate: class-aware rotated NMS of one frame's boxes ([n, >= 7] with the bottom z of get_bboxes, on
+    either side) on the device -> (boxes, scores, labels of the kept rows, best first, on the device; their number)"""
+    import torch
+    from projects.mmdet3d_plugin import native_iou as NI
+    n = int(scores.shape[0])
+    if n > NI.NMS_MAX:
+        raise SystemExit(f"--nms: a frame has {n} boxes, rotated NMS takes {NI.NMS_MAX}")
+    boxes, scores, labels = boxes.to(device), scores.to(device), labels.to(device)
+    keep_idx, count = NI.nms_rotated(boxes.float().contiguous(), scores.float().contiguous(), iou_thr,
+                                     labels=labels.to(torch.int32).contiguous(), z_origin=0.0)
+    kept = int(count.item())
+    sel = keep_idx[:kept].long()
+    return boxes[sel], scores[sel], labels[sel], kept
+
+
 def eval_config(class_names):
     """TUMTraf constants for TUMTraf class names, the nuScenes detection constants otherwise"""
     from projects.mmdet3d_plugin.core import evaluation as E
@@ -429,6 +455,10 @@ def _run(args, name, device, rank, world, distributed):
         from projects.mmdet3d_plugin import native_track as NT
         tracker = NT.Tracker(class_names, device, max_dets=NT.MAX_DETS)
 
+    nms_thr = None
+    if args.nms:
+        nms_thr = args.nms_thr if args.nms_thr is not None else float((cfg.get("test_cfg") or {}).get("nms_thr", 0.2))
+
     empty_gt = []   # per frame, a device count of the ground truth without points (--count-gt-points)
 
     def feed(frame, boxes, scores, labels, points=None):
@@ -460,12 +490,15 @@ def _run(args, name, device, rank, world, distributed):
                 boxes, scores, labels = res["boxes_3d"], res["scores_3d"], res["labels_3d"]
             else:
                 boxes, scores, labels = run_frame(head, name, feats, metas)
+            nms = {}
+            if args.nms:
+                boxes, scores, labels, nms["nms_kept"] = nms_frame(boxes, scores, labels, nms_thr, device)
             if want_nds and not distributed:   # the boxes as tensors: no lists, no JSON
                 feed(f, boxes.float(), scores.float(), labels, points if args.count_gt_points else None)
             track = {}
             if tracker is not None:
                 track = track_frame(tracker, f, boxes, scores, labels, device, args.format_only)
-            results.append(dict(frame=f, voxels=vox_stats, **track,
+            results.append(dict(frame=f, voxels=vox_stats, **track, **nms,
                                 boxes_3d=boxes.float().cpu().tolist(), scores_3d=scores.float().cpu().tolist(),
                                 labels_3d=labels.cpu().tolist(),
                                 points_xyz=torch.cat([p[:, :3][torch.isfinite(p[:, :3]).all(1)] for p in points]).cpu().tolist()

@@ -49,6 +49,10 @@ in numpy and uploaded as the reference does), in alternating windows of --iters 
 detection rows against the same algorithm as numpy + scipy on the host (with the copy of the boxes it needs), in
 alternating windows.
 
+``--only iou`` (``--iou-out FILE``) times ``native_iou.box_iou`` at 300 x 300 and 2048 x 2048 boxes and
+``fuse_detections`` of two and of four agents with 300 rows each against the same algorithm as vectorised numpy on the
+host (with the copies it needs), in alternating windows.
+
 ``--only gtdb`` (``--gtdb-out FILE``) times the ground-truth database (native_gtdb.py) in alternating windows of --iters
 calls: ``GtDatabase.add_frame`` on one cloud of --points rows with 64 boxes against a boolean-mask chain per box and
 ``torch.cat``; and ``UnifiedDataBaseSampler.sample_all`` + ``augment_points`` on a database of 320 objects against the
@@ -58,8 +62,8 @@ same draws and collision test followed by torch ops per object and per paste box
 runs VoVNet on the one-pass fp16 kernels; everything else is unchanged.
 
     python dev/detector_probe.py [--img-precision ref|fp16] [--points 300000] [--repeats 20] [--warmup 3]
-                                 [--iters 20] [--seed 0] [--out FILE] [--only resize|points|eval|augment|img-augment|gtdb|track]
-                                 [--gtdb-out FILE] [--track-out FILE] [--resize-out FILE] [--augment-out FILE] [--img-augment-out FILE]
+                                 [--iters 20] [--seed 0] [--out FILE] [--only resize|points|eval|augment|img-augment|gtdb|track|iou]
+                                 [--gtdb-out FILE] [--track-out FILE] [--iou-out FILE] [--resize-out FILE] [--augment-out FILE] [--img-augment-out FILE]
                                  [--points-out FILE] [--sweep-points 27000] [--sweeps K] [--eval-out FILE]
                                  [--eval-frames 800]
 
@@ -110,10 +114,11 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--img-precision", choices=("ref", "fp16"), default="ref")
     ap.add_argument("--out", default=None)
-    ap.add_argument("--only", choices=("resize", "points", "eval", "augment", "img-augment", "gtdb", "track"), default=None,
+    ap.add_argument("--only", choices=("resize", "points", "eval", "augment", "img-augment", "gtdb", "track", "iou"), default=None,
                     help="run this section alone")
     ap.add_argument("--gtdb-out", default=None, help="write the ground-truth database section to this file")
     ap.add_argument("--track-out", default=None, help="write the tracker section to this file")
+    ap.add_argument("--iou-out", default=None, help="write the rotated-box IoU and late-fusion section to this file")
     ap.add_argument("--img-augment-out", default=None, help="write the cmt_img_augment section to this file")
     ap.add_argument("--augment-out", default=None, help="write the cmt_pts_augment section to this file")
     ap.add_argument("--eval-out", default=None, help="write the detection-evaluation section to this file")
@@ -293,6 +298,9 @@ def main():
         return
     if args.only == "track":
         track_section(args, dev, say, lines)
+        return
+    if args.only == "iou":
+        iou_section(args, dev, say, lines)
         return
     frames = frame("cmt_fusion_nus")
     frame("cmtcoop_fusion_tumtraf")
@@ -1113,6 +1121,183 @@ def track_section(args, dev, say, lines):
         say(f"{name:>34} {fmt(med(ts))}   one call between two events, over the {FR} frames (launch overhead included)")
     say(f"peak device memory {torch.cuda.max_memory_allocated() / 2 ** 20:.0f} MiB")
     for path, text in ((args.out, lines), (args.track_out, lines[first:])):
+        if path:
+            os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+            with open(path, "w") as f:
+                f.write("\n".join(text) + "\n")
+
+
+def host_bev_iou(a, b):
+    """the contract of cmt_box_iou (BEV) as vectorised numpy, float64: every row of a against every row of b, B's
+    footprint clipped in A's frame against A's four half-planes"""
+    import numpy as np
+    n, m = len(a), len(b)
+    if n * m > 400000 and n > 1:          # bounded working set: blocks of rows
+        step = max(1, 400000 // m)
+        return np.concatenate([host_bev_iou(a[i:i + step], b) for i in range(0, n, step)])
+    A, B = np.repeat(a[:, :7].astype(np.float64), m, 0), np.tile(b[:, :7].astype(np.float64), (n, 1))
+    sa, ca, sb, cb = np.sin(A[:, 6]), np.cos(A[:, 6]), np.sin(B[:, 6]), np.cos(B[:, 6])
+    tx, ty = B[:, 0] - A[:, 0], B[:, 1] - A[:, 1]
+    ox, oy, c, s = tx * ca + ty * sa, ty * ca - tx * sa, cb * ca + sb * sa, sb * ca - cb * sa
+    P = len(A)
+    U, V = np.zeros((P, 8)), np.zeros((P, 8))
+    for k, (sx, sy) in enumerate(((-1, -1), (-1, 1), (1, 1), (1, -1))):
+        lx, ly = sx * B[:, 3] * 0.5, sy * B[:, 4] * 0.5
+        U[:, k], V[:, k] = lx * c - ly * s + ox, lx * s + ly * c + oy
+    cnt, rows = np.full(P, 4), np.arange(P)
+    for axis, bound, upper in ((0, A[:, 3] * 0.5, True), (0, -A[:, 3] * 0.5, False), (1, A[:, 4] * 0.5, True), (1, -A[:, 4] * 0.5, False)):
+        if axis:
+            U, V = V, U
+        OU, OV, mm = np.zeros_like(U), np.zeros_like(V), np.zeros(P, np.int64)
+        for i in range(8):
+            act = i < cnt
+            if not act.any():
+                break
+            k = np.where(i + 1 < cnt, i + 1, 0)
+            pu, pv, qu, qv = U[:, i], V[:, i], U[rows, k], V[rows, k]
+            pin, qin = (pu <= bound, qu <= bound) if upper else (pu >= bound, qu >= bound)
+            e = act & pin & (mm < 8)
+            OU[rows[e], mm[e]], OV[rows[e], mm[e]] = pu[e], pv[e]
+            mm = mm + e
+            e = act & (pin != qin) & (mm < 8)
+            with np.errstate(all="ignore"):
+                cv = pv + (bound - pu) / (qu - pu) * (qv - pv)
+            OU[rows[e], mm[e]], OV[rows[e], mm[e]] = bound[e], cv[e]
+            mm = mm + e
+        U, V, cnt = OU, OV, mm
+        if axis:
+            U, V = V, U
+    acc = np.zeros(P)
+    for i in range(1, 7):
+        cr = (U[:, i] - U[:, 0]) * (V[:, i + 1] - V[:, 0]) - (V[:, i] - V[:, 0]) * (U[:, i + 1] - U[:, 0])
+        acc = np.where(i + 1 < cnt, acc + cr, acc)
+    area = np.abs(acc) * 0.5
+    return (area / (A[:, 3] * A[:, 4] + B[:, 3] * B[:, 4] - area)).reshape(n, m)
+
+
+def host_fuse(results, poses, thr):
+    """fuse_detections on the host: copy every agent's tensors back, transform, the full IoU matrix in rank order,
+    the greedy loop (class-aware), one gather"""
+    import math
+    import numpy as np
+    bs, ss, ls = [], [], []
+    for (b, s_, lab, cnt), pose in zip(results, poses):
+        k = int(cnt.item())
+        b, s_, lab = b.cpu().numpy()[:k].astype(np.float64), s_.cpu().numpy()[:k], lab.cpu().numpy()[:k]
+        if pose is not None:
+            b[:, :3] = b[:, :3] @ pose[:3, :3].T + pose[:3, 3]
+            b[:, 6] += math.atan2(pose[1, 0], pose[0, 0])
+            b[:, 7:9] = b[:, 7:9] @ pose[:2, :2].T
+        bs.append(b), ss.append(s_), ls.append(lab)
+    b, s_, lab = np.concatenate(bs), np.concatenate(ss), np.concatenate(ls)
+    order = np.argsort(-s_, kind="stable")
+    b, s_, lab = b[order], s_[order], lab[order]
+    sup = (host_bev_iou(b, b) > thr) & (lab[:, None] == lab[None, :])
+    removed, kept = np.zeros(len(b), bool), []
+    for r in range(len(b)):
+        if not removed[r]:
+            kept.append(r)
+            removed[r + 1:] |= sup[r, r + 1:]
+    return b[kept], s_[kept], lab[kept]
+
+
+def iou_section(args, dev, say, lines):
+    """cmt_box_iou and fuse_detections against the same algorithm as numpy on the host"""
+    import math
+    import numpy as np
+    from projects.mmdet3d_plugin import native_iou as NIOU
+    from projects.mmdet3d_plugin.core.post_processing import fuse_detections
+    first = len(lines)
+    rng = np.random.RandomState(args.seed)
+
+    def objects(n):
+        """n objects on a jittered 12 m grid -> [n, 9]"""
+        side = int(math.ceil(math.sqrt(n)))
+        cells = rng.permutation(side * side)[:n]
+        b = np.zeros((n, 9), np.float32)
+        b[:, 0], b[:, 1] = (cells // side) * 12.0 - side * 6.0 + rng.uniform(-1.5, 1.5, n), (cells % side) * 12.0 - side * 6.0 + rng.uniform(-1.5, 1.5, n)
+        b[:, 2], b[:, 3], b[:, 4], b[:, 5] = rng.uniform(-1, 1, n), rng.uniform(1.5, 5, n), rng.uniform(1.2, 2.5, n), rng.uniform(1, 2, n)
+        b[:, 6], b[:, 7:9] = rng.uniform(-3.1, 3.1, n), rng.uniform(-5, 5, (n, 2))
+        return b
+
+    def seen(world, cap):
+        """one agent's view of the objects: small perturbations, padded to cap rows -> (boxes, scores, labels, count)"""
+        n = len(world)
+        b = np.zeros((cap, 9), np.float32)
+        b[:n] = world
+        b[:n, 0:2] += rng.uniform(-0.2, 0.2, (n, 2))
+        b[:n, 6] += rng.uniform(-0.05, 0.05, n)
+        return b, rng.uniform(0.05, 1.0, cap).astype(np.float32), (np.arange(cap) % 3).astype(np.int32), n
+
+    def dev_t(src):
+        return tuple(torch.from_numpy(x).to(dev) if isinstance(x, np.ndarray) else torch.tensor([x], dtype=torch.int32, device=dev)
+                     for x in src)
+
+    say(f"--- {torch.cuda.get_device_name(0)}: rotated-box IoU and late fusion; (a) the device calls and (b) the same "
+        f"algorithm as vectorised numpy (float64) on the host with the copies it needs, in alternating windows ((a): "
+        f"{args.iters} calls a window, (b): one), median of {args.repeats} windows for (a) and of 3 for (b) (min .. max) "
+        f"after {args.warmup} warm-up windows of (a), device events for (a), perf_counter for (b), ms per call")
+    for n in (300, 2048):
+        w = objects(n)
+        a, b = dev_t(seen(w, n))[0], dev_t(seen(w, n))[0]       # two views of the same n objects
+        out = torch.zeros((n, n), dtype=torch.float32, device=dev)
+        fa = lambda: [NIOU.box_iou(a, b, out=out) for _ in range(args.iters)]
+
+        def fb():
+            t0 = time.perf_counter()
+            r = host_bev_iou(a.cpu().numpy(), b.cpu().numpy())
+            return (time.perf_counter() - t0) * 1e3, r
+
+        for _ in range(args.warmup):
+            fa()
+        ta, tb = [], []
+        reps_b = 3 if n <= 300 else 1
+        for r in range(args.repeats):
+            ta.append(event_ms(fa) / args.iters)
+            if r < reps_b:
+                ms, host = fb()
+                tb.append(ms)
+        diff = float(np.abs(out.cpu().numpy().astype(np.float64) - host).max())
+        ta, tb = med(ta), med(tb)
+        say(f"{'(a) box_iou %d x %d (bev)' % (n, n):>34} {fmt(ta)}   one launch, {n * n} pairs; max |device - host| {diff:.2e}")
+        say(f"{'(b) numpy on the host':>34} {fmt(tb)}   (a) / (b) {ta[0] / tb[0]:.5f}; 2 device-to-host copies")
+    for agents in (2, 4):
+        w = objects(250)
+        poses = [None] + [np.array([[math.cos(0.3 * k), -math.sin(0.3 * k), 0, 10.0 * k], [math.sin(0.3 * k), math.cos(0.3 * k), 0, -5.0 * k],
+                                    [0, 0, 1, 0.2], [0, 0, 0, 1]]) for k in range(1, agents)]
+        res = []
+        for k in range(agents):
+            bx, sc, lab, cnt = seen(w, 300)
+            if poses[k] is not None:                             # the agent's own frame
+                inv = np.linalg.inv(poses[k])
+                bx[:cnt, :3] = bx[:cnt, :3] @ inv[:3, :3].T + inv[:3, 3]
+                bx[:cnt, 6] -= 0.3 * k
+                bx[:cnt, 7:9] = bx[:cnt, 7:9] @ inv[:2, :2].T
+            res.append(dev_t((bx, sc, lab, cnt)))
+        fa = lambda: [fuse_detections(res, iou_thr=0.2, poses=poses) for _ in range(args.iters)]
+
+        def fb():
+            t0 = time.perf_counter()
+            r = host_fuse(res, poses, 0.2)
+            return (time.perf_counter() - t0) * 1e3, r
+
+        for _ in range(args.warmup):
+            fa()
+        ta, tb = [], []
+        for r in range(args.repeats):
+            ta.append(event_ms(fa) / args.iters)
+            if r < 3:
+                ms, host = fb()
+                tb.append(ms)
+        got = fuse_detections(res, iou_thr=0.2, poses=poses)
+        k = int(got[4].item())
+        same = k == len(host[1]) and bool(np.array_equal(got[1][:k].cpu().numpy(), host[1]))
+        ta, tb = med(ta), med(tb)
+        say(f"{'(a) fuse_detections %d x 300' % agents:>34} {fmt(ta)}   concat, rank, matrix, scan, gathers; {k} of "
+            f"{agents * 250} candidates kept, {'the same boxes as' if same else 'NOT the boxes of'} (b)")
+        say(f"{'(b) numpy on the host':>34} {fmt(tb)}   (a) / (b) {ta[0] / tb[0]:.5f}; {4 * agents} device-to-host copies")
+    say(f"peak device memory {torch.cuda.max_memory_allocated() / 2 ** 20:.0f} MiB")
+    for path, text in ((args.out, lines), (args.iou_out, lines[first:])):
         if path:
             os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
             with open(path, "w") as f:

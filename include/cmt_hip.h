@@ -1902,6 +1902,139 @@ int64_t cmt_track_update_args_size(void);
 int cmt_track_predict(const cmt_track_predict_args* args, void* stream);
 int cmt_track_update(const cmt_track_update_args* args, void* stream);
 
+/* ---- rotated-box IoU, NMS and the candidate set of late fusion (boxiou.hip; additive to ABI 25) ----------
+ * How much two boxes overlap, greedy rotated NMS of one box set, and the concatenation of several agents' boxes
+ * in one frame.  THIS TEXT is the contract.  fl32 = one rounding to float32; every sum, difference, product and
+ * quotient below is an IEEE single operation rounded on its own (none is fused), in the order the parentheses
+ * give.  Caller-owned buffers and workspaces, stream-ordered, no allocation, no host read: graph-capturable.  No
+ * workgroup waits for another and there are no atomics: results are bitwise repeatable.  Buffers must not
+ * overlap.  Every CMT_EINVAL below is returned before any device work.
+ *
+ * Box rows: fp32 [n][ld], ld >= 7, columns x y z dx dy dz yaw, later columns ignored.  z_origin in {0, 0.5} says
+ * what z is: 0.5 the gravity centre (cmt_box_decode's rows, the evaluator's, the tracker's), 0 the bottom
+ * (LiDARInstance3DBoxes.tensor).  A row is INVALID if one of its seven values is not finite or dx, dy or dz <= 0:
+ * it overlaps nothing, its IoU with every row is exactly 0.  Derived values of a valid row, one sinf / cosf pair
+ * per box:
+ *   hx = dx * 0.5f, hy = dy * 0.5f, s = sinf(yaw), c = cosf(yaw), bot = z - z_origin * dz, top = bot + dz,
+ *   area = dx * dy, vol = area * dz.
+ *
+ * The overlap of a pair (A, B) is computed IN A'S OWN FRAME: the result does not depend on where in the scene
+ * the pair sits, and A's edges are axis-parallel, so identical boxes have no near-parallel edge intersections.
+ *   t = (xB - xA, yB - yA);   o = (t.x * cA + t.y * sA,  t.y * cA - t.x * sA)        (B's centre in A's frame)
+ *   c = cB * cA + sB * sA;    s = sB * cA - cB * sA                                  (the relative rotation)
+ *   corners k = 0..3 with (sx, sy) = (-,-), (-,+), (+,+), (+,-), the order of cmt_gtdb_collide:
+ *     lx = sx * hxB, ly = sy * hyB,  X_k = (lx * c - ly * s) + o.x,  Y_k = (lx * s + ly * c) + o.y
+ *   The quadrilateral is clipped (Sutherland-Hodgman) against x <= hxA, x >= -hxA, y <= hyA, y >= -hyA, in that
+ *   order.  One half-plane with bound b on coordinate u (v the other coordinate), input vertices V_0..V_n-1:
+ *   for i = 0..n-1 with p = V_i, q = V_(i+1) mod n: emit p if p is inside; then, if exactly one of p and q is
+ *   inside, emit the crossing (u, v) = (b, p.v + ((b - p.u) / (q.u - p.u)) * (q.v - p.v)).  Inside is u <= b
+ *   (u >= b for the lower bounds).  The divisor is never 0 and the clipped coordinate is the bound itself.  A
+ *   list holds at most 8 vertices; an emission beyond the eighth is dropped (it cannot occur for a convex input).
+ *   area = |sum over i = 1..n-2 of ((V_i - V_0) x (V_i+1 - V_0))| * 0.5f, the terms added in ascending i, each
+ *     cross product (a.x * b.y) - (a.y * b.x); 0 with fewer than 3 vertices.
+ *   bev   = area / ((areaA + areaB) - area)
+ *   h     = max(0, min(topA, topB) - max(botA, botB))
+ *   iou3d = (area * h) / ((volA + volB) - area * h)
+ *
+ * cmt_box_iou.  a [N][lda], b [M][ldb]; n_a, n_b: null (N, M) or device int32 words clamped to [0, N] and
+ *   [0, M].  bev and / or iou3d fp32 [N][ldo], ldo >= M; either may be null, not both.  Element (i, j) for
+ *   i < n_a, j < n_b is written exactly once; nothing else is written.  aligned != 0: M == N, the outputs are
+ *   [N], element i is row i of a against row i of b, for i < min(n_a, n_b); ldo is ignored.
+ *   One lane per pair over tiles of 64 x 64: 256 threads, a lane owns a column and walks 16 rows; the derived
+ *   values of the tile's boxes are computed once per workgroup and staged in LDS; a lane's polygon lives in an
+ *   LDS slot of its own (32 KB a workgroup), not in scratch.
+ *   CMT_EINVAL: a null struct; N or M < 0; lda or ldb < 7; z_origin not 0 or 0.5; bev and iou3d both null;
+ *   aligned with N != M; ldo < M (not aligned); more than 2^31 tiles; a misaligned (4 bytes) pointer; a or b null
+ *   with N, M > 0.  N == 0 or M == 0 is a valid call that launches nothing.
+ *
+ * cmt_box_nms.  Greedy rotated NMS of boxes [N][ld], scores fp32 [N], labels int32 [N] or null, N <=
+ *   CMT_NMS_MAX; count null (N) or a device int32 clamped to [0, N].  A row EXISTS iff it is below count, its
+ *   score is not NaN and score >= score_thr.  The existing rows are visited in descending score, equal scores
+ *   (-0 equals +0) in ascending row index.  A visited row is kept iff no previously kept row suppresses it; row j
+ *   suppresses row i iff iou(j, i) > iou_thr (strict; j the earlier, the pair computed in j's frame; bev with
+ *   use_3d == 0, iou3d otherwise) and, with labels given, labels[j] == labels[i].  An invalid box that exists is
+ *   kept and suppresses nothing.
+ *   keep_idx int32 [N]: the kept rows in visiting order, then -1.  keep (null, or uint8 [N] with keep_dtype 0,
+ *   int32 [N] with keep_dtype 1): 1 for a kept row, else 0.  keep_count: a device int32.
+ *   The contract binds only inputs in which every pair the loop can compare (two existing valid rows, of equal
+ *   label when labels are given) has |iou - iou_thr| > 8e-5, iou the exact value of the formulas above: the
+ *   float32 evaluation is held to 1e-5 of it on the host and to 8 times the host's error on the device; nearer to
+ *   the threshold than that it may fall on either side.
+ *   Three launches ordered by the stream only: (1) one workgroup ranks the rows, a bitonic sort of (key, index)
+ *   words in LDS; (2) a grid over the upper triangle of 64 x 64 tiles in rank order writes the suppression
+ *   matrix as 64-bit words, bit b of word (r, w) = rank r suppresses rank 64 w + b (ranks after r only): the 64
+ *   lanes of a wave are the 64 bits of a word; (3) one wave runs the greedy scan, lane l holding word l of the
+ *   removed set, the mask rows loaded 8 rows ahead whatever the outcome of the rows before.  Every word the scan
+ *   uses is rewritten by (2) before: the workspace needs no initialisation.
+ *   workspace: 8-byte aligned, cmt_box_nms_workspace_bytes(N) = 16 + 4 Np + Np * Np / 8 bytes, Np = N rounded up
+ *   to a multiple of 64 (-1 for N outside [0, CMT_NMS_MAX]).
+ *   CMT_EINVAL: a null struct; N outside [0, CMT_NMS_MAX]; ld < 7; z_origin not 0 or 0.5; iou_thr not finite or
+ *   negative; score_thr NaN; keep_dtype not 0 or 1; with N > 0 a null boxes, scores or keep_idx; a null
+ *   keep_count or workspace; a misaligned pointer (4 bytes, workspace 8); workspace_bytes too small.
+ *
+ * cmt_box_concat.  K <= CMT_CONCAT_MAX sources, source k with boxes [n_k][ld_k], scores fp32 [n_k], labels int32
+ *   [n_k], count_k null (n_k) or a device int32 clamped to [0, n_k], and with has_transform[k] a HOST float[12],
+ *   row-major 3 x 4 [R|t] (Rab = transform[4a + b], ta = transform[4a + 3]).  cols in 7..16 columns are carried,
+ *   every ld_k and ld_out >= cols.  Row i of source k goes to row e = n_0 + .. + n_(k-1) + i of the outputs:
+ *     i < count_k: score and label copied; without a transform the columns copied bit for bit; with one
+ *       x' = ((R00 * x + R01 * y) + R02 * z) + t0, y' and z' likewise with rows 1 and 2; sizes unchanged;
+ *       yaw' = yaw + atan2f(R10, R00) (the angle computed once on the host in float32, no wrap);
+ *       with cols >= 9: vx' = R00 * vx + R01 * vy, vy' = R10 * vx + R11 * vy; columns from 9 on copied.
+ *     i >= count_k: score -inf, label -1, the cols columns 0.
+ *   out_source int32 [sum n_k] = k for the whole segment, out_count (device int32) = sum n_k.  One launch, one
+ *   writer per element.  cmt_box_nms drops the -inf rows through any score_thr above -inf.
+ *   CMT_EINVAL: a null struct; K outside 1..CMT_CONCAT_MAX; cols outside 7..16; ld_out or an ld_k < cols; an
+ *   n_k < 0; the total capacity >= 2^30; a transform that is not finite; with n_k > 0 a null boxes, scores or
+ *   labels; with a total > 0 a null output; a null out_count; a misaligned (4 bytes) pointer. */
+#define CMT_NMS_MAX 2048
+#define CMT_CONCAT_MAX 8
+typedef struct cmt_box_iou_args {
+    int N, M, lda, ldb;
+    int aligned, reserved;
+    float z_origin, reserved_f;
+    int64_t ldo;
+    const void* a;
+    const void* b;
+    const int* n_a;
+    const int* n_b;
+    void* bev;
+    void* iou3d;
+} cmt_box_iou_args;
+typedef struct cmt_box_nms_args {
+    int N, ld, use_3d, keep_dtype;
+    float iou_thr, score_thr, z_origin, reserved_f;
+    const void* boxes;
+    const void* scores;
+    const int* labels;
+    const int* count;
+    int* keep_idx;
+    void* keep;
+    int* keep_count;
+    void* workspace;
+    int64_t workspace_bytes;
+} cmt_box_nms_args;
+typedef struct cmt_box_concat_args {
+    int K, cols, ld_out, reserved;
+    int n[CMT_CONCAT_MAX], ld[CMT_CONCAT_MAX], has_transform[CMT_CONCAT_MAX];
+    float transform[CMT_CONCAT_MAX][12];
+    const void* boxes[CMT_CONCAT_MAX];
+    const void* scores[CMT_CONCAT_MAX];
+    const int* labels[CMT_CONCAT_MAX];
+    const int* count[CMT_CONCAT_MAX];
+    void* out_boxes;
+    void* out_scores;
+    int* out_labels;
+    int* out_source;
+    int* out_count;
+} cmt_box_concat_args;
+int64_t cmt_box_iou_args_size(void);
+int64_t cmt_box_nms_args_size(void);
+int64_t cmt_box_concat_args_size(void);
+int64_t cmt_box_nms_workspace_bytes(int N);
+int cmt_box_iou(const cmt_box_iou_args* args, void* stream);
+int cmt_box_nms(const cmt_box_nms_args* args, void* stream);
+int cmt_box_concat(const cmt_box_concat_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
