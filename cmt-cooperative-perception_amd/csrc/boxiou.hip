@@ -14,7 +14,8 @@
 // bits of one word: a ballot builds it and lane 0 stores it.
 // No atomics and no workgroup waits for another: results are bitwise repeatable.
 // The file is built with -ffp-contract=off: every product, sum and quotient of the contract is rounded on its own.
-#include "cmt_common.h"
+#include "box_rigid.h"
+#include "wave_ops.h"
 
 #include <cmath>
 
@@ -35,15 +36,12 @@ struct bi_box {
     int ok;
 };
 
-__device__ __forceinline__ bool bi_finite(float v) { return __builtin_fabsf(v) < __builtin_inff(); }
-__device__ __forceinline__ int bi_clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
-
 __device__ __forceinline__ bi_box bi_derive(const float* r, float z_origin) {
 #pragma clang fp contract(off)
     const float x = r[0], y = r[1], z = r[2], dx = r[3], dy = r[4], dz = r[5], yaw = r[6];
     bi_box b;
-    b.ok = (bi_finite(x) && bi_finite(y) && bi_finite(z) && bi_finite(dx) && bi_finite(dy) && bi_finite(dz) &&
-            bi_finite(yaw) && dx > 0.f && dy > 0.f && dz > 0.f) ? 1 : 0;
+    b.ok = (finite32(x) && finite32(y) && finite32(z) && finite32(dx) && finite32(dy) && finite32(dz) &&
+            finite32(yaw) && dx > 0.f && dy > 0.f && dz > 0.f) ? 1 : 0;
     const float yw = b.ok ? yaw : 0.f;
     b.x = x, b.y = y;
     b.hx = dx * 0.5f, b.hy = dy * 0.5f;
@@ -165,17 +163,10 @@ struct bi_p {
     float z_origin;
 };
 
-__device__ __forceinline__ void bi_counts(const bi_p& p, int& na, int& nb) {
-    na = p.N, nb = p.M;
-    if (p.n_a) na = bi_clampi(*p.n_a, p.N);
-    if (p.n_b) nb = bi_clampi(*p.n_b, p.M);
-}
-
 __global__ __launch_bounds__(BI_THREADS) void box_iou_kernel(bi_p p) {
     __shared__ float px[2 * BI_SLOT], py[2 * BI_SLOT];
     __shared__ bi_box sa[BI_TILE], sb[BI_TILE];
-    int na, nb;
-    bi_counts(p, na, nb);
+    const int na = clamp_count(p.n_a, p.N), nb = clamp_count(p.n_b, p.M);
     const int tile = (int)blockIdx.x;
     const int r0 = (tile / p.tiles_x) * BI_TILE, c0 = (tile % p.tiles_x) * BI_TILE;
     if (r0 >= na || c0 >= nb) return;
@@ -211,8 +202,7 @@ __global__ __launch_bounds__(BI_THREADS) void box_iou_kernel(bi_p p) {
 
 __global__ __launch_bounds__(BI_THREADS) void box_iou_aligned_kernel(bi_p p) {
     __shared__ float px[2 * BI_SLOT], py[2 * BI_SLOT];
-    int na, nb;
-    bi_counts(p, na, nb);
+    const int na = clamp_count(p.n_a, p.N), nb = clamp_count(p.n_b, p.M);
     const int n = na < nb ? na : nb;
     const int tid = (int)threadIdx.x;
     const int64_t i = (int64_t)blockIdx.x * BI_THREADS + tid;
@@ -252,18 +242,12 @@ __device__ __forceinline__ unsigned nms_hi(u64 k) { return (unsigned)(k >> 32); 
 __global__ __launch_bounds__(NMS_RANK_THREADS) void nms_rank_kernel(nms_p p) {
     __shared__ u64 key[CMT_NMS_MAX];
     const int tid = (int)threadIdx.x;
-    int n = p.N;
-    if (p.count) n = bi_clampi(*p.count, p.N);
+    const int n = clamp_count(p.count, p.N);
     for (int e = tid; e < p.P; e += NMS_RANK_THREADS) {
         unsigned hi = 0xFFFFFFFFu;
         if (e < n) {
-            float s = p.scores[e];
-            if (s >= p.score_thr) {           // false for a NaN score
-                s = s == 0.f ? 0.f : s;       // -0 ranks as +0
-                const unsigned u = __float_as_uint(s);
-                const unsigned asc = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-                hi = ~asc;                     // descending score; at most 0xFF800000 (-inf), never all ones
-            }
+            const float s = p.scores[e];
+            if (s >= p.score_thr) hi = score_desc_key(s);   // false for a NaN score; at most 0xFF800000 (-inf), never all ones
         }
         key[e] = ((u64)hi << 32) | (unsigned)e;
     }
@@ -292,7 +276,7 @@ __global__ __launch_bounds__(BI_THREADS) void nms_mask_kernel(nms_p p) {
     __shared__ float px[2 * BI_SLOT], py[2 * BI_SLOT];
     __shared__ bi_box sa[BI_TILE], sb[BI_TILE];
     __shared__ int la[BI_TILE], lb[BI_TILE];
-    const int nv = bi_clampi(*p.nv, p.N);
+    const int nv = clamp_count(p.nv, p.N);
     const int wv = (nv + 63) >> 6;
     const int ti = (int)blockIdx.x / p.W, tj = (int)blockIdx.x % p.W;
     if (tj < ti || tj >= wv) return;          // the upper triangle of the existing ranks
@@ -304,7 +288,7 @@ __global__ __launch_bounds__(BI_THREADS) void nms_mask_kernel(nms_p p) {
         bi_box d = bi_none();
         int lab = 0;
         if (r < nv) {
-            const int row = bi_clampi(p.order[r], p.N - 1);
+            const int row = clamp_index(p.order[r], p.N - 1);
             d = bi_derive(p.boxes + (int64_t)row * p.ld, p.z_origin);
             if (p.labels) lab = p.labels[row];
         }
@@ -340,7 +324,7 @@ __device__ __forceinline__ u64 nms_readlane(u64 v, int l) {
 
 __global__ __launch_bounds__(64) void nms_scan_kernel(nms_p p) {
     const int lane = (int)threadIdx.x;
-    const int nv = __builtin_amdgcn_readfirstlane(bi_clampi(*p.nv, p.N));
+    const int nv = __builtin_amdgcn_readfirstlane(clamp_count(p.nv, p.N));
     const int wv = (nv + 63) >> 6;
     // word `lane` of mask row r; words left of the diagonal tile and rows at or beyond nv were never written
     auto load = [&](int r) -> u64 {
@@ -373,7 +357,7 @@ __global__ __launch_bounds__(64) void nms_scan_kernel(nms_p p) {
         const int r = w * 64 + lane;
         const bool bit = (k >> lane) & 1ull;
         if (r < p.N) {
-            const int row = bi_clampi(p.order[r], p.N - 1);
+            const int row = clamp_index(p.order[r], p.N - 1);
             if (bit) p.keep_idx[base + __popcll(k & ((1ull << lane) - 1ull))] = row;
             if (p.keep) {
                 if (p.keep_i32) ((int*)p.keep)[row] = bit ? 1 : 0;
@@ -429,8 +413,7 @@ __global__ __launch_bounds__(256) void box_concat_kernel(bc_p p) {
             off += p.n[q];
         }
     }
-    int c = nk;
-    if (cnt) c = bi_clampi(*cnt, nk);
+    const int c = clamp_count(cnt, nk);
     float* o = p.ob + (int64_t)e * p.ld_out;
     p.osrc[e] = k;
     if (i >= c) {
@@ -446,21 +429,14 @@ __global__ __launch_bounds__(256) void box_concat_kernel(bc_p p) {
         for (int t = 0; t < p.cols; ++t) o[t] = r[t];
         return;
     }
-    const float x = r[0], y = r[1], z = r[2];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float m0 = m[4 * a] * x, m1 = m[4 * a + 1] * y, m2 = m[4 * a + 2] * z;
-        const float s01 = m0 + m1;
-        const float s012 = s01 + m2;
-        o[a] = s012 + m[4 * a + 3];
-    }
+    const bool has_vel = p.cols >= 9;   // below 9 columns box_rigid's velocity runs on zeros and is dropped (r[7], r[8] may not exist)
+    float pos[3], vel[2];
+    box_rigid(m, r[0], r[1], r[2], has_vel ? r[7] : 0.f, has_vel ? r[8] : 0.f, pos, vel);
+    o[0] = pos[0], o[1] = pos[1], o[2] = pos[2];
     o[3] = r[3], o[4] = r[4], o[5] = r[5];
     o[6] = r[6] + yaw;
-    if (p.cols >= 9) {
-        const float vx = r[7], vy = r[8];
-        const float a0 = m[0] * vx, a1 = m[1] * vy, b0 = m[4] * vx, b1 = m[5] * vy;
-        o[7] = a0 + a1;
-        o[8] = b0 + b1;
+    if (has_vel) {
+        o[7] = vel[0], o[8] = vel[1];
         for (int t = 9; t < p.cols; ++t) o[t] = r[t];
     } else {
         for (int t = 7; t < p.cols; ++t) o[t] = r[t];
@@ -472,8 +448,6 @@ extern "C" int64_t cmt_box_iou_args_size(void) { return (int64_t)sizeof(cmt_box_
 extern "C" int64_t cmt_box_nms_args_size(void) { return (int64_t)sizeof(cmt_box_nms_args); }
 extern "C" int64_t cmt_box_concat_args_size(void) { return (int64_t)sizeof(cmt_box_concat_args); }
 
-static inline bool bi_al(const void* q, uintptr_t a) { return q != nullptr && (((uintptr_t)q) & (a - 1)) == 0; }
-static inline bool bi_al0(const void* q, uintptr_t a) { return (((uintptr_t)q) & (a - 1)) == 0; }   // null allowed
 static inline bool bi_zo(float z) { return z == 0.f || z == 0.5f; }
 
 extern "C" int64_t cmt_box_nms_workspace_bytes(int N) {
@@ -491,9 +465,9 @@ extern "C" int cmt_box_iou(const cmt_box_iou_args* a, void* stream) {
     CMT_REQUIRE(!a->aligned || a->N == a->M, "cmt_box_iou: aligned needs N == M");
     CMT_REQUIRE(a->aligned || a->ldo >= a->M, "cmt_box_iou: ldo must be at least M");
     CMT_REQUIRE(cdiv64(a->N, BI_TILE) * cdiv64(a->M, BI_TILE) < (int64_t)1 << 31, "cmt_box_iou: N * M / 4096 must stay below 2^31 tiles");
-    CMT_REQUIRE(bi_al0(a->bev, 4) && bi_al0(a->iou3d, 4), "cmt_box_iou: bev and iou3d must be 4-byte aligned");
-    CMT_REQUIRE(bi_al0(a->n_a, 4) && bi_al0(a->n_b, 4), "cmt_box_iou: n_a and n_b must be 4-byte aligned");
-    CMT_REQUIRE(bi_al0(a->a, 4) && bi_al0(a->b, 4) && (a->N == 0 || a->M == 0 || (a->a != nullptr && a->b != nullptr)),
+    CMT_REQUIRE(ptr_aligned_or_null(a->bev, 4) && ptr_aligned_or_null(a->iou3d, 4), "cmt_box_iou: bev and iou3d must be 4-byte aligned");
+    CMT_REQUIRE(ptr_aligned_or_null(a->n_a, 4) && ptr_aligned_or_null(a->n_b, 4), "cmt_box_iou: n_a and n_b must be 4-byte aligned");
+    CMT_REQUIRE(ptr_aligned_or_null(a->a, 4) && ptr_aligned_or_null(a->b, 4) && (a->N == 0 || a->M == 0 || (a->a != nullptr && a->b != nullptr)),
                 "cmt_box_iou: a and b must be non-null (with N, M > 0) and 4-byte aligned");
     if (a->N == 0 || a->M == 0) return 0;
     bi_p p;
@@ -518,12 +492,12 @@ extern "C" int cmt_box_nms(const cmt_box_nms_args* a, void* stream) {
     CMT_REQUIRE(std::isfinite(a->iou_thr) && a->iou_thr >= 0.f, "cmt_box_nms: iou_thr must be finite and not negative");
     CMT_REQUIRE(!std::isnan(a->score_thr), "cmt_box_nms: score_thr must not be NaN");
     CMT_REQUIRE(a->keep_dtype == 0 || a->keep_dtype == 1, "cmt_box_nms: keep_dtype must be 0 (uint8) or 1 (int32)");
-    CMT_REQUIRE(a->N == 0 || (bi_al(a->boxes, 4) && bi_al(a->scores, 4)), "cmt_box_nms: boxes and scores must be non-null and 4-byte aligned");
-    CMT_REQUIRE(bi_al0(a->labels, 4) && bi_al0(a->count, 4), "cmt_box_nms: labels and count must be 4-byte aligned");
-    CMT_REQUIRE(a->N == 0 || bi_al(a->keep_idx, 4), "cmt_box_nms: keep_idx must be non-null and 4-byte aligned");
-    CMT_REQUIRE(bi_al0(a->keep, a->keep_dtype ? 4 : 1), "cmt_box_nms: an int32 keep must be 4-byte aligned");
-    CMT_REQUIRE(bi_al(a->keep_count, 4), "cmt_box_nms: keep_count must be non-null and 4-byte aligned");
-    CMT_REQUIRE(bi_al(a->workspace, 8), "cmt_box_nms: workspace must be non-null and 8-byte aligned");
+    CMT_REQUIRE(a->N == 0 || (ptr_aligned(a->boxes, 4) && ptr_aligned(a->scores, 4)), "cmt_box_nms: boxes and scores must be non-null and 4-byte aligned");
+    CMT_REQUIRE(ptr_aligned_or_null(a->labels, 4) && ptr_aligned_or_null(a->count, 4), "cmt_box_nms: labels and count must be 4-byte aligned");
+    CMT_REQUIRE(a->N == 0 || ptr_aligned(a->keep_idx, 4), "cmt_box_nms: keep_idx must be non-null and 4-byte aligned");
+    CMT_REQUIRE(ptr_aligned_or_null(a->keep, a->keep_dtype ? 4 : 1), "cmt_box_nms: an int32 keep must be 4-byte aligned");
+    CMT_REQUIRE(ptr_aligned(a->keep_count, 4), "cmt_box_nms: keep_count must be non-null and 4-byte aligned");
+    CMT_REQUIRE(ptr_aligned(a->workspace, 8), "cmt_box_nms: workspace must be non-null and 8-byte aligned");
     CMT_REQUIRE(a->workspace_bytes >= cmt_box_nms_workspace_bytes(a->N), "cmt_box_nms: workspace_bytes is below cmt_box_nms_workspace_bytes(N)");
     const int np = (int)cdiv64(a->N, 64) * 64;
     nms_p p;
@@ -558,9 +532,9 @@ extern "C" int cmt_box_concat(const cmt_box_concat_args* a, void* stream) {
     for (int k = 0; k < a->K; ++k) {
         CMT_REQUIRE(a->n[k] >= 0, "cmt_box_concat: a source's capacity must not be negative");
         CMT_REQUIRE(a->ld[k] >= a->cols, "cmt_box_concat: a source's ld must be at least cols");
-        CMT_REQUIRE(a->n[k] == 0 || (bi_al(a->boxes[k], 4) && bi_al(a->scores[k], 4) && bi_al(a->labels[k], 4)),
+        CMT_REQUIRE(a->n[k] == 0 || (ptr_aligned(a->boxes[k], 4) && ptr_aligned(a->scores[k], 4) && ptr_aligned(a->labels[k], 4)),
                     "cmt_box_concat: a source's boxes, scores and labels must be non-null and 4-byte aligned");
-        CMT_REQUIRE(bi_al0(a->count[k], 4), "cmt_box_concat: a source's count must be 4-byte aligned");
+        CMT_REQUIRE(ptr_aligned_or_null(a->count[k], 4), "cmt_box_concat: a source's count must be 4-byte aligned");
         if (a->has_transform[k]) {
             bool fin = true;
             for (int t = 0; t < 12; ++t) fin = fin && std::isfinite(a->transform[k][t]);
@@ -574,9 +548,9 @@ extern "C" int cmt_box_concat(const cmt_box_concat_args* a, void* stream) {
         total += a->n[k];
     }
     CMT_REQUIRE(total < (int64_t)1 << 30, "cmt_box_concat: the total capacity must stay below 2^30");
-    CMT_REQUIRE(total == 0 || (bi_al(a->out_boxes, 4) && bi_al(a->out_scores, 4) && bi_al(a->out_labels, 4) && bi_al(a->out_source, 4)),
+    CMT_REQUIRE(total == 0 || (ptr_aligned(a->out_boxes, 4) && ptr_aligned(a->out_scores, 4) && ptr_aligned(a->out_labels, 4) && ptr_aligned(a->out_source, 4)),
                 "cmt_box_concat: out_boxes, out_scores, out_labels and out_source must be non-null and 4-byte aligned");
-    CMT_REQUIRE(bi_al(a->out_count, 4), "cmt_box_concat: out_count must be non-null and 4-byte aligned");
+    CMT_REQUIRE(ptr_aligned(a->out_count, 4), "cmt_box_concat: out_count must be non-null and 4-byte aligned");
     p.ob = (float*)a->out_boxes, p.os = (float*)a->out_scores, p.ol = a->out_labels, p.osrc = a->out_source;
     p.ocount = a->out_count;
     p.K = a->K, p.cols = a->cols, p.ld_out = a->ld_out, p.total = (int)total;

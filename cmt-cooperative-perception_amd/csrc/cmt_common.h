@@ -29,6 +29,12 @@ int cmt_check_launch(const char* what);
         if (!(cond)) return cmt_fail(CMT_EINVAL, std::string(msg)); \
     } while (0)
 
+// a valid request beyond what is built (a cap of the kernels)
+#define CMT_REQUIRE_SUPPORTED(cond, msg)                          \
+    do {                                                          \
+        if (!(cond)) return cmt_fail(CMT_ENOTSUP, std::string(msg)); \
+    } while (0)
+
 // ---- element conversion ----------------------------------------------------
 template <typename T>
 __device__ __forceinline__ float to_f32(T x) { return (float)x; }
@@ -159,6 +165,9 @@ __device__ __forceinline__ int acc_row(int i, int h) { return (i & 3) + 8 * (i >
 
 template <typename T>
 static inline bool aligned16(const T* p) { return (((uintptr_t)p) & 15) == 0; }
+// a (a power of two) divides the address; a null pointer passes only the second
+static inline bool ptr_aligned_or_null(const void* q, uintptr_t a) { return (((uintptr_t)q) & (a - 1)) == 0; }
+static inline bool ptr_aligned(const void* q, uintptr_t a) { return q != nullptr && ptr_aligned_or_null(q, a); }
 
 // The long-key f16 attention forward (attention.hip, cmt_attn_fwd's bounded-offset path) that
 // also writes the row statistic lse[(b * H + h) * Nq + q] = log2(sum_k exp2(c s_qk)) (exp2 units

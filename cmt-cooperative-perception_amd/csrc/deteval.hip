@@ -18,7 +18,7 @@
 //                     integer block scan of tp (exact) with the order-preserving compaction of the matches,
 //                     the two 101-point resamplings by binary search, per error the NaN-aware cumulative mean
 //                     as a fixed-tree float64 scan and the reversed resampling, then calc_ap / calc_tp.
-#include "cmt_common.h"
+#include "wave_ops.h"
 
 #include <cmath>
 #include <cstdint>
@@ -63,30 +63,17 @@ __device__ __forceinline__ int64_t det_lower_bound(const int64_t* k, int64_t n, 
     return lo;
 }
 
-// ~ord(score): ascending in this value is descending in the score; -0 counts as +0
-__device__ __forceinline__ uint32_t det_score_key(float s) {
-    uint32_t u = __float_as_uint(s + 0.f);
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return ~u;
-}
-
-__device__ __forceinline__ int det_count(const int* word, int64_t cap) {
-    if (word == nullptr) return (int)cap;
-    const int v = *word;
-    return v < 0 ? 0 : ((int64_t)v > cap ? (int)cap : v);
-}
-
 __global__ __launch_bounds__(DET_THREADS) void det_keys_kernel(det_p p) {
     const int64_t i = (int64_t)blockIdx.x * DET_THREADS + threadIdx.x;
     if (i < p.N) {
         int64_t kc = DET_NONE, ks = DET_NONE;
-        if (i < det_count(p.n_pred, p.N)) {
+        if (i < clamp_count(p.n_pred, p.N)) {
             const int c = p.plabel[i], s = p.psample[i];
             if (c >= 0 && c < p.C && s >= 0 && s < p.S) {
                 const double x = (double)p.pbox[i * 9], y = (double)p.pbox[i * 9 + 1];
                 const double xx = x * x, yy = y * y;
                 if (sqrt(xx + yy) < p.range[c]) {
-                    const int64_t sk = (int64_t)det_score_key(p.pscore[i]);
+                    const int64_t sk = (int64_t)score_desc_key(p.pscore[i]);
                     kc = ((int64_t)c << 32) | sk;
                     ks = ((((int64_t)s << 6) | (int64_t)c) << 32) | sk;
                 }
@@ -97,7 +84,7 @@ __global__ __launch_bounds__(DET_THREADS) void det_keys_kernel(det_p p) {
     }
     if (i < p.G) {
         int64_t kg = DET_NONE;
-        if (i < det_count(p.n_gt, p.G)) {
+        if (i < clamp_count(p.n_gt, p.G)) {
             const int c = p.glabel[i], s = p.gsample[i];
             if (c >= 0 && c < p.C && s >= 0 && s < p.S && p.gnum[i] != 0) {
                 const double x = (double)p.gbox[i * 9], y = (double)p.gbox[i * 9 + 1];
@@ -148,8 +135,7 @@ __device__ __forceinline__ void det_write_miss(const det_p& p, int t, int64_t i)
 }
 
 __device__ __forceinline__ int det_block_sum(int v, int* part) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
+    v = wave_sum(v);
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
     __syncthreads();
     int s = 0;
@@ -268,24 +254,12 @@ __global__ __launch_bounds__(DET_THREADS) void det_match_kernel(det_p p) {
 // inclusive scan over the workgroup's DET_CHUNK terms, thread-major: v[] in, inclusive prefix out; returns the
 // chunk total.  Tree: the thread's 8 terms in order, shuffle-up scan of the 64 thread totals, the 4 wave totals
 // in order.  part: DET_WAVES entries, free again after the call.
-__device__ __forceinline__ int det_shfl_up(int v, int d) { return __shfl_up(v, d, 64); }
-__device__ __forceinline__ double det_shfl_up(double v, int d) {
-    const long long bits = __double_as_longlong(v);
-    const int hi = __shfl_up((int)(bits >> 32), d, 64), lo = __shfl_up((int)(uint32_t)bits, d, 64);
-    return __longlong_as_double(((long long)hi << 32) | (long long)(uint32_t)lo);
-}
-
 template <typename V>
 __device__ __forceinline__ V det_block_scan(V (&v)[DET_PER], V* part) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 #pragma unroll
     for (int j = 1; j < DET_PER; ++j) v[j] = v[j - 1] + v[j];
-    V run = v[DET_PER - 1];   // becomes the inclusive sum over the wave's threads up to this one
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const V o = det_shfl_up(run, d);
-        if (lane >= d) run = o + run;
-    }
+    const V run = wave_scan_incl(v[DET_PER - 1]);   // the inclusive sum over the wave's threads up to this one, as o + run
     __syncthreads();   // part may still be read from the call before
     if (lane == 63) part[w] = run;
     __syncthreads();
@@ -295,7 +269,7 @@ __device__ __forceinline__ V det_block_scan(V (&v)[DET_PER], V* part) {
         if (k == w) before = total;
         total = total + part[k];
     }
-    V tb = det_shfl_up(run, 1);   // the threads before in the wave
+    V tb = wave_shfl_up(run, 1);   // the threads before in the wave
     if (lane == 0) tb = (V)0;
     const V base = before + tb;
 #pragma unroll
@@ -541,16 +515,14 @@ static int det_fill(const cmt_det_eval_args* a, det_p& p, const char* who) {
     return 0;
 }
 
-static bool det_aligned(const void* q, uintptr_t al) { return q != nullptr && (((uintptr_t)q) & (al - 1)) == 0; }
-
 #define DET_PTR(field, al, rows)                                                                                     \
-    CMT_REQUIRE((rows) == 0 || det_aligned(a->field, al), std::string(who) + ": " #field " must be non-null and " #al \
+    CMT_REQUIRE((rows) == 0 || ptr_aligned(a->field, al), std::string(who) + ": " #field " must be non-null and " #al \
                                                                                  "-byte aligned")
 
 static int det_check_inputs(const cmt_det_eval_args* a, const char* who) {
     DET_PTR(pred_box, 4, a->N); DET_PTR(pred_score, 4, a->N); DET_PTR(pred_label, 4, a->N); DET_PTR(pred_sample, 4, a->N);
     DET_PTR(gt_box, 4, a->G); DET_PTR(gt_label, 4, a->G); DET_PTR(gt_sample, 4, a->G); DET_PTR(gt_num_pts, 4, a->G);
-    CMT_REQUIRE((((uintptr_t)a->n_pred) & 3) == 0 && (((uintptr_t)a->n_gt) & 3) == 0,
+    CMT_REQUIRE(ptr_aligned_or_null(a->n_pred, 4) && ptr_aligned_or_null(a->n_gt, 4),
                 std::string(who) + ": n_pred and n_gt must be 4-byte aligned");
     return 0;
 }

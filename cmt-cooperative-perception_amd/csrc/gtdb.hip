@@ -37,7 +37,7 @@ struct gtx_p {
 __device__ __forceinline__ void gtx_load(const gtx_p& p, int w, int lane, float (&x)[AUG_R], float (&y)[AUG_R],
                                          float (&z)[AUG_R]) {
     const unsigned t0 = blockIdx.x * (unsigned)AUG_T;
-    const unsigned cnt = (unsigned)aug_clamped(p.count_in, p.N);
+    const unsigned cnt = (unsigned)clamp_count(p.count_in, p.N);
 #pragma unroll
     for (int r = 0; r < AUG_R; ++r) {
         const unsigned i = t0 + (unsigned)((r * 4 + w) * 64 + lane);
@@ -90,12 +90,7 @@ __global__ __launch_bounds__(AUG_THREADS) void gtdb_scan_kernel(gtx_p p) {
     int a[4], local = 0;
 #pragma unroll
     for (int q = 0; q < 4; ++q) a[q] = s[4 * tid + q], local += a[q];
-    int incl = local;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int up = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += up;
-    }
+    const int incl = wave_scan_incl(local);
     if (lane == 63) wt[w] = incl;
     __syncthreads();   // s has been read by every thread, wt is written
     int run = incl - local;
@@ -120,6 +115,8 @@ __global__ __launch_bounds__(AUG_THREADS) void gtdb_scan_kernel(gtx_p p) {
     }
 }
 
+// Not on tile_rank (wave_ops.h): the chunk table is per box (cc[b]), one barrier covers the tables of all the boxes a
+// tile visits and a chunk without a hit skips its walk; tile_rank would cost a barrier pair per box.
 __global__ __launch_bounds__(AUG_THREADS) void gtdb_scatter_kernel(gtx_p p) {
     __shared__ aug_box bx[PIB_CB];
     __shared__ int cc[PIB_CB][AUG_CHUNKS];
@@ -168,7 +165,7 @@ __global__ __launch_bounds__(AUG_THREADS) void gtdb_scatter_kernel(gtx_p p) {
                 const int c = r * 4 + w;
                 int at = sbase[b];
                 for (int v = 0; v < c; ++v) at += cc[b][v];
-                const long long g = (long long)at + aug_wave_rank(m);
+                const long long g = (long long)at + wave_rank(m);
                 if (in && g < p.cap) {
 #pragma clang fp contract(off)
                     const unsigned i = t0 + (unsigned)(c * 64 + lane);   // below *count_in <= N: the row exists
@@ -349,12 +346,12 @@ extern "C" int cmt_gtdb_extract(const cmt_gtdb_extract_args* a, void* stream) {
     CMT_REQUIRE(a->cap >= 0 && a->cap < ((int64_t)1 << 31), "cmt_gtdb_extract: cap must be in [0, 2^31)");
     const int64_t need = cmt_gtdb_extract_workspace_bytes(a->N, a->M);
     CMT_REQUIRE(a->workspace_bytes >= need, "cmt_gtdb_extract: workspace below cmt_gtdb_extract_workspace_bytes(N, M)");
-    if (a->N > 0) CMT_REQUIRE(a->points && aug_aligned(a->points, 4), "cmt_gtdb_extract: points must be non-null and 4-byte aligned");
-    if (a->M > 0) CMT_REQUIRE(a->boxes && aug_aligned(a->boxes, 4), "cmt_gtdb_extract: boxes must be non-null and 4-byte aligned");
-    CMT_REQUIRE(a->offsets && aug_aligned(a->offsets, 4), "cmt_gtdb_extract: offsets must be non-null and 4-byte aligned");
-    CMT_REQUIRE(aug_aligned(a->count_in, 4) && aug_aligned(a->rows, 4), "cmt_gtdb_extract: count_in and rows must be 4-byte aligned");
+    if (a->N > 0) CMT_REQUIRE(ptr_aligned(a->points, 4), "cmt_gtdb_extract: points must be non-null and 4-byte aligned");
+    if (a->M > 0) CMT_REQUIRE(ptr_aligned(a->boxes, 4), "cmt_gtdb_extract: boxes must be non-null and 4-byte aligned");
+    CMT_REQUIRE(ptr_aligned(a->offsets, 4), "cmt_gtdb_extract: offsets must be non-null and 4-byte aligned");
+    CMT_REQUIRE(ptr_aligned_or_null(a->count_in, 4) && ptr_aligned_or_null(a->rows, 4), "cmt_gtdb_extract: count_in and rows must be 4-byte aligned");
     if (a->cap > 0) CMT_REQUIRE(a->rows != nullptr, "cmt_gtdb_extract: rows must be non-null with cap > 0");
-    if (need > 0) CMT_REQUIRE(a->workspace && aug_aligned(a->workspace, 4), "cmt_gtdb_extract: workspace must be non-null and 4-byte aligned");
+    if (need > 0) CMT_REQUIRE(ptr_aligned(a->workspace, 4), "cmt_gtdb_extract: workspace must be non-null and 4-byte aligned");
     gtx_p p;
     p.pts = (const float*)a->points;
     p.count_in = a->count_in;
@@ -380,8 +377,8 @@ extern "C" int cmt_gtdb_gather(const cmt_gtdb_gather_args* a, void* stream) {
     CMT_REQUIRE(a->F >= 3 && a->F <= 8, "cmt_gtdb_gather: F must be 3..8");
     CMT_REQUIRE(a->n_rows >= 0 && a->n_rows < ((int64_t)1 << 31) && a->n_dst >= 0 && a->n_dst < ((int64_t)1 << 31),
                 "cmt_gtdb_gather: n_rows and n_dst must be in [0, 2^31)");
-    CMT_REQUIRE(aug_aligned(a->rows, 4) && aug_aligned(a->dst, 4) && aug_aligned(a->seg_offset, 4) && aug_aligned(a->seg_len, 4) &&
-                    aug_aligned(a->dst_offset, 4) && aug_aligned(a->centre, 4),
+    CMT_REQUIRE(ptr_aligned_or_null(a->rows, 4) && ptr_aligned_or_null(a->dst, 4) && ptr_aligned_or_null(a->seg_offset, 4) && ptr_aligned_or_null(a->seg_len, 4) &&
+                    ptr_aligned_or_null(a->dst_offset, 4) && ptr_aligned_or_null(a->centre, 4),
                 "cmt_gtdb_gather: every buffer must be 4-byte aligned");
     if (a->K == 0) return 0;
     CMT_REQUIRE(a->seg_offset && a->seg_len && a->dst_offset && a->centre,
@@ -415,9 +412,9 @@ extern "C" int cmt_gtdb_collide(const cmt_gtdb_collide_args* a, void* stream) {
             if (i == 0 || a->group[i] != a->group[i - 1]) p.first[i >> 5] |= 1u << (i & 31);
         }
     }
-    CMT_REQUIRE(a->count && aug_aligned(a->count, 4), "cmt_gtdb_collide: count must be non-null and 4-byte aligned");
-    if (a->n_gt + a->n_s > 0) CMT_REQUIRE(a->boxes && aug_aligned(a->boxes, 4), "cmt_gtdb_collide: boxes must be non-null and 4-byte aligned");
-    if (a->n_s > 0) CMT_REQUIRE(a->keep && aug_aligned(a->keep, 4), "cmt_gtdb_collide: keep must be non-null and 4-byte aligned");
+    CMT_REQUIRE(ptr_aligned(a->count, 4), "cmt_gtdb_collide: count must be non-null and 4-byte aligned");
+    if (a->n_gt + a->n_s > 0) CMT_REQUIRE(ptr_aligned(a->boxes, 4), "cmt_gtdb_collide: boxes must be non-null and 4-byte aligned");
+    if (a->n_s > 0) CMT_REQUIRE(ptr_aligned(a->keep, 4), "cmt_gtdb_collide: keep must be non-null and 4-byte aligned");
     p.boxes = (const float*)a->boxes;
     p.keep = a->keep;
     p.count = a->count;

@@ -7,18 +7,13 @@
 //   cmt_boxes_augment:   the same parameters on the annotations, with ObjectRangeFilter, ObjectNameFilter,
 //                        limit_yaw and the gravity-centre layout, in one workgroup.
 //
-// cmt_pts_augment has the structure of ptsprep.hip: two launches, no workgroup waits for another.  A workgroup
-// owns a tile of AUG_T consecutive slots; a thread owns AUG_R of them, slot c * 64 + lane of chunk
-// c = r * 4 + wave, so slot order is (chunk, lane) order.  aug_count_kernel stores the tile's kept count in the
-// workspace; aug_scatter_kernel sums the counts in front of its tile and of all tiles, evaluates its slots again
-// with the same function, ranks the kept ones (ballot / mbcnt inside a chunk, an LDS prefix over the chunks),
-// writes them at their rank and NaN-fills the rows of its own index range at or beyond the total.  Scatter
-// targets lie below the total and fill targets at or beyond it, so no element has two writers.
+// cmt_pts_augment has the structure of ptsprep.hip: the count and the scatter launch of wave_ops.h's compaction
+// (compact_count, compact_scatter) over tiles of AUG_T consecutive slots, with aug_slot as the row function of both.
 // The boxes are staged in LDS as centre, half extents and one sinf / cosf pair each: both launches of
 // cmt_pts_augment compute them with the same instructions, so a point near a face falls on the same side in both.
 // Contraction is off for the row functions (and for the file, see the Makefile): the contract's products and
-// sums are separate roundings.  The tile constants, aug_stage / aug_inside and the wave helpers are aug_inside.h,
-// which gtdb.hip includes too: its extraction puts a point near a face on the same side as the calls here.
+// sums are separate roundings.  The tile constants and aug_stage / aug_inside are aug_inside.h, which gtdb.hip
+// includes too: its extraction puts a point near a face on the same side as the calls here.
 #include "aug_inside.h"
 
 // rotation, scale, translation and flips on v[0..2]
@@ -60,7 +55,7 @@ __global__ __launch_bounds__(AUG_THREADS) void pib_kernel(pib_p p) {
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const unsigned t0 = blockIdx.x * (unsigned)AUG_T;
-    const unsigned cnt = (unsigned)aug_clamped(p.count_in, p.N);
+    const unsigned cnt = (unsigned)clamp_count(p.count_in, p.N);
     float x[AUG_R], y[AUG_R], z[AUG_R];
     int first[AUG_R];
 #pragma unroll
@@ -154,84 +149,17 @@ __device__ __forceinline__ bool aug_slot(const aug_p& p, const aug_box* bx, unsi
 
 __global__ __launch_bounds__(AUG_THREADS) void aug_count_kernel(aug_p p) {
     __shared__ aug_box bx[CMT_AUG_MAX_BOXES];
-    __shared__ int part[AUG_THREADS / 64];
     aug_stage_all(p, bx);
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const unsigned t0 = blockIdx.x * (unsigned)AUG_T;
-    const unsigned cnt = (unsigned)aug_clamped(p.count_in, p.n_src);
-    int kept = 0;
-#pragma unroll
-    for (int r = 0; r < AUG_R; ++r) {
-        float o[8];
-        const bool keep = aug_slot(p, bx, cnt, t0 + (unsigned)((r * 4 + w) * 64 + lane), o);
-        kept += __popcll(__ballot(keep));
-    }
-    if (lane == 0) part[w] = kept;
-    __syncthreads();
-    if (threadIdx.x == 0) p.tile_cnt[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
+    const unsigned cnt = (unsigned)clamp_count(p.count_in, p.n_src);
+    compact_count(p.tile_cnt, [&](unsigned j, float (&o)[8]) { return aug_slot(p, bx, cnt, j, o); });
 }
 
 __global__ __launch_bounds__(AUG_THREADS) void aug_scatter_kernel(aug_p p) {
     __shared__ aug_box bx[CMT_AUG_MAX_BOXES];
-    __shared__ int part[2][AUG_THREADS / 64];
-    __shared__ int chunk[AUG_CHUNKS];
     aug_stage_all(p, bx);
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int b = (int)blockIdx.x;
-    int before = 0, total = 0;
-    for (int t = (int)threadIdx.x; t < p.tiles; t += AUG_THREADS) {
-        const int c = p.tile_cnt[t];
-        total += c;
-        before += t < b ? c : 0;
-    }
-    before = aug_wave_sum(before);
-    total = aug_wave_sum(total);
-    if (lane == 0) part[0][w] = before, part[1][w] = total;
-
-    const unsigned t0 = (unsigned)b * (unsigned)AUG_T;
-    const unsigned cnt = (unsigned)aug_clamped(p.count_in, p.n_src);
-    float o[AUG_R][8];
-    bool keep[AUG_R];
-    int rank[AUG_R];
-#pragma unroll
-    for (int r = 0; r < AUG_R; ++r) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) o[r][j] = 0.f;
-        keep[r] = aug_slot(p, bx, cnt, t0 + (unsigned)((r * 4 + w) * 64 + lane), o[r]);
-        const unsigned long long m = __ballot(keep[r]);
-        rank[r] = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-        if (lane == 0) chunk[r * 4 + w] = __popcll(m);
-    }
-    __syncthreads();
-    before = part[0][0] + part[0][1] + part[0][2] + part[0][3];
-    total = part[1][0] + part[1][1] + part[1][2] + part[1][3];
-    if (b == 0 && threadIdx.x == 0) *p.count = total;
-
-    const unsigned nan32 = 0x7fc00000u;
-    int run = before;   // kept rows in front of chunk c
-#pragma unroll
-    for (int c = 0; c < AUG_CHUNKS; ++c) {
-        if ((c & 3) == w) {
-            const int r = c >> 2;
-            const unsigned i = t0 + (unsigned)(c * 64 + lane);
-            const unsigned g = (unsigned)(run + rank[r]);   // below total <= n_in: both launches evaluate the same function
-            if (keep[r] && g < p.n_in) {
-                float* q = p.dst + (int64_t)g * p.F;
-#pragma unroll
-                for (int j = 0; j < 8; ++j)
-                    if (j < p.F) q[j] = o[r][j];
-            }
-            if (i < p.n_in && i >= (unsigned)total) {
-                unsigned* q = (unsigned*)p.dst + (int64_t)i * p.F;
-#pragma unroll
-                for (int j = 0; j < 8; ++j)
-                    if (j < p.F) q[j] = nan32;
-            }
-        }
-        run += chunk[c];
-    }
+    const unsigned cnt = (unsigned)clamp_count(p.count_in, p.n_src);
+    compact_scatter(p.tile_cnt, p.tiles, p.dst, p.count, p.n_in, p.F,
+                    [&](unsigned j, float (&o)[8]) { return aug_slot(p, bx, cnt, j, o); });
 }
 
 // ---- cmt_boxes_augment --------------------------------------------------------------------------------------
@@ -282,9 +210,7 @@ __device__ __forceinline__ bool aug_box_eval(const box_p& p, float (&b)[9], long
 }
 
 __global__ __launch_bounds__(AUG_THREADS) void boxes_augment_kernel(box_p p) {
-    __shared__ int wsum[AUG_THREADS / 64];
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    __shared__ int tab[4];
     int base = 0;   // kept boxes in front of this pass, the same in every thread
     for (int c0 = 0; c0 < p.n; c0 += AUG_THREADS) {
         const int i = c0 + (int)threadIdx.x;
@@ -292,27 +218,19 @@ __global__ __launch_bounds__(AUG_THREADS) void boxes_augment_kernel(box_p p) {
 #pragma unroll
         for (int k = 0; k < 9; ++k) b[k] = 0.f;
         long long label = -1;
-        bool keep = false;
+        bool keep[1] = {false};
         if (i < p.n) {
             const float* q = p.boxes + (int64_t)i * p.D;
 #pragma unroll
             for (int k = 0; k < 9; ++k)
                 if (k < p.D) b[k] = q[k];
             label = p.labels[i];
-            keep = aug_box_eval(p, b, label);
+            keep[0] = aug_box_eval(p, b, label);
         }
-        const unsigned long long m = __ballot(keep);
-        const int rank = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-        if (lane == 0) wsum[w] = __popcll(m);
-        __syncthreads();
-        int off = base, tot = 0;
-#pragma unroll
-        for (int v = 0; v < AUG_THREADS / 64; ++v) {
-            off += v < w ? wsum[v] : 0;
-            tot += wsum[v];
-        }
-        if (keep) {
-            const int g = off + rank;   // <= i
+        int rank[1];
+        const int tot = tile_rank<1>(keep, rank, tab);
+        if (keep[0]) {
+            const int g = base + rank[0];   // <= i
             float* q = p.out_boxes + (int64_t)g * p.D;
 #pragma unroll
             for (int k = 0; k < 9; ++k)
@@ -320,12 +238,10 @@ __global__ __launch_bounds__(AUG_THREADS) void boxes_augment_kernel(box_p p) {
             p.out_labels[g] = label;
         }
         base += tot;
-        __syncthreads();   // wsum is rewritten by the next pass
     }
-    const unsigned nan32 = 0x7fc00000u;
     for (int i = base + (int)threadIdx.x; i < p.n; i += AUG_THREADS) {
         unsigned* q = (unsigned*)p.out_boxes + (int64_t)i * p.D;
-        for (int k = 0; k < p.D; ++k) q[k] = nan32;
+        for (int k = 0; k < p.D; ++k) q[k] = QNAN32;
         p.out_labels[i] = -1;
     }
     if (threadIdx.x == 0) *p.count = base;
@@ -368,9 +284,9 @@ extern "C" int cmt_points_in_boxes(const cmt_points_in_boxes_args* a, void* stre
     CMT_REQUIRE(a->M >= 0 && a->M < (1 << 24), "cmt_points_in_boxes: M must be in [0, 2^24)");
     CMT_REQUIRE(a->F >= 3 && a->F <= 8, "cmt_points_in_boxes: F must be 3..8");
     CMT_REQUIRE(a->D == 7 || a->D == 9, "cmt_points_in_boxes: D must be 7 or 9");
-    if (a->N > 0) CMT_REQUIRE(a->points && aug_aligned(a->points, 4), "cmt_points_in_boxes: points must be non-null and 4-byte aligned");
-    if (a->M > 0) CMT_REQUIRE(a->boxes && aug_aligned(a->boxes, 4), "cmt_points_in_boxes: boxes must be non-null and 4-byte aligned");
-    CMT_REQUIRE(aug_aligned(a->count_in, 4) && aug_aligned(a->box_of_point, 4) && aug_aligned(a->count_per_box, 4),
+    if (a->N > 0) CMT_REQUIRE(ptr_aligned(a->points, 4), "cmt_points_in_boxes: points must be non-null and 4-byte aligned");
+    if (a->M > 0) CMT_REQUIRE(ptr_aligned(a->boxes, 4), "cmt_points_in_boxes: boxes must be non-null and 4-byte aligned");
+    CMT_REQUIRE(ptr_aligned_or_null(a->count_in, 4) && ptr_aligned_or_null(a->box_of_point, 4) && ptr_aligned_or_null(a->count_per_box, 4),
                 "cmt_points_in_boxes: count_in, box_of_point and count_per_box must be 4-byte aligned");
     const hipStream_t st = (hipStream_t)stream;
     pib_p p;
@@ -398,14 +314,14 @@ extern "C" int cmt_pts_augment(const cmt_pts_augment_args* a, void* stream) {
     CMT_REQUIRE(a->shift_height == 0, "cmt_pts_augment: shift_height is not built");
     if (const char* e = aug_xform_error(a->xf)) return cmt_fail(CMT_EINVAL, std::string("cmt_pts_augment: ") + e);
     const int64_t n_in = a->n_src + a->n_paste;
-    CMT_REQUIRE(a->count != nullptr && aug_aligned(a->count, 4), "cmt_pts_augment: count must be non-null and 4-byte aligned");
-    CMT_REQUIRE(aug_aligned(a->count_in, 4) && aug_aligned(a->order, 4), "cmt_pts_augment: count_in and order must be 4-byte aligned");
-    if (a->n_src > 0) CMT_REQUIRE(a->src && aug_aligned(a->src, 4), "cmt_pts_augment: src must be non-null and 4-byte aligned");
-    if (a->n_paste > 0) CMT_REQUIRE(a->paste && aug_aligned(a->paste, 4), "cmt_pts_augment: paste must be non-null and 4-byte aligned");
-    if (a->K > 0) CMT_REQUIRE(a->paste_boxes && aug_aligned(a->paste_boxes, 4), "cmt_pts_augment: paste_boxes must be non-null and 4-byte aligned");
+    CMT_REQUIRE(ptr_aligned(a->count, 4), "cmt_pts_augment: count must be non-null and 4-byte aligned");
+    CMT_REQUIRE(ptr_aligned_or_null(a->count_in, 4) && ptr_aligned_or_null(a->order, 4), "cmt_pts_augment: count_in and order must be 4-byte aligned");
+    if (a->n_src > 0) CMT_REQUIRE(ptr_aligned(a->src, 4), "cmt_pts_augment: src must be non-null and 4-byte aligned");
+    if (a->n_paste > 0) CMT_REQUIRE(ptr_aligned(a->paste, 4), "cmt_pts_augment: paste must be non-null and 4-byte aligned");
+    if (a->K > 0) CMT_REQUIRE(ptr_aligned(a->paste_boxes, 4), "cmt_pts_augment: paste_boxes must be non-null and 4-byte aligned");
     if (n_in > 0) {
-        CMT_REQUIRE(a->dst && aug_aligned(a->dst, 4), "cmt_pts_augment: dst must be non-null and 4-byte aligned");
-        CMT_REQUIRE(a->workspace && aug_aligned(a->workspace, 4), "cmt_pts_augment: workspace must be non-null and 4-byte aligned");
+        CMT_REQUIRE(ptr_aligned(a->dst, 4), "cmt_pts_augment: dst must be non-null and 4-byte aligned");
+        CMT_REQUIRE(ptr_aligned(a->workspace, 4), "cmt_pts_augment: workspace must be non-null and 4-byte aligned");
         CMT_REQUIRE(a->workspace_bytes >= cmt_pts_augment_workspace_bytes(n_in),
                     "cmt_pts_augment: workspace below cmt_pts_augment_workspace_bytes(n_in)");
     }
@@ -435,11 +351,11 @@ extern "C" int cmt_boxes_augment(const cmt_boxes_augment_args* a, void* stream) 
     CMT_REQUIRE(a->D == 7 || a->D == 9, "cmt_boxes_augment: D must be 7 or 9");
     CMT_REQUIRE(a->num_classes >= 0, "cmt_boxes_augment: num_classes must not be negative");
     if (const char* e = aug_xform_error(a->xf)) return cmt_fail(CMT_EINVAL, std::string("cmt_boxes_augment: ") + e);
-    CMT_REQUIRE(a->count != nullptr && aug_aligned(a->count, 4), "cmt_boxes_augment: count must be non-null and 4-byte aligned");
+    CMT_REQUIRE(ptr_aligned(a->count, 4), "cmt_boxes_augment: count must be non-null and 4-byte aligned");
     if (a->n > 0) {
-        CMT_REQUIRE(a->boxes && a->out_boxes && aug_aligned(a->boxes, 4) && aug_aligned(a->out_boxes, 4),
+        CMT_REQUIRE(ptr_aligned(a->boxes, 4) && ptr_aligned(a->out_boxes, 4),
                     "cmt_boxes_augment: boxes and out_boxes must be non-null and 4-byte aligned");
-        CMT_REQUIRE(a->labels && a->out_labels && aug_aligned(a->labels, 8) && aug_aligned(a->out_labels, 8),
+        CMT_REQUIRE(ptr_aligned(a->labels, 8) && ptr_aligned(a->out_labels, 8),
                     "cmt_boxes_augment: labels and out_labels must be non-null and 8-byte aligned");
     }
     box_p p;

@@ -3,26 +3,20 @@
 // remove_close, the float64 sweep transform, the time column, the column selection, the float32 agent
 // transform and the strict range filter of include/cmt_hip.h, as an order-preserving stream compaction.
 //
-// Two launches, no workgroup waits for another.  A workgroup owns a tile of PTS_T consecutive rows; a
-// thread owns PTS_R of them, row c * 64 + lane of chunk c = r * 4 + wave, so a wave's 64 lanes hold 64
-// consecutive rows and input order is (chunk, lane) order.
-//   pts_count_kernel:   evaluates every row of the tile and stores the tile's kept count in the workspace.
-//   pts_scatter_kernel: sums the counts of the tiles before its own and of all tiles (every workgroup gets
-//                       the same total), evaluates its rows again with the same function, ranks the kept
-//                       ones (ballot / mbcnt inside a chunk, an LDS prefix over the 16 chunks), writes them
-//                       at their rank and NaN-fills the rows of its own index range at or beyond the total.
-// Scatter targets lie below the total and fill targets at or beyond it, so no element has two writers.
+// Two launches, no workgroup waits for another, over tiles of PTS_T consecutive rows, a wave's 64 lanes on 64
+// consecutive rows (a chunk), with pts_row as the row function of both: the count launch is wave_ops.h's
+// compact_count, the scatter launch keeps its own copy of compact_scatter's body (see pts_scatter_kernel).
 // The segment's parameters stay scalar: a chunk loops over the segments that overlap its 64 rows (one, at
 // a segment boundary two or more) and the rows of that segment are evaluated under the loop.  Rows are read
 // with dword loads (a load_dim = 5 row is 20 bytes).  Contraction is off for the row function (and for the
 // file, see the Makefile): the contract's products and sums are separate roundings.
-#include "cmt_common.h"
+#include "wave_ops.h"
 
 #include <cmath>
 
-constexpr int PTS_T = 1024;           // rows per tile
-constexpr int PTS_THREADS = 256;
-constexpr int PTS_R = PTS_T / PTS_THREADS;
+constexpr int PTS_T = TILE_T;         // rows per tile
+constexpr int PTS_THREADS = TILE_THREADS;
+constexpr int PTS_R = TILE_R;
 constexpr int PTS_CHUNKS = PTS_T / 64;
 
 struct pts_p {
@@ -90,6 +84,9 @@ __device__ __forceinline__ bool pts_eval(const pts_p& p, const cmt_pts_segment& 
     return keep;
 }
 
+// the first row of row i's chunk, as a scalar: the 64 lanes of a wave hold one chunk
+__device__ __forceinline__ unsigned pts_chunk(unsigned i) { return (unsigned)__builtin_amdgcn_readfirstlane((int)(i & ~63u)); }
+
 // row i of the chunk that starts at row c0 (wave-uniform): false for a row at or beyond n
 __device__ __forceinline__ bool pts_row(const pts_p& p, unsigned c0, unsigned i, float (&o)[8]) {
     bool keep = false;
@@ -102,30 +99,14 @@ __device__ __forceinline__ bool pts_row(const pts_p& p, unsigned c0, unsigned i,
     return keep;
 }
 
-__device__ __forceinline__ int pts_wave_sum(int v) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
 __global__ __launch_bounds__(PTS_THREADS) void pts_count_kernel(pts_p p) {
-    __shared__ int part[PTS_THREADS / 64];
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const unsigned t0 = blockIdx.x * (unsigned)PTS_T;
-    int kept = 0;
-#pragma unroll
-    for (int r = 0; r < PTS_R; ++r) {
-        const unsigned c0 = t0 + (unsigned)((r * 4 + w) * 64);
-        float o[8];
-        const bool keep = pts_row(p, c0, c0 + (unsigned)lane, o);
-        kept += __popcll(__ballot(keep));
-    }
-    if (lane == 0) part[w] = kept;
-    __syncthreads();
-    if (threadIdx.x == 0) p.tile_cnt[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
+    compact_count(p.tile_cnt, [&](unsigned i, float (&o)[8]) { return pts_row(p, pts_chunk(i), i, o); });
 }
 
+// Its own copy of compact_scatter's body (wave_ops.h), kept on purpose: on the shared body pts_row's per-chunk scalar
+// state (the segment loop of four chunks) stays live across the barrier and the kernel's SGPR spills go from 38 to 108,
+// which costs the two launches about a microsecond.  Here the chunk table is walked in chunk order and a chunk is
+// stored as the walk reaches it.  Same contract: rank, bounded store g < n, NaN tail, one writer of *count.
 __global__ __launch_bounds__(PTS_THREADS) void pts_scatter_kernel(pts_p p) {
     __shared__ int part[2][PTS_THREADS / 64];
     __shared__ int chunk[PTS_CHUNKS];
@@ -138,8 +119,8 @@ __global__ __launch_bounds__(PTS_THREADS) void pts_scatter_kernel(pts_p p) {
         total += c;
         before += t < b ? c : 0;
     }
-    before = pts_wave_sum(before);
-    total = pts_wave_sum(total);
+    before = wave_sum(before);
+    total = wave_sum(total);
     if (lane == 0) part[0][w] = before, part[1][w] = total;
 
     const unsigned t0 = (unsigned)b * (unsigned)PTS_T;
@@ -153,7 +134,7 @@ __global__ __launch_bounds__(PTS_THREADS) void pts_scatter_kernel(pts_p p) {
         const unsigned c0 = t0 + (unsigned)((r * 4 + w) * 64);
         keep[r] = pts_row(p, c0, c0 + (unsigned)lane, o[r]);
         const unsigned long long m = __ballot(keep[r]);
-        rank[r] = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+        rank[r] = wave_rank(m);
         if (lane == 0) chunk[r * 4 + w] = __popcll(m);
     }
     __syncthreads();
@@ -161,7 +142,6 @@ __global__ __launch_bounds__(PTS_THREADS) void pts_scatter_kernel(pts_p p) {
     total = part[1][0] + part[1][1] + part[1][2] + part[1][3];
     if (b == 0 && threadIdx.x == 0) *p.count = total;
 
-    const unsigned nan32 = 0x7fc00000u;
     int run = before;   // kept rows in front of chunk c
 #pragma unroll
     for (int c = 0; c < PTS_CHUNKS; ++c) {
@@ -179,7 +159,7 @@ __global__ __launch_bounds__(PTS_THREADS) void pts_scatter_kernel(pts_p p) {
                 unsigned* q = (unsigned*)p.dst + (int64_t)i * p.F;
 #pragma unroll
                 for (int j = 0; j < 8; ++j)
-                    if (j < p.F) q[j] = nan32;
+                    if (j < p.F) q[j] = QNAN32;
             }
         }
         run += chunk[c];
@@ -226,11 +206,11 @@ extern "C" int cmt_pts_prepare(const cmt_pts_prepare_args* a, void* stream) {
         for (int k = 0; k < 3; ++k) CMT_REQUIRE(a->range[k] < a->range[3 + k], "cmt_pts_prepare: range min must be below max");
     }
     CMT_REQUIRE(a->count != nullptr, "cmt_pts_prepare: count must be non-null");
-    CMT_REQUIRE((((uintptr_t)a->count) & 3) == 0, "cmt_pts_prepare: count must be 4-byte aligned");
+    CMT_REQUIRE(ptr_aligned_or_null(a->count, 4), "cmt_pts_prepare: count must be 4-byte aligned");
     const int64_t need = cmt_pts_prepare_workspace_bytes(a->n_total);
     if (a->n_total > 0) {
         CMT_REQUIRE(a->src && a->dst && a->workspace, "cmt_pts_prepare: src, dst and workspace must be non-null");
-        CMT_REQUIRE(((((uintptr_t)a->src) | ((uintptr_t)a->dst) | ((uintptr_t)a->workspace)) & 3) == 0,
+        CMT_REQUIRE(ptr_aligned_or_null(a->src, 4) && ptr_aligned_or_null(a->dst, 4) && ptr_aligned_or_null(a->workspace, 4),
                     "cmt_pts_prepare: src, dst and workspace must be 4-byte aligned");
         CMT_REQUIRE(a->workspace_bytes >= need, "cmt_pts_prepare: workspace below cmt_pts_prepare_workspace_bytes(n_total)");
     }

@@ -8,7 +8,7 @@
 // These are latency kernels: a frame has about 100 tracks and 300 boxes, the caps are 512 and 1024.  Everything
 // that needs a total order (the live list, the free-slot list, the birth ranks) runs in ONE workgroup of 256
 // threads: entry e = it * 256 + tid, so the 64 lanes of a wave hold 64 consecutive entries, a ballot / mbcnt
-// gives the rank inside them and an LDS table of at most 16 words the entries before (trk_scan).  No atomics:
+// gives the rank inside them and an LDS table of at most 16 words the entries before (tile_rank of wave_ops.h).  No atomics:
 // the results are bitwise repeatable.  The cost matrix is a launch of its own over tiles of 16 rows x 256
 // columns: at the caps it is 512 K elements, 2048 per thread of one workgroup, while as tiles it is one
 // short wave of workgroups; it needs the predicted state and the live list complete, which the launch boundary
@@ -16,45 +16,14 @@
 // and position are the same in every lane (scalar loads).  Tiles at or beyond n_live rows or n_det columns
 // return at once: the counts come from lsap_desc in device memory, the grid is sized by T and D alone.
 // The file is built with -ffp-contract=off: every product and sum of the contract is rounded on its own.
-#include "cmt_common.h"
+#include "box_rigid.h"
+#include "wave_ops.h"
 
 constexpr int TRK_THREADS = 256;
 constexpr int TRK_T_ITERS = CMT_TRACK_MAX_TRACKS / TRK_THREADS;   // 2
 constexpr int TRK_D_ITERS = CMT_TRACK_MAX_DETS / TRK_THREADS;     // 4
 constexpr int TRK_ROWS = 16;                                      // rows of a cost tile
 static_assert(CMT_TRACK_MAX_TRACKS % TRK_THREADS == 0 && CMT_TRACK_MAX_DETS % TRK_THREADS == 0, "whole passes");
-
-__device__ __forceinline__ int trk_wave_rank(unsigned long long m) {
-    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-}
-__device__ __forceinline__ bool trk_finite(float v) { return __builtin_fabsf(v) < __builtin_inff(); }
-__device__ __forceinline__ int trk_clampi(long long v, int hi) { return v < 0 ? 0 : (v > hi ? hi : (int)v); }
-
-// Ordered compaction by one workgroup: flag[it] belongs to entry it * 256 + tid; rank[it] becomes the number of
-// flagged entries before it, the return value their total.  tab: ITERS * 4 LDS words.  Every thread calls it.
-template <int ITERS>
-__device__ __forceinline__ int trk_scan(const bool (&flag)[ITERS], int (&rank)[ITERS], int* tab) {
-    const int lane = (int)threadIdx.x & 63, w = (int)threadIdx.x >> 6;
-    __syncthreads();   // the table's previous use has been read
-#pragma unroll
-    for (int it = 0; it < ITERS; ++it) {
-        const unsigned long long m = __ballot(flag[it]);
-        rank[it] = trk_wave_rank(m);
-        if (lane == 0) tab[it * 4 + w] = __popcll(m);
-    }
-    __syncthreads();
-    int total = 0;
-#pragma unroll
-    for (int it = 0; it < ITERS; ++it) {
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            const int c = tab[it * 4 + v];
-            if (v == w) rank[it] += total;
-            total += c;
-        }
-    }
-    return total;
-}
 
 // ---- cmt_track_predict ---------------------------------------------------------------------------------------
 struct trp_p {
@@ -94,28 +63,16 @@ __global__ __launch_bounds__(TRK_THREADS) void track_predict_kernel(trp_p p) {
 #pragma clang fp contract(off)
     __shared__ int tab[TRK_T_ITERS * 4];
     const int tid = (int)threadIdx.x;
-    int n_det = p.D;
-    if (p.count) {
-        const int c = *p.count;
-        n_det = c < 0 ? 0 : (c > p.D ? p.D : c);
-    }
+    const int n_det = clamp_count(p.count, p.D);
     for (int j = tid; j < p.D; j += TRK_THREADS) {
         const float* q = p.det + (int64_t)j * p.ld;
         float o[9];
 #pragma unroll
         for (int k = 0; k < 9; ++k) o[k] = q[k];
         if (p.has_pose) {
-            const float x = o[0], y = o[1], z = o[2], vx = o[7], vy = o[8];
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                const float m0 = p.m[4 * a] * x, m1 = p.m[4 * a + 1] * y, m2 = p.m[4 * a + 2] * z;
-                const float s01 = m0 + m1;
-                const float s012 = s01 + m2;
-                o[a] = s012 + p.m[4 * a + 3];
-            }
-            const float a0 = p.m[0] * vx, a1 = p.m[1] * vy, b0 = p.m[4] * vx, b1 = p.m[5] * vy;
-            o[7] = a0 + a1;
-            o[8] = b0 + b1;
+            float pos[3], vel[2];
+            box_rigid(p.m, o[0], o[1], o[2], o[7], o[8], pos, vel);
+            o[0] = pos[0], o[1] = pos[1], o[2] = pos[2], o[7] = vel[0], o[8] = vel[1];
             float yaw = o[6] + p.pose_yaw;
             if (yaw >= 3.1415927f) yaw = yaw - 6.2831855f;
             else if (yaw < -3.1415927f) yaw = yaw + 6.2831855f;
@@ -126,7 +83,7 @@ __global__ __launch_bounds__(TRK_THREADS) void track_predict_kernel(trp_p p) {
 #pragma unroll
         for (int k = 0; k < 9; ++k) {
             d[k] = o[k];
-            fin = fin && trk_finite(o[k]);
+            fin = fin && finite32(o[k]);
         }
         const int lab = p.labels[j];
         p.det_ok[j] = (j < n_det && fin && lab >= 0 && lab < p.ncls && p.scores[j] >= p.score_thr) ? 1 : 0;
@@ -145,7 +102,7 @@ __global__ __launch_bounds__(TRK_THREADS) void track_predict_kernel(trp_p p) {
             p.trk_i[s * 8 + 4] += 1;
         }
     }
-    const int n_live = trk_scan<TRK_T_ITERS>(alive, rank, tab);
+    const int n_live = tile_rank<TRK_T_ITERS>(alive, rank, tab);
 #pragma unroll
     for (int it = 0; it < TRK_T_ITERS; ++it)
         if (alive[it]) p.live[rank[it]] = it * TRK_THREADS + tid;
@@ -154,7 +111,7 @@ __global__ __launch_bounds__(TRK_THREADS) void track_predict_kernel(trp_p p) {
 
 __global__ __launch_bounds__(TRK_THREADS) void track_cost_kernel(trp_p p) {
 #pragma clang fp contract(off)
-    const int n_live = trk_clampi(p.desc[1], p.T), n_det = trk_clampi(p.desc[2], p.D);
+    const int n_live = clamp_index(p.desc[1], p.T), n_det = clamp_index(p.desc[2], p.D);
     const int r0 = (int)blockIdx.y * TRK_ROWS;
     const int j = (int)blockIdx.x * TRK_THREADS + (int)threadIdx.x;
     if (r0 >= n_live || j >= n_det) return;
@@ -236,7 +193,7 @@ __global__ __launch_bounds__(TRK_THREADS) void track_update_kernel(tru_p p) {
     __shared__ int slot_match[CMT_TRACK_MAX_TRACKS];   // the detection matched to a slot or -1
     __shared__ int dslot[CMT_TRACK_MAX_DETS];          // the slot matched to a detection or -1
     const int tid = (int)threadIdx.x;
-    const int n_live_in = trk_clampi(p.desc[1], p.T), n_det = trk_clampi(p.desc[2], p.D);
+    const int n_live_in = clamp_index(p.desc[1], p.T), n_det = clamp_index(p.desc[2], p.D);
     const int next_id = p.counters[1], dropped = p.counters[2], frames = p.counters[3];
     bool tf[TRK_T_ITERS];
     int trank[TRK_T_ITERS];
@@ -249,7 +206,7 @@ __global__ __launch_bounds__(TRK_THREADS) void track_update_kernel(tru_p p) {
         slot_match[s] = -1;
     }
     for (int j = tid; j < CMT_TRACK_MAX_DETS; j += TRK_THREADS) dslot[j] = -1;
-    int n_live = trk_scan<TRK_T_ITERS>(tf, trank, tab);
+    int n_live = tile_rank<TRK_T_ITERS>(tf, trank, tab);
 #pragma unroll
     for (int it = 0; it < TRK_T_ITERS; ++it)
         if (tf[it]) list[trank[it]] = it * TRK_THREADS + tid;
@@ -295,7 +252,7 @@ __global__ __launch_bounds__(TRK_THREADS) void track_update_kernel(tru_p p) {
         }
         tf[it] = s < p.T && id[it] < 0;
     }
-    const int n_free = trk_scan<TRK_T_ITERS>(tf, trank, tab);   // its first barrier: list has been read
+    const int n_free = tile_rank<TRK_T_ITERS>(tf, trank, tab);   // its first barrier: list has been read
 #pragma unroll
     for (int it = 0; it < TRK_T_ITERS; ++it)
         if (tf[it]) list[trank[it]] = it * TRK_THREADS + tid;
@@ -307,7 +264,7 @@ __global__ __launch_bounds__(TRK_THREADS) void track_update_kernel(tru_p p) {
         const int j = it * TRK_THREADS + tid;
         df[it] = j < n_det && p.det_ok[j] != 0 && dslot[j] < 0 && p.scores[j] >= p.birth_thr;
     }
-    const int n_born = trk_scan<TRK_D_ITERS>(df, drank, tab);   // its barriers: the free-slot list is written
+    const int n_born = tile_rank<TRK_D_ITERS>(df, drank, tab);   // its barriers: the free-slot list is written
 #pragma unroll
     for (int it = 0; it < TRK_D_ITERS; ++it) {
         const int j = it * TRK_THREADS + tid;
@@ -352,22 +309,16 @@ __global__ __launch_bounds__(TRK_THREADS) void track_update_kernel(tru_p p) {
 extern "C" int64_t cmt_track_predict_args_size(void) { return (int64_t)sizeof(cmt_track_predict_args); }
 extern "C" int64_t cmt_track_update_args_size(void) { return (int64_t)sizeof(cmt_track_update_args); }
 
-static inline bool trk_al(const void* q, uintptr_t a) { return q != nullptr && (((uintptr_t)q) & (a - 1)) == 0; }
 static inline bool trk_nonneg(float v) { return std::isfinite(v) && v >= 0.f; }
 static inline bool trk_pos(float v) { return std::isfinite(v) && v > 0.f; }
-
-#define TRK_NOTSUP(cond, msg)                                           \
-    do {                                                                \
-        if (!(cond)) return cmt_fail(CMT_ENOTSUP, std::string(msg));    \
-    } while (0)
 
 extern "C" int cmt_track_predict(const cmt_track_predict_args* a, void* stream) {
     CMT_REQUIRE(a != nullptr, "cmt_track_predict: null argument struct");
     CMT_REQUIRE(a->T >= 1 && a->D >= 1, "cmt_track_predict: T and D must be at least 1");
     CMT_REQUIRE(a->ncls >= 1, "cmt_track_predict: ncls must be at least 1");
-    TRK_NOTSUP(a->T <= CMT_TRACK_MAX_TRACKS, "cmt_track_predict: T above 512 is not supported");
-    TRK_NOTSUP(a->D <= CMT_TRACK_MAX_DETS, "cmt_track_predict: D above 1024 is not supported");
-    TRK_NOTSUP(a->ncls <= CMT_TRACK_MAX_CLASSES, "cmt_track_predict: ncls above 32 is not supported");
+    CMT_REQUIRE_SUPPORTED(a->T <= CMT_TRACK_MAX_TRACKS, "cmt_track_predict: T above 512 is not supported");
+    CMT_REQUIRE_SUPPORTED(a->D <= CMT_TRACK_MAX_DETS, "cmt_track_predict: D above 1024 is not supported");
+    CMT_REQUIRE_SUPPORTED(a->ncls <= CMT_TRACK_MAX_CLASSES, "cmt_track_predict: ncls above 32 is not supported");
     CMT_REQUIRE(a->ld >= 9, "cmt_track_predict: ld must be at least 9");
     CMT_REQUIRE(trk_nonneg(a->dt), "cmt_track_predict: dt must be finite and not negative");
     CMT_REQUIRE(trk_nonneg(a->q_pos) && trk_nonneg(a->q_vel), "cmt_track_predict: q_pos and q_vel must be finite and not negative");
@@ -377,11 +328,11 @@ extern "C" int cmt_track_predict(const cmt_track_predict_args* a, void* stream) 
         for (int k = 0; k < 12; ++k) fin = fin && std::isfinite(a->pose[k]);
         CMT_REQUIRE(fin, "cmt_track_predict: pose and pose_yaw must be finite");
     }
-    CMT_REQUIRE(trk_al(a->trk_f, 4) && trk_al(a->trk_i, 4), "cmt_track_predict: the state (trk_f, trk_i) must be non-null and 4-byte aligned");
-    CMT_REQUIRE(trk_al(a->det, 4) && trk_al(a->scores, 4) && trk_al(a->labels, 4) && trk_al(a->gate2, 4),
+    CMT_REQUIRE(ptr_aligned(a->trk_f, 4) && ptr_aligned(a->trk_i, 4), "cmt_track_predict: the state (trk_f, trk_i) must be non-null and 4-byte aligned");
+    CMT_REQUIRE(ptr_aligned(a->det, 4) && ptr_aligned(a->scores, 4) && ptr_aligned(a->labels, 4) && ptr_aligned(a->gate2, 4),
                 "cmt_track_predict: det, scores, labels and gate2 must be non-null and 4-byte aligned");
-    CMT_REQUIRE(a->count == nullptr || trk_al(a->count, 4), "cmt_track_predict: count must be 4-byte aligned");
-    CMT_REQUIRE(trk_al(a->det_w, 4) && trk_al(a->det_ok, 4) && trk_al(a->live, 4) && trk_al(a->cost, 4) && trk_al(a->lsap_desc, 8),
+    CMT_REQUIRE(ptr_aligned_or_null(a->count, 4), "cmt_track_predict: count must be 4-byte aligned");
+    CMT_REQUIRE(ptr_aligned(a->det_w, 4) && ptr_aligned(a->det_ok, 4) && ptr_aligned(a->live, 4) && ptr_aligned(a->cost, 4) && ptr_aligned(a->lsap_desc, 8),
                 "cmt_track_predict: det_w, det_ok, live, cost (4 bytes) and lsap_desc (8 bytes) must be non-null and aligned");
     trp_p p;
     p.trk_f = (float*)a->trk_f, p.trk_i = a->trk_i;
@@ -402,20 +353,20 @@ extern "C" int cmt_track_update(const cmt_track_update_args* a, void* stream) {
     CMT_REQUIRE(a != nullptr, "cmt_track_update: null argument struct");
     CMT_REQUIRE(a->T >= 1 && a->D >= 1, "cmt_track_update: T and D must be at least 1");
     CMT_REQUIRE(a->H >= 1, "cmt_track_update: H must be at least 1");
-    TRK_NOTSUP(a->T <= CMT_TRACK_MAX_TRACKS, "cmt_track_update: T above 512 is not supported");
-    TRK_NOTSUP(a->D <= CMT_TRACK_MAX_DETS, "cmt_track_update: D above 1024 is not supported");
-    TRK_NOTSUP(a->H <= CMT_TRACK_MAX_HISTORY, "cmt_track_update: H above 32 is not supported");
+    CMT_REQUIRE_SUPPORTED(a->T <= CMT_TRACK_MAX_TRACKS, "cmt_track_update: T above 512 is not supported");
+    CMT_REQUIRE_SUPPORTED(a->D <= CMT_TRACK_MAX_DETS, "cmt_track_update: D above 1024 is not supported");
+    CMT_REQUIRE_SUPPORTED(a->H <= CMT_TRACK_MAX_HISTORY, "cmt_track_update: H above 32 is not supported");
     CMT_REQUIRE(a->max_age >= 0, "cmt_track_update: max_age must not be negative");
     CMT_REQUIRE(trk_pos(a->r_pos) && trk_pos(a->r_vel), "cmt_track_update: r_pos and r_vel must be finite and positive");
     CMT_REQUIRE(trk_nonneg(a->p0_pos) && trk_nonneg(a->p0_vel), "cmt_track_update: p0_pos and p0_vel must be finite and not negative");
     CMT_REQUIRE(!std::isnan(a->birth_thr), "cmt_track_update: birth_thr must not be NaN");
-    CMT_REQUIRE(trk_al(a->trk_f, 4) && trk_al(a->trk_i, 4) && trk_al(a->hist, 4) && trk_al(a->counters, 4),
+    CMT_REQUIRE(ptr_aligned(a->trk_f, 4) && ptr_aligned(a->trk_i, 4) && ptr_aligned(a->hist, 4) && ptr_aligned(a->counters, 4),
                 "cmt_track_update: the state (trk_f, trk_i, hist, counters) must be non-null and 4-byte aligned");
-    CMT_REQUIRE(trk_al(a->live, 4) && trk_al(a->lsap_desc, 8) && trk_al(a->cost, 4) && trk_al(a->match_g, 4) && trk_al(a->match_q, 4),
+    CMT_REQUIRE(ptr_aligned(a->live, 4) && ptr_aligned(a->lsap_desc, 8) && ptr_aligned(a->cost, 4) && ptr_aligned(a->match_g, 4) && ptr_aligned(a->match_q, 4),
                 "cmt_track_update: live, cost, match_g, match_q (4 bytes) and lsap_desc (8 bytes) must be non-null and aligned");
-    CMT_REQUIRE(trk_al(a->det_w, 4) && trk_al(a->scores, 4) && trk_al(a->labels, 4) && trk_al(a->det_ok, 4),
+    CMT_REQUIRE(ptr_aligned(a->det_w, 4) && ptr_aligned(a->scores, 4) && ptr_aligned(a->labels, 4) && ptr_aligned(a->det_ok, 4),
                 "cmt_track_update: det_w, scores, labels and det_ok must be non-null and 4-byte aligned");
-    CMT_REQUIRE(trk_al(a->det_track, 4) && trk_al(a->det_slot, 4), "cmt_track_update: det_track and det_slot must be non-null and 4-byte aligned");
+    CMT_REQUIRE(ptr_aligned(a->det_track, 4) && ptr_aligned(a->det_slot, 4), "cmt_track_update: det_track and det_slot must be non-null and 4-byte aligned");
     tru_p p;
     p.trk_f = (float*)a->trk_f, p.trk_i = a->trk_i, p.hist = (float*)a->hist, p.counters = a->counters;
     p.live = a->live, p.desc = (const long long*)a->lsap_desc, p.cost = (const float*)a->cost;

@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from . import native as N
+from ._argcheck import count_word as _count_word, rows as _rows, same_device, tensor
 from .native import _check, _p, _stream, lib
 from .native_pts import PointsWorkspace, _pipeline_steps
 
@@ -92,30 +93,8 @@ def _fill_xform(xf, params, point_cloud_range):
         xf.range[:] = rng.tolist()
 
 
-def _rows(t, name, widths, dtype=torch.float32):
-    if not torch.is_tensor(t) or t.dtype != dtype or t.dim() != 2 or t.shape[1] not in widths:
-        raise ValueError(f"{name} must be a {dtype} [n, c] tensor with c in {list(widths)}, got "
-                         f"{(t.dtype, tuple(t.shape)) if torch.is_tensor(t) else type(t)}")
-    if not t.is_contiguous():
-        raise ValueError(f"{name} must be contiguous rows")
-    return t
-
-
-def _count_word(count, name="count"):
-    if count is None:
-        return None
-    if not torch.is_tensor(count) or count.dtype != torch.int32 or count.numel() != 1:
-        raise ValueError(f"{name} must be a one-element int32 tensor, got "
-                         f"{(count.dtype, tuple(count.shape)) if torch.is_tensor(count) else type(count)}")
-    return count
-
-
 def _on_device(dev, **tensors):
-    if dev.type != "cuda":
-        raise ValueError("tensors must live on a HIP device (no CPU path)")
-    for name, t in tensors.items():
-        if t is not None and t.device != dev:
-            raise ValueError(f"{name} must live on {dev}, got {t.device}")
+    same_device(dev, "tensors must live", **tensors)
 
 
 def points_in_boxes(points, boxes, count=None, want=("box_of_point", "count_per_box")):
@@ -187,10 +166,7 @@ def augment_points(points, params, *, count=None, paste_points=None, paste_boxes
     _fill_xform(a.xf, params, point_cloud_range)
     order = None
     if torch.is_tensor(shuffle):
-        order = shuffle
-        if order.dtype != torch.int32 or tuple(order.shape) != (n_in,) or not order.is_contiguous():
-            raise ValueError(f"an order tensor must be a contiguous int32 [{n_in}] tensor, got "
-                             f"{(order.dtype, tuple(order.shape))}")
+        order = tensor(shuffle, "an order tensor", torch.int32, (n_in,))
     elif not (shuffle is None or isinstance(shuffle, (bool, torch.Generator))):
         raise ValueError(f"shuffle must be None, a bool, a torch.Generator or an int32 order tensor, got {type(shuffle)}")
     dev = points.device

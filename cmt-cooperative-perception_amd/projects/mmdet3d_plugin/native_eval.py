@@ -13,6 +13,7 @@ import math
 
 import torch
 
+from ._argcheck import count_word, rows, same_device, tensor
 from .native import _check, _i64, _int, _p, _stream, _vp, lib
 
 __all__ = ["MAX_CLASSES", "MAX_THRESHOLDS", "MAX_SAMPLES", "MAX_PER_SAMPLE", "NELEM", "DetEvalArgs", "eval_lib",
@@ -105,24 +106,6 @@ def check_config(class_range, yaw_period, dist_ths, dist_th_tp, min_recall, min_
     return rng, per, ths, ths.index(float(dist_th_tp)), first_ind, float(min_precision)
 
 
-def _rows(name, t, dtype, cols=None):
-    shape = "[n]" if cols is None else f"[n, {cols}]"
-    if not torch.is_tensor(t) or t.dtype != dtype or t.dim() != (1 if cols is None else 2) or \
-            (cols is not None and t.shape[1] != cols):
-        raise ValueError(f"{name} must be a {str(dtype).replace('torch.', '')} {shape} tensor, got "
-                         f"{(t.dtype, tuple(t.shape)) if torch.is_tensor(t) else type(t)}")
-    if not t.is_contiguous():
-        raise ValueError(f"{name} must be contiguous")
-    return int(t.shape[0])
-
-
-def _count(name, t):
-    if t is None:
-        return
-    if not torch.is_tensor(t) or t.dtype != torch.int32 or t.numel() != 1:
-        raise ValueError(f"{name} must be one int32 on the device")
-
-
 def det_eval(pred_boxes, pred_scores, pred_labels, pred_samples, gt_boxes, gt_labels, gt_samples, gt_num_pts, *,
              num_samples, class_range, yaw_period, dist_ths, dist_th_tp, min_recall=0.1, min_precision=0.1,
              n_pred=None, n_gt=None, out=None, workspace=None, events=None):
@@ -137,39 +120,32 @@ def det_eval(pred_boxes, pred_scores, pred_labels, pred_samples, gt_boxes, gt_la
     device int32 each, the rows actually filled (default: all).  ``out``: a dict of the seven tensors to write into;
     ``workspace``: a uint8 tensor of at least ``workspace_bytes(N, G, S, C, T)`` bytes.  ``events``: a list that
     receives (phase name, start event, end event) for keys, sort, match and curves (for measurements)."""
-    N = _rows("pred_boxes", pred_boxes, torch.float32, 9)
-    G = _rows("gt_boxes", gt_boxes, torch.float32, 9)
+    N = int(rows(pred_boxes, "pred_boxes", (9,)).shape[0])
+    G = int(rows(gt_boxes, "gt_boxes", (9,)).shape[0])
     for name, t, dt, n in (("pred_scores", pred_scores, torch.float32, N), ("pred_labels", pred_labels, torch.int32, N),
                            ("pred_samples", pred_samples, torch.int32, N), ("gt_labels", gt_labels, torch.int32, G),
                            ("gt_samples", gt_samples, torch.int32, G), ("gt_num_pts", gt_num_pts, torch.int32, G)):
-        if _rows(name, t, dt) < n:
+        if rows(t, name, None, dt).shape[0] < n:
             raise ValueError(f"{name} is short: {t.shape[0]} rows for {n} boxes")
-    _count("n_pred", n_pred)
-    _count("n_gt", n_gt)
+    count_word(n_pred, "n_pred"), count_word(n_gt, "n_gt")
     rng, per, ths, tp_index, first_ind, min_prec = check_config(class_range, yaw_period, dist_ths, dist_th_tp,
                                                                 min_recall, min_precision)
     S, C, T = int(num_samples), len(rng), len(ths)
     _check_dims(N, G, S, C, T)
-    tensors = [pred_boxes, pred_scores, pred_labels, pred_samples, gt_boxes, gt_labels, gt_samples, gt_num_pts]
-    tensors += [t for t in (n_pred, n_gt) if t is not None]
+    tensors = dict(pred_scores=pred_scores, pred_labels=pred_labels, pred_samples=pred_samples, gt_boxes=gt_boxes,
+                   gt_labels=gt_labels, gt_samples=gt_samples, gt_num_pts=gt_num_pts, n_pred=n_pred, n_gt=n_gt)
     shapes = dict(tp=((T, N), torch.uint8), match_gt=((T, N), torch.int32), err=((T, 4, N), torch.float64),
                   npos=((C,), torch.int32), md=((C, T, 7, NELEM), torch.float64), ap=((C, T), torch.float64),
                   tp_err=((C, 4), torch.float64))
     if out is not None:
         for k, (shape, dt) in shapes.items():
-            t = out.get(k)
-            if not torch.is_tensor(t) or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
-                raise ValueError(f"out[{k!r}] must be a contiguous {str(dt).replace('torch.', '')} {shape} tensor")
-            tensors.append(t)
+            tensors[f"out[{k!r}]"] = tensor(out.get(k), f"out[{k!r}]", dt, shape)
     if workspace is not None:
         if not torch.is_tensor(workspace) or workspace.dtype != torch.uint8 or not workspace.is_contiguous():
             raise ValueError("workspace must be a contiguous uint8 tensor")
-        tensors.append(workspace)
-    if any(not t.is_cuda for t in tensors):
-        raise ValueError("detection evaluation needs its tensors on a HIP device (no CPU path)")
+        tensors["workspace"] = workspace
     dev = pred_boxes.device
-    if any(t.device != dev for t in tensors):
-        raise ValueError("all tensors must live on one device")
+    same_device(dev, "detection evaluation needs its tensors", **tensors)
     L = eval_lib()
     need = int(L.cmt_det_eval_workspace_bytes(N, G, S, C, T))
     if workspace is None:

@@ -20,8 +20,9 @@ import numpy as np
 import torch
 
 from . import native as N
+from ._argcheck import count_word as _count_word, rows as _rows, same_device, tensor
 from .native import _check, _p, _stream, lib
-from .native_aug import _SAMPLERS, _count_word, _on_device, _rows
+from .native_aug import _SAMPLERS
 from .native_pts import PointsWorkspace, _pipeline_steps
 
 __all__ = ["MAX_FRAME_BOXES", "MAX_COLLIDE_BOXES", "MAX_PASTE_BOXES", "workspace_bytes", "extract_objects",
@@ -38,11 +39,8 @@ def workspace_bytes(n_points, n_boxes):
     return int(lib().cmt_gtdb_extract_workspace_bytes(int(n_points), int(n_boxes)))
 
 
-def _table(t, name, k):
-    if not torch.is_tensor(t) or t.dtype != torch.int32 or tuple(t.shape) != (k,) or not t.is_contiguous():
-        raise ValueError(f"{name} must be a contiguous int32 [{k}] tensor, got "
-                         f"{(t.dtype, tuple(t.shape)) if torch.is_tensor(t) else type(t)}")
-    return t
+def _on_device(dev, **tensors):
+    same_device(dev, "the database needs tensors", **tensors)
 
 
 def extract_objects(points, boxes, count=None, out=None, workspace=None):
@@ -102,17 +100,14 @@ def gather_objects(rows, seg_offset, seg_len, dst_offset, centre, n_dst, out=Non
     K = int(seg_offset.shape[0])
     if K > MAX_PASTE_BOXES:
         raise ValueError(f"at most {MAX_PASTE_BOXES} segments, got {K}")
-    seg_offset, seg_len, dst_offset = (_table(t, nm, K) for t, nm in ((seg_offset, "seg_offset"), (seg_len, "seg_len"),
-                                                                      (dst_offset, "dst_offset")))
-    if (not torch.is_tensor(centre) or centre.dtype != torch.float32 or tuple(centre.shape) != (K, 3)
-            or not centre.is_contiguous()):
-        raise ValueError(f"centre must be a contiguous fp32 [{K}, 3] tensor")
+    seg_offset, seg_len, dst_offset = (tensor(t, nm, torch.int32, (K,)) for t, nm in (
+        (seg_offset, "seg_offset"), (seg_len, "seg_len"), (dst_offset, "dst_offset")))
+    centre = tensor(centre, "centre", torch.float32, (K, 3))
     n_dst = int(n_dst)
     if n_dst < 0 or n_dst >= 2 ** 31 or rows.shape[0] >= 2 ** 31:
         raise ValueError("n_dst and len(rows) must be in [0, 2^31)")
-    if out is not None and (not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != (n_dst, F)
-                            or not out.is_contiguous()):
-        raise ValueError(f"out must be a contiguous fp32 {(n_dst, F)} tensor")
+    if out is not None:
+        tensor(out, "out", torch.float32, (n_dst, F))
     dev = rows.device
     _on_device(dev, seg_offset=seg_offset, seg_len=seg_len, dst_offset=dst_offset, centre=centre, out=out)
     dst = out if out is not None else torch.empty((n_dst, F), dtype=torch.float32, device=dev)

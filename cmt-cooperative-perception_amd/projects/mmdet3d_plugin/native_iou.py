@@ -10,38 +10,15 @@ there is no CPU fallback.
 import ctypes
 import math
 
-import numpy as np
 import torch
 
 from . import native as N
+from ._argcheck import count_word as _count, nonneg, pose_arguments, same_device, strided_rows, tensor
 from .native import _check, _p, _stream, lib
 
 __all__ = ["NMS_MAX", "CONCAT_MAX", "box_iou", "nms_rotated", "nms_workspace", "concat_detections"]
 
 NMS_MAX, CONCAT_MAX = N.NMS_MAX, N.CONCAT_MAX
-
-
-def _rows(t, name, min_cols=7):
-    """fp32 [n, >= min_cols] with unit column stride -> (n, the row stride)"""
-    if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] < min_cols \
-            or (t.shape[0] > 0 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
-        raise ValueError(f"{name} must be an fp32 [n, >= {min_cols}] tensor with unit column stride, got "
-                         f"{(t.dtype, tuple(t.shape)) if torch.is_tensor(t) else type(t)}")
-    n = int(t.shape[0])
-    return n, int(t.stride(0)) if n > 1 else int(t.shape[1])
-
-
-def _vec(t, name, dtype, n):
-    if not torch.is_tensor(t) or t.dtype != dtype or t.dim() != 1 or int(t.shape[0]) != n or not t.is_contiguous():
-        raise ValueError(f"{name} must be a contiguous {str(dtype).replace('torch.', '')} [{n}] tensor, got "
-                         f"{(t.dtype, tuple(t.shape)) if torch.is_tensor(t) else type(t)}")
-    return t
-
-
-def _count(t, name):
-    if t is not None and (not torch.is_tensor(t) or t.dtype != torch.int32 or t.numel() != 1):
-        raise ValueError(f"{name} must be None or an int32 tensor of one element")
-    return t
 
 
 def _z_origin(z):
@@ -52,11 +29,7 @@ def _z_origin(z):
 
 
 def _on_device(dev, **ts):
-    if dev.type != "cuda":
-        raise ValueError("the box overlap calls need tensors on a HIP device (no CPU fallback)")
-    for name, t in ts.items():
-        if t is not None and t.device != dev:
-            raise ValueError(f"{name} is on {t.device}, the boxes on {dev}")
+    same_device(dev, "the box overlap calls need tensors", **ts)
 
 
 def box_iou(a, b, *, mode="bev", z_origin=0.5, aligned=False, n_a=None, n_b=None, out=None):
@@ -67,8 +40,8 @@ def box_iou(a, b, *, mode="bev", z_origin=0.5, aligned=False, n_a=None, n_b=None
     for 'both' a pair) to write into, [N, >= M] with unit column stride ([N] when aligned)."""
     if mode not in ("bev", "3d", "both"):
         raise ValueError(f"mode must be 'bev', '3d' or 'both', got {mode!r}")
-    n, lda = _rows(a, "a")
-    m, ldb = _rows(b, "b")
+    n, lda = strided_rows(a, "a", 7)
+    m, ldb = strided_rows(b, "b", 7)
     z_origin = _z_origin(z_origin)
     if aligned and n != m:
         raise ValueError(f"aligned needs as many rows in a as in b, got {n} and {m}")
@@ -83,12 +56,11 @@ def box_iou(a, b, *, mode="bev", z_origin=0.5, aligned=False, n_a=None, n_b=None
     ldo = m
     for k, o in enumerate(outs):
         if aligned:
-            _vec(o, "out", torch.float32, n)
+            tensor(o, "out", torch.float32, (n,))
         else:
-            if not torch.is_tensor(o) or o.dtype != torch.float32 or o.dim() != 2 or o.shape[0] != n or o.shape[1] < m \
-                    or (o.numel() > 0 and o.stride(1) != 1) or (n > 1 and o.stride(0) < o.shape[1]):
-                raise ValueError(f"out must be fp32 [{n}, >= {m}] with unit column stride")
-            ld = int(o.stride(0)) if n > 1 else int(o.shape[1])
+            rows, ld = strided_rows(o, "out", m, rows=n)
+            if rows != n:
+                raise ValueError(f"out must have {n} rows, got {rows}")
             if k and ld != ldo:
                 raise ValueError("the two outputs must have the same row stride")
             ldo = ld
@@ -124,22 +96,20 @@ def nms_rotated(boxes, scores, iou_thr, *, labels=None, count=None, score_thr=-m
     None or a device int32, the valid rows.  Rows below ``score_thr`` or with a NaN score do not take part.
     ``use_3d``: suppress by the 3D IoU instead of the BEV IoU.  ``work``: the tensor of ``nms_workspace(N, device)``
     (allocated when None).  ``keep``: an optional uint8 or int32 [N] tensor that receives the 0 / 1 flags."""
-    n, ld = _rows(boxes, "boxes")
+    n, ld = strided_rows(boxes, "boxes", 7)
     if n > NMS_MAX:
         raise ValueError(f"rotated NMS takes at most {NMS_MAX} rows, got {n}")
-    scores = _vec(scores, "scores", torch.float32, n)
+    scores = tensor(scores, "scores", torch.float32, (n,))
     if labels is not None:
-        labels = _vec(labels, "labels", torch.int32, n)
+        labels = tensor(labels, "labels", torch.int32, (n,))
     _count(count, "count")
-    iou_thr, score_thr, z_origin = float(iou_thr), float(score_thr), _z_origin(z_origin)
-    if not math.isfinite(iou_thr) or iou_thr < 0:
-        raise ValueError(f"iou_thr must be finite and not negative, got {iou_thr}")
+    iou_thr, score_thr, z_origin = nonneg(iou_thr, "iou_thr"), float(score_thr), _z_origin(z_origin)
     if math.isnan(score_thr):
         raise ValueError("score_thr must not be NaN")
     if keep is not None:
         if not torch.is_tensor(keep) or keep.dtype not in (torch.uint8, torch.int32):
             raise ValueError("keep must be a uint8 or int32 tensor")
-        _vec(keep, "keep", keep.dtype, n)
+        tensor(keep, "keep", keep.dtype, (n,))
     dev = boxes.device
     _on_device(dev, scores=scores, labels=labels, count=count, work=work, keep=keep)
     need = int(lib().cmt_box_nms_workspace_bytes(n))
@@ -162,10 +132,7 @@ def nms_rotated(boxes, scores, iou_thr, *, labels=None, count=None, score_thr=-m
 
 def transform_arguments(pose):
     """A 4 x 4 (or 3 x 4) rigid transform -> its 12 floats, row-major [R|t]"""
-    m = np.asarray(pose.detach().cpu().numpy() if torch.is_tensor(pose) else pose, dtype=np.float64)
-    if m.shape not in ((4, 4), (3, 4)) or not np.isfinite(m).all():
-        raise ValueError(f"a pose must be a finite 4 x 4 (or 3 x 4) matrix, got shape {m.shape}")
-    return [float(v) for v in m[:3].reshape(-1)]
+    return pose_arguments(pose)[0]
 
 
 def concat_detections(sources, poses=None, *, cols=None):
@@ -191,9 +158,9 @@ def concat_detections(sources, poses=None, *, cols=None):
             raise ValueError(f"source {k} must be (boxes, scores, labels[, count])")
         boxes, scores, labels = src[:3]
         count = src[3] if len(src) == 4 else None
-        n, ld = _rows(boxes, f"boxes of source {k}")
-        scores = _vec(scores, f"scores of source {k}", torch.float32, n)
-        labels = _vec(labels, f"labels of source {k}", torch.int32, n)
+        n, ld = strided_rows(boxes, f"boxes of source {k}", 7)
+        scores = tensor(scores, f"scores of source {k}", torch.float32, (n,))
+        labels = tensor(labels, f"labels of source {k}", torch.int32, (n,))
         _count(count, f"count of source {k}")
         dev = boxes.device if dev is None else dev
         _on_device(dev, boxes=boxes, scores=scores, labels=labels, count=count)

@@ -18,6 +18,8 @@ import numpy as np
 import torch
 
 from . import native as N
+from ._argcheck import (count_word, nonneg as _nonneg, pose_arguments, positive as _positive, same_device, strided_rows,
+                        tensor as _t)
 from .native import _check, _p, _stream, lib
 
 __all__ = ["MAX_TRACKS", "MAX_DETS", "MAX_HISTORY", "MAX_CLASSES", "BIG", "MAX_GATE2", "new_state", "track_predict",
@@ -29,36 +31,8 @@ BIG = N.TRACK_BIG
 MAX_GATE2 = 1.0e5      # a squared gate must stay below it: every gated cost is then far below BIG
 
 
-def _t(t, name, dtype, shape):
-    """a contiguous tensor of the dtype and shape (None in ``shape``: any extent)"""
-    if (not torch.is_tensor(t) or t.dtype != dtype or t.dim() != len(shape) or not t.is_contiguous()
-            or any(w is not None and int(g) != w for g, w in zip(t.shape, shape))):
-        want = "[" + ", ".join("n" if w is None else str(w) for w in shape) + "]"
-        raise ValueError(f"{name} must be a contiguous {str(dtype).replace('torch.', '')} {want} tensor, got "
-                         f"{(t.dtype, tuple(t.shape)) if torch.is_tensor(t) else type(t)}")
-    return t
-
-
 def _same_device(dev, **ts):
-    if dev.type != "cuda":
-        raise ValueError("the tracker needs tensors on a HIP device (no CPU fallback)")
-    for name, t in ts.items():
-        if t is not None and t.device != dev:
-            raise ValueError(f"{name} is on {t.device}, the state on {dev}")
-
-
-def _nonneg(v, name):
-    v = float(v)
-    if not math.isfinite(v) or v < 0:
-        raise ValueError(f"{name} must be finite and not negative, got {v}")
-    return v
-
-
-def _positive(v, name):
-    v = float(v)
-    if not math.isfinite(v) or v <= 0:
-        raise ValueError(f"{name} must be finite and positive, got {v}")
-    return v
+    same_device(dev, "the tracker needs tensors", **ts)
 
 
 def _caps(T, D, H=None, ncls=None):
@@ -94,15 +68,6 @@ def _state(state, need_hist):
     return trk_f, trk_i, hist, counters, T
 
 
-def pose_arguments(pose):
-    """A 4 x 4 (or 3 x 4) rigid pose -> (12 floats row-major [R|t], pose_yaw): ``pose_yaw = atan2(R10, R00)`` in
-    float64, rounded once to float32."""
-    m = np.asarray(pose, dtype=np.float64)
-    if m.shape not in ((4, 4), (3, 4)) or not np.isfinite(m).all():
-        raise ValueError(f"pose must be a finite 4 x 4 (or 3 x 4) matrix, got shape {m.shape}")
-    return [float(v) for v in m[:3].reshape(-1)], float(np.float32(math.atan2(m[1, 0], m[0, 0])))
-
-
 def track_predict(state, det, scores, labels, count, gate2, work, *, dt, q_pos, q_vel, score_thr, pose=None,
                   gate2_host=None):
     """cmt_track_predict.  ``state``: the dict of ``new_state``; ``det`` fp32 [D, >= 9] (rows may be a view with a
@@ -112,18 +77,13 @@ def track_predict(state, det, scores, labels, count, gate2, work, *, dt, q_pos, 
     ``work``: dict(det_w [D, 9] fp32, det_ok [D] int32, live [T] int32, cost [T, D] fp32, lsap_desc [1, 4] int64), all
     written.  No host read with ``gate2_host`` given."""
     trk_f, trk_i, _, _, T = _state(state, False)
-    if not torch.is_tensor(det) or det.dtype != torch.float32 or det.dim() != 2 or det.shape[1] < 9 or det.stride(1) != 1 \
-            or (det.shape[0] > 1 and det.stride(0) < det.shape[1]):
-        raise ValueError("det must be an fp32 [D, >= 9] tensor with unit column stride")
-    D = int(det.shape[0])
+    D, ld = strided_rows(det, "det", 9, rows="D")
     gate2 = _t(gate2, "gate2", torch.float32, (None,))
     ncls = int(gate2.shape[0])
     _caps(T, D, None, ncls)
     scores = _t(scores, "scores", torch.float32, (D,))
     labels = _t(labels, "labels", torch.int32, (D,))
-    if count is not None:
-        if not torch.is_tensor(count) or count.dtype != torch.int32 or count.numel() != 1:
-            raise ValueError("count must be None or an int32 tensor of one element")
+    count_word(count)
     g = np.asarray(gate2.cpu() if gate2_host is None else gate2_host, dtype=np.float64).reshape(-1)
     if g.shape[0] != ncls or not np.isfinite(g).all() or (g < 0).any() or (g >= MAX_GATE2).any():
         raise ValueError(f"gate2 needs {ncls} finite entries in [0, {MAX_GATE2:g})")
@@ -144,7 +104,7 @@ def track_predict(state, det, scores, labels, count, gate2, work, *, dt, q_pos, 
     dev = trk_f.device
     _same_device(dev, trk_i=trk_i, det=det, scores=scores, labels=labels, count=count, gate2=gate2, det_w=det_w,
                  det_ok=det_ok, live=live, cost=cost, lsap_desc=desc)
-    a.T, a.D, a.ld, a.ncls = T, D, int(det.stride(0)) if D > 1 else int(det.shape[1]), ncls
+    a.T, a.D, a.ld, a.ncls = T, D, ld, ncls
     a.dt, a.q_pos, a.q_vel, a.score_thr = dt, q_pos, q_vel, float(score_thr)
     a.trk_f, a.trk_i, a.det, a.scores, a.labels, a.count = _p(trk_f), _p(trk_i), _p(det), _p(scores), _p(labels), _p(count)
     a.gate2, a.det_w, a.det_ok, a.live, a.cost, a.lsap_desc = _p(gate2), _p(det_w), _p(det_ok), _p(live), _p(cost), _p(desc)
@@ -296,15 +256,12 @@ class Tracker:
         if self.frames == 0:
             dt = 0.0   # nothing to move yet
         D, dev = self.max_dets, self.device
-        if not torch.is_tensor(boxes) or boxes.dtype != torch.float32 or boxes.dim() != 2 or boxes.shape[1] < 9 \
-                or boxes.stride(1) != 1 or (boxes.shape[0] > 1 and boxes.stride(0) < boxes.shape[1]):
-            raise ValueError("boxes must be an fp32 [max_dets, >= 9] tensor with unit column stride")
-        if boxes.shape[0] != D:
+        n, ld = strided_rows(boxes, "boxes", 9, rows="max_dets")
+        if n != D:
             raise ValueError(f"boxes must have max_dets = {D} rows, got {boxes.shape[0]}")
         scores = _t(scores, "scores", torch.float32, (D,))
         labels = _t(labels, "labels", torch.int32, (D,))
-        if count is not None and (not torch.is_tensor(count) or count.dtype != torch.int32 or count.numel() != 1):
-            raise ValueError("count must be None or an int32 tensor of one element")
+        count_word(count)
         _same_device(dev, boxes=boxes, scores=scores, labels=labels, count=count)
         pa, ua, L, stream = self._predict, self._update, lib(), _stream()
         pa.has_pose = 0
@@ -313,7 +270,7 @@ class Tracker:
             pa.has_pose = 1
             for k in range(12):
                 pa.pose[k] = m[k]
-        pa.dt, pa.ld = dt, int(boxes.stride(0)) if D > 1 else int(boxes.shape[1])
+        pa.dt, pa.ld = dt, ld
         pa.det, pa.scores, pa.labels, pa.count = _p(boxes), _p(scores), _p(labels), _p(count)
         ua.scores, ua.labels = pa.scores, pa.labels
         _check(L.cmt_track_predict(ctypes.byref(pa), stream), "cmt_track_predict")

@@ -5,7 +5,8 @@
 
 Kernels are matched on their demangled names; --rename rewrites OLD's names first (for template
 arguments a refactor removed, e.g. 'gemm_x3_kernel<256, =gemm_x3_kernel<').  For every kernel:
-instruction count old -> new, VGPR / AGPR / scratch / LDS from the kernel descriptor, and
+instruction count old -> new, VGPR / AGPR / scratch / LDS from the kernel descriptor, SGPR and VGPR
+spill counts from the metadata, s_barrier count, and
 'identical' or the number of differing lines once .LBB label numbers are normalised.  For a kernel
 that differs, 'k loop' says whether the ordered sequence of MFMA, ds_read, LDS-DMA and s_waitcnt
 instructions (mnemonics and wait counts, no registers) inside its loops that hold MFMAs is the
@@ -69,6 +70,13 @@ def parse(path):
         # .LBB<function>_<block> -> numbered in order of first appearance inside the kernel
         s = re.sub(r"\.LBB\d+_\d+", lambda m: labels.setdefault(m.group(0), "L%d" % len(labels)), s)
         kernels[cur]["body"].append(re.sub(r"\s+", " ", s))
+    name = None                                # the metadata's spill counts (.name comes before them in an entry)
+    for raw in open(path, errors="replace"):
+        m = re.match(r"^\s+(?:- )?\.(name|sgpr_spill_count|vgpr_spill_count):\s+(\S+)", raw)
+        if m and m.group(1) == "name":
+            name = m.group(2)
+        elif m and name in kernels:
+            kernels[name]["desc"][m.group(1)] = int(m.group(2))
     return {k: v for k, v in kernels.items() if v["desc"]}
 
 
@@ -80,6 +88,10 @@ def regs(d):
 
 def insts(body):
     return [l for l in body if not l.endswith(":")]
+
+
+def barriers(body):
+    return sum(1 for l in body if l.split(" ", 1)[0] == "s_barrier")
 
 
 def pipe(body):
@@ -137,8 +149,11 @@ def main():
             continue
         o, w = old[on[n]], new[nn[n]]
         ro, rw = regs(o["desc"]), regs(w["desc"])
-        head = "%6d -> %6d  vgpr %3d -> %3d  agpr %3d -> %3d  scratch %d -> %d  lds %6d -> %6d" % (
-            len(insts(o["body"])), len(insts(w["body"])), ro[0], rw[0], ro[1], rw[1], ro[2], rw[2], ro[3], rw[3])
+        head = "%6d -> %6d  vgpr %3d -> %3d  agpr %3d -> %3d  scratch %d -> %d  spills s %d -> %d v %d -> %d  lds %6d -> %6d  barriers %d -> %d" % (
+            len(insts(o["body"])), len(insts(w["body"])), ro[0], rw[0], ro[1], rw[1], ro[2], rw[2],
+            o["desc"].get("sgpr_spill_count", 0), w["desc"].get("sgpr_spill_count", 0),
+            o["desc"].get("vgpr_spill_count", 0), w["desc"].get("vgpr_spill_count", 0), ro[3], rw[3],
+            barriers(o["body"]), barriers(w["body"]))
         if o["body"] == w["body"]:
             same += 1
             rows.append((n, head + "  identical"))

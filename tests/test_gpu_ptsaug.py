@@ -298,6 +298,24 @@ def test_aug_every_row_dropped(dev):
     assert c == 0 and np.all(words == R.QNAN)
 
 
+def test_aug_more_tiles_than_threads(dev):
+    """257 tiles and one slot, one kept row per tile and the last: a thread of the scatter launch sums more than
+    one entry of the tiles' counts"""
+    T = _T()
+    n = 257 * T + 1
+    keep = np.zeros(n, bool)
+    keep[T - 1::T] = True
+    keep[-1] = True
+    src = np.zeros((n, 4), np.float32)
+    src[:, 0] = np.where(keep, 1.0, 100.0)      # inside RANGE where kept
+    src[:, 1] = (np.arange(n) % 61) * 0.5 - 15
+    src[:, 2] = -1.0
+    src[:, 3] = np.arange(n)
+    words, c = _aug(dev, src, {}, rng=RANGE)
+    assert c == 258
+    assert np.array_equal(words[:c, 3].view(np.float32), np.flatnonzero(keep).astype(np.float32))   # input order
+
+
 def test_aug_workspace_reuse(dev):
     """two different calls through one workspace, nothing cleaned between them; a caller's dirty tensor"""
     rng = np.random.default_rng(25)

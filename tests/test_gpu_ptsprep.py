@@ -221,6 +221,19 @@ def test_keep_patterns(dev, pattern):
         assert np.all(words == R.QNAN)
 
 
+def test_more_tiles_than_threads(dev):
+    """257 tiles and one row: a thread of the scatter launch sums more than one entry of the tiles' counts"""
+    T = _T()
+    n = 257 * T + 1
+    keep = np.zeros(n, bool)
+    keep[T - 1::T] = True
+    keep[-1] = True
+    p = _pattern_rows(n, keep)[:, :4].copy()
+    words, c = _run_and_check(dev, [R.seg(p)], [0, 1, 2, 3], 4, None, RANGE)
+    assert c == 258
+    assert np.array_equal(words[:c, 3].view(np.float32), np.flatnonzero(keep).astype(np.float32))   # input order
+
+
 # ---- edges -------------------------------------------------------------------------------------------------------
 def test_range_faces(dev):
     """a coordinate exactly on one of the six faces drops the row, the next float inside keeps it"""
