@@ -18,6 +18,14 @@
 //                     integer block scan of tp (exact) with the order-preserving compaction of the matches,
 //                     the two 101-point resamplings by binary search, per error the NaN-aware cumulative mean
 //                     as a fixed-tree float64 scan and the reversed resampling, then calc_ap / calc_tp.
+//   det_match_iou_kernel  the same wave per (sample, class) with the rotated-box IoU of box_overlap.h (float32, the
+//                     ground truth as the first box) in place of the centre distance and the largest value in place
+//                     of the smallest.  The derived box of the lane's first ground truth stays in registers, the
+//                     prediction's is derived once per prediction, the clip runs once per (prediction, lane) in the
+//                     lane's LDS slot; the thresholds differ only in the taken mask.
+//   det_ap_interp_kernel  one workgroup per (class, threshold): the precision envelope at the matches as a reverse
+//                     running maximum, then the all-point AP and the 40-point AP as serial sums.
+#include "box_overlap.h"
 #include "wave_ops.h"
 
 #include <cmath>
@@ -50,7 +58,16 @@ struct det_p {
     int* ws_ctp;             // [T][N] running tp count
     int* ws_mpos;            // [T][N] class-run position of the m-th match
     unsigned char* ws_taken; // [G] taken bits of ground truth beyond the first 64 of a (sample, class)
+    float* match_iou;        // [T][N], the IoU match only (else null)
 };
+
+struct det_iou_p {
+    float th[CMT_DET_MAX_THRESHOLDS];
+    float z_origin;
+    int use_3d;
+    double* ap_interp;
+};
+static_assert(DET_THREADS == BI_THREADS, "a lane of the match workgroup owns one clip slot");
 
 __device__ __forceinline__ double det_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
 
@@ -132,6 +149,7 @@ __device__ __forceinline__ void det_write_miss(const det_p& p, int t, int64_t i)
     p.match_gt[(int64_t)t * p.N + i] = -1;
 #pragma unroll
     for (int e = 0; e < 4; ++e) p.err[((int64_t)t * 4 + e) * p.N + i] = det_nan();
+    if (p.match_iou) p.match_iou[(int64_t)t * p.N + i] = __uint_as_float(QNAN32);
 }
 
 __device__ __forceinline__ int det_block_sum(int v, int* part) {
@@ -144,29 +162,34 @@ __device__ __forceinline__ int det_block_sum(int v, int* part) {
     return s;
 }
 
+// the workgroups behind the matching ones, x = 0 ..: C that count npos, DET_FILL_BLOCKS that fill the rows of
+// predictions that take no part
+__device__ __forceinline__ void det_match_rest(const det_p& p, int64_t x, int* part) {
+    if (x < p.C) {   // npos of class x: kept ground truth sorts in front of the rest
+        int n = 0;
+        for (int64_t j = threadIdx.x; j < p.G; j += DET_THREADS) {
+            const int64_t k = p.sk_gt[j];
+            n += (k != DET_NONE && (int)(k & 63) == (int)x) ? 1 : 0;
+        }
+        n = det_block_sum(n, part);
+        if (threadIdx.x == 0) p.npos[x] = n;
+    } else {         // rows of predictions that take no part: they sort behind every kept one
+        const int64_t first = det_lower_bound(p.sk_sample, p.N, DET_NONE);
+        for (int64_t q = first + (x - p.C) * DET_THREADS + threadIdx.x; q < p.N;
+             q += (int64_t)DET_FILL_BLOCKS * DET_THREADS) {
+            const int64_t i = p.N - 1 - p.si_sample[q];
+            for (int t = 0; t < p.T; ++t) det_write_miss(p, t, i);
+        }
+    }
+}
+
 __global__ __launch_bounds__(DET_THREADS) void det_match_kernel(det_p p) {
     __shared__ int part[DET_WAVES];
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int64_t b = blockIdx.x;
     if (b >= p.match_blocks) {
-        const int64_t x = b - p.match_blocks;
-        if (x < p.C) {   // npos of class x: kept ground truth sorts in front of the rest
-            int n = 0;
-            for (int64_t j = threadIdx.x; j < p.G; j += DET_THREADS) {
-                const int64_t k = p.sk_gt[j];
-                n += (k != DET_NONE && (int)(k & 63) == (int)x) ? 1 : 0;
-            }
-            n = det_block_sum(n, part);
-            if (threadIdx.x == 0) p.npos[x] = n;
-        } else {         // rows of predictions that take no part: they sort behind every kept one
-            const int64_t first = det_lower_bound(p.sk_sample, p.N, DET_NONE);
-            for (int64_t q = first + (x - p.C) * DET_THREADS + threadIdx.x; q < p.N;
-                 q += (int64_t)DET_FILL_BLOCKS * DET_THREADS) {
-                const int64_t i = p.N - 1 - p.si_sample[q];
-                for (int t = 0; t < p.T; ++t) det_write_miss(p, t, i);
-            }
-        }
+        det_match_rest(p, b - p.match_blocks, part);
         return;
     }
     const int64_t pair = b * DET_WAVES + w;
@@ -249,6 +272,113 @@ __global__ __launch_bounds__(DET_THREADS) void det_match_kernel(det_p p) {
     }
 }
 
+// ---- the IoU match --------------------------------------------------------------------------------------
+
+// ~bits(iou) of ground truth Gt (the first box: the pair is clipped in its frame) and prediction P: iou >= 0, so
+// ascending in this key is descending in the value.  An invalid box on either side gives 0, and so does a NaN
+// quotient (0 / 0 of extents whose products underflow).  px, py: the lane's clip slot.
+__device__ __forceinline__ uint32_t det_iou_key(const bi_box& Gt, const bi_box& P, int use_3d, float* px, float* py) {
+    float v = 0.f;
+    if (Gt.ok && P.ok) {
+        float area, h;
+        bi_pair(Gt, P, px, py, area, h);
+        v = use_3d ? bi_3d(Gt, P, area, h) : bi_bev(Gt, P, area);
+        if (!(v == v)) v = 0.f;
+    }
+    return ~__float_as_uint(v);
+}
+
+__global__ __launch_bounds__(DET_THREADS) void det_match_iou_kernel(det_p p, det_iou_p q) {
+    __shared__ float px[2 * BI_SLOT], py[2 * BI_SLOT];
+    __shared__ int part[DET_WAVES];
+    const int tid = (int)threadIdx.x;
+    const int lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int64_t b = blockIdx.x;
+    if (b >= p.match_blocks) {
+        det_match_rest(p, b - p.match_blocks, part);
+        return;
+    }
+    const int64_t pair = b * DET_WAVES + w;
+    if (pair >= (int64_t)p.S * p.C) return;
+    const int c = (int)(pair % p.C);
+    const int64_t sc = ((pair / p.C) << 6) | (int64_t)c;
+    const int64_t g0 = det_lower_bound(p.sk_gt, p.G, sc), g1 = det_lower_bound(p.sk_gt, p.G, sc + 1);
+    const int64_t p0 = det_lower_bound(p.sk_sample, p.N, sc << 32), p1 = det_lower_bound(p.sk_sample, p.N, (sc + 1) << 32);
+    const int ng = (int)(g1 - g0);
+    const int chunks = (ng + 63) >> 6;
+    float* sx = px + tid;
+    float* sy = py + tid;
+
+    const bool have0 = lane < ng;
+    const bi_box G0 = have0 ? bi_derive(p.gbox + p.si_gt[g0 + lane] * 9, q.z_origin) : bi_none();
+    unsigned taken0 = 0;
+    for (int k = 1; k < chunks; ++k)
+        if (k * 64 + lane < ng) p.ws_taken[g0 + k * 64 + lane] = 0;
+
+    for (int64_t v = p0; v < p1; ++v) {
+        const int64_t i = p.N - 1 - p.si_sample[v];
+        const bi_box P = bi_derive(p.pbox + i * 9, q.z_origin);
+        uint32_t bk[CMT_DET_MAX_THRESHOLDS];
+        int bpos[CMT_DET_MAX_THRESHOLDS];
+#pragma unroll
+        for (int t = 0; t < CMT_DET_MAX_THRESHOLDS; ++t) bk[t] = ~0u, bpos[t] = INT32_MAX;
+        if (have0) {
+            const uint32_t key = det_iou_key(G0, P, q.use_3d, sx, sy);
+#pragma unroll
+            for (int t = 0; t < CMT_DET_MAX_THRESHOLDS; ++t)
+                if (t < p.T && !((taken0 >> t) & 1u)) bk[t] = key, bpos[t] = lane;
+        }
+        for (int k = 1; k < chunks; ++k) {
+            const int pos = k * 64 + lane;
+            if (pos < ng) {
+                const bi_box Gk = bi_derive(p.gbox + p.si_gt[g0 + pos] * 9, q.z_origin);
+                const unsigned tk = p.ws_taken[g0 + pos];
+                const uint32_t key = det_iou_key(Gk, P, q.use_3d, sx, sy);
+#pragma unroll
+                for (int t = 0; t < CMT_DET_MAX_THRESHOLDS; ++t)   // strict, or the first candidate: the lowest index stays
+                    if (t < p.T && !((tk >> t) & 1u) && (key < bk[t] || bpos[t] == INT32_MAX)) bk[t] = key, bpos[t] = pos;
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < CMT_DET_MAX_THRESHOLDS; ++t) {
+            if (t < p.T) {
+                uint32_t k = bk[t];
+                int pos = bpos[t];
+#pragma unroll
+                for (int d = 32; d > 0; d >>= 1) {
+                    const uint32_t ok = (uint32_t)__shfl_xor((int)k, d, 64);
+                    const int op = __shfl_xor(pos, d, 64);
+                    if (ok < k || (ok == k && op < pos)) k = ok, pos = op;
+                }
+                const float iou = __uint_as_float(~k);
+                const bool match = pos != INT32_MAX && iou > q.th[t];
+                if (match) {
+                    if ((pos & 63) == lane) {   // the owner of the winner
+                        if (pos < 64)
+                            taken0 |= 1u << t;
+                        else
+                            p.ws_taken[g0 + pos] = (unsigned char)(p.ws_taken[g0 + pos] | (1u << t));
+                        const int64_t row = p.si_gt[g0 + pos];
+                        const double dx = (double)p.pbox[i * 9] - (double)p.gbox[row * 9];
+                        const double dy = (double)p.pbox[i * 9 + 1] - (double)p.gbox[row * 9 + 1];
+                        const double xx = dx * dx, yy = dy * dy;
+                        double e[4];
+                        det_errors(p, i, row, c, sqrt(xx + yy), e);
+                        p.tp[(int64_t)t * p.N + i] = 1;
+                        p.match_gt[(int64_t)t * p.N + i] = (int)row;
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) p.err[((int64_t)t * 4 + j) * p.N + i] = e[j];
+                        if (p.match_iou) p.match_iou[(int64_t)t * p.N + i] = iou;
+                    }
+                } else if (lane == 0) {
+                    det_write_miss(p, t, i);
+                }
+            }
+        }
+    }
+}
+
 // ---- curves -------------------------------------------------------------------------------------------
 
 // inclusive scan over the workgroup's DET_CHUNK terms, thread-major: v[] in, inclusive prefix out; returns the
@@ -275,6 +405,36 @@ __device__ __forceinline__ V det_block_scan(V (&v)[DET_PER], V* part) {
 #pragma unroll
     for (int j = 0; j < DET_PER; ++j) v[j] = base + v[j];
     return total;
+}
+
+// The running tp count ctp[0 .. n) and the positions mpos[0 .. M) of the matches of one (class, threshold), in
+// visiting order (si: the class's run of the class-major order); returns M.  Integer block scans: exact.  Ends with
+// a barrier, so every thread may read both arrays.
+__device__ __forceinline__ int det_scan_tp(const det_p& p, const unsigned char* tp, const int64_t* si, int64_t n, int* ctp,
+                                           int* mpos, int* ipart) {
+    int M = 0;
+    for (int64_t base = 0; base < n; base += DET_CHUNK) {
+        int v[DET_PER];
+        unsigned hit = 0;
+        const int64_t j0 = base + (int64_t)threadIdx.x * DET_PER;
+#pragma unroll
+        for (int j = 0; j < DET_PER; ++j) {
+            v[j] = j0 + j < n ? (int)(tp[p.N - 1 - si[j0 + j]] != 0) : 0;
+            hit |= (unsigned)v[j] << j;
+        }
+        const int total = det_block_scan(v, ipart);
+#pragma unroll
+        for (int j = 0; j < DET_PER; ++j) {
+            if (j0 + j < n) {
+                const int inc = M + v[j];
+                ctp[j0 + j] = inc;
+                if ((hit >> j) & 1u) mpos[inc - 1] = (int)(j0 + j);
+            }
+        }
+        M += total;
+    }
+    __syncthreads();
+    return M;
 }
 
 __device__ __forceinline__ void det_no_predictions(const det_p& p, int c, int t, double* md) {
@@ -307,29 +467,7 @@ __global__ __launch_bounds__(DET_THREADS) void det_curve_kernel(det_p p) {
     double* cm = p.ws_cm + (int64_t)t * p.N + a;
     const unsigned char* tp = p.tp + (int64_t)t * p.N;
 
-    // running tp count and the positions of the matches, in visiting order
-    int M = 0;
-    for (int64_t base = 0; base < n; base += DET_CHUNK) {
-        int v[DET_PER];
-        unsigned hit = 0;
-        const int64_t j0 = base + (int64_t)threadIdx.x * DET_PER;
-#pragma unroll
-        for (int j = 0; j < DET_PER; ++j) {
-            v[j] = j0 + j < n ? (int)(tp[p.N - 1 - si[j0 + j]] != 0) : 0;
-            hit |= (unsigned)v[j] << j;
-        }
-        const int total = det_block_scan(v, ipart);
-#pragma unroll
-        for (int j = 0; j < DET_PER; ++j) {
-            if (j0 + j < n) {
-                const int inc = M + v[j];
-                ctp[j0 + j] = inc;
-                if ((hit >> j) & 1u) mpos[inc - 1] = (int)(j0 + j);
-            }
-        }
-        M += total;
-    }
-    __syncthreads();
+    const int M = det_scan_tp(p, tp, si, n, ctp, mpos, ipart);
     if (npos == 0 || M == 0) {
         det_no_predictions(p, c, t, md);
         return;
@@ -458,6 +596,88 @@ __global__ __launch_bounds__(DET_THREADS) void det_curve_kernel(det_p p) {
     }
 }
 
+// ---- interpolated APs ---------------------------------------------------------------------------------
+// env[j] = max over k >= j of prec[k] is only read at the matches, and between two matches prec falls (the count
+// stays, the position grows), so env[pos(m)] = max over m' >= m of m' / (pos(m') + 1): a reverse running maximum over
+// the M matches.  A maximum selects, it does not round: any tree gives the same bits.  It is kept in the workspace
+// slot of the curves' cumulative mean.
+__global__ __launch_bounds__(DET_THREADS) void det_ap_interp_kernel(det_p p, det_iou_p q) {
+    __shared__ int ipart[DET_WAVES];
+    __shared__ double dpart[DET_WAVES];
+    __shared__ double stage[DET_CHUNK];
+    const int tid = (int)threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int c = (int)blockIdx.x / p.T, t = (int)blockIdx.x % p.T;
+    const int64_t a = det_lower_bound(p.sk_class, p.N, (int64_t)c << 32);
+    const int64_t n = det_lower_bound(p.sk_class, p.N, (int64_t)(c + 1) << 32) - a;
+    const int npos = p.npos[c];
+    int* ctp = p.ws_ctp + (int64_t)t * p.N + a;
+    int* mpos = p.ws_mpos + (int64_t)t * p.N + a;
+    double* env = p.ws_cm + (int64_t)t * p.N + a;
+    double* out = q.ap_interp + ((int64_t)c * p.T + t) * 2;
+    const int M = det_scan_tp(p, p.tp + (int64_t)t * p.N, p.si_class + a, n, ctp, mpos, ipart);
+    if (npos == 0 || M == 0) {
+        if (tid == 0) out[0] = 0.0, out[1] = 0.0;
+        return;
+    }
+    // from the last match backwards: term r is match M - 1 - r, the (M - r)-th
+    double carry = 0.0;   // precisions are positive
+    for (int base = 0; base < M; base += DET_CHUNK) {
+        double v[DET_PER];
+        const int r0 = base + tid * DET_PER;
+#pragma unroll
+        for (int j = 0; j < DET_PER; ++j) {
+            const int r = r0 + j;
+            v[j] = r < M ? (double)(M - r) / (double)(mpos[M - 1 - r] + 1) : 0.0;
+        }
+#pragma unroll
+        for (int j = 1; j < DET_PER; ++j) v[j] = fmax(v[j - 1], v[j]);
+        double run = v[DET_PER - 1];
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const double o = wave_shfl_up(run, d);
+            if (lane >= d) run = fmax(o, run);
+        }
+        __syncthreads();   // dpart may still be read from the chunk before
+        if (lane == 63) dpart[w] = run;
+        __syncthreads();
+        double before = 0.0, total = 0.0;
+#pragma unroll
+        for (int k = 0; k < DET_WAVES; ++k) {
+            if (k == w) before = total;
+            total = fmax(total, dpart[k]);
+        }
+        double tb = wave_shfl_up(run, 1);
+        if (lane == 0) tb = 0.0;
+        const double behind = fmax(carry, fmax(before, tb));
+#pragma unroll
+        for (int j = 0; j < DET_PER; ++j) {
+            const int r = r0 + j;
+            if (r < M) env[M - 1 - r] = fmax(behind, v[j]);
+        }
+        carry = fmax(carry, total);
+    }
+    __syncthreads();
+    // the serial sum in match order: one thread adds, all of them stage its terms in LDS
+    double s = 0.0;
+    for (int base = 0; base < M; base += DET_CHUNK) {
+        const int cnt = M - base < DET_CHUNK ? M - base : DET_CHUNK;
+        for (int k = tid; k < cnt; k += DET_THREADS) stage[k] = env[base + k];
+        __syncthreads();
+        if (tid == 0)
+            for (int k = 0; k < cnt; ++k) s = s + stage[k];
+        __syncthreads();
+    }
+    if (tid == 0) {
+        out[0] = s / (double)npos;
+        double r40 = 0.0;
+        for (int k = 1; k <= 40; ++k) {
+            const int64_t m = ((int64_t)k * npos + 39) / 40;   // the smallest m with m * 40 >= k * npos
+            r40 = r40 + (m <= (int64_t)M ? env[m - 1] : 0.0);
+        }
+        out[1] = r40 / 40.0;
+    }
+}
+
 // ---- entry points -------------------------------------------------------------------------------------
 
 extern "C" int64_t cmt_det_eval_args_size(void) { return (int64_t)sizeof(cmt_det_eval_args); }
@@ -512,6 +732,20 @@ static int det_fill(const cmt_det_eval_args* a, det_p& p, const char* who) {
     p.ws_ctp = (int*)(ws + tn * 8);
     p.ws_mpos = (int*)(ws + tn * 12);
     p.ws_taken = (unsigned char*)(ws + tn * 16);
+    p.match_iou = nullptr;
+    return 0;
+}
+
+static int det_iou_fill(const cmt_det_eval_args* a, const cmt_det_iou_args* ia, det_iou_p& q, const char* who) {
+    const std::string w(who);
+    CMT_REQUIRE(ia != nullptr, w + ": null IoU argument struct");
+    CMT_REQUIRE(ia->mode == 0 || ia->mode == 1, w + ": mode must be 0 (BEV) or 1 (3D)");
+    CMT_REQUIRE(ia->z_origin == 0.f || ia->z_origin == 0.5f, w + ": z_origin must be 0 or 0.5");
+    for (int t = 0; t < a->T; ++t)
+        CMT_REQUIRE(std::isfinite(ia->iou_th[t]) && ia->iou_th[t] >= 0.f && ia->iou_th[t] < 1.f, w + ": iou_th must be in [0, 1)");
+    for (int t = 0; t < CMT_DET_MAX_THRESHOLDS; ++t) q.th[t] = ia->iou_th[t < a->T ? t : 0];
+    q.z_origin = ia->z_origin, q.use_3d = ia->mode;
+    q.ap_interp = (double*)ia->ap_interp;
     return 0;
 }
 
@@ -557,6 +791,37 @@ extern "C" int cmt_det_eval_match(const cmt_det_eval_args* a, void* stream) {
     const int64_t blocks = p.match_blocks + a->C + DET_FILL_BLOCKS;
     CMT_REQUIRE(blocks < ((int64_t)1 << 31), std::string(who) + ": S * C too large for one launch");
     det_match_kernel<<<dim3((unsigned)blocks), DET_THREADS, 0, (hipStream_t)stream>>>(p);
+    return cmt_check_launch(who);
+}
+
+extern "C" int64_t cmt_det_iou_args_size(void) { return (int64_t)sizeof(cmt_det_iou_args); }
+
+extern "C" int cmt_det_eval_match_iou(const cmt_det_eval_args* a, const cmt_det_iou_args* ia, void* stream) {
+    const char* who = "cmt_det_eval_match_iou";
+    det_p p;
+    det_iou_p q;
+    if (int rc = det_fill(a, p, who)) return rc;
+    if (int rc = det_iou_fill(a, ia, q, who)) return rc;
+    if (int rc = det_check_inputs(a, who)) return rc;
+    if (int rc = det_check_sorted(a, who)) return rc;
+    CMT_REQUIRE(ptr_aligned_or_null(ia->match_iou, 4), std::string(who) + ": match_iou must be 4-byte aligned");
+    p.match_iou = (float*)ia->match_iou;
+    const int64_t blocks = p.match_blocks + a->C + DET_FILL_BLOCKS;
+    CMT_REQUIRE(blocks < ((int64_t)1 << 31), std::string(who) + ": S * C too large for one launch");
+    det_match_iou_kernel<<<dim3((unsigned)blocks), DET_THREADS, 0, (hipStream_t)stream>>>(p, q);
+    return cmt_check_launch(who);
+}
+
+extern "C" int cmt_det_eval_ap_interp(const cmt_det_eval_args* a, const cmt_det_iou_args* ia, void* stream) {
+    const char* who = "cmt_det_eval_ap_interp";
+    det_p p;
+    det_iou_p q;
+    if (int rc = det_fill(a, p, who)) return rc;
+    if (int rc = det_iou_fill(a, ia, q, who)) return rc;
+    if (int rc = det_check_inputs(a, who)) return rc;
+    if (int rc = det_check_sorted(a, who)) return rc;
+    CMT_REQUIRE(ptr_aligned(ia->ap_interp, 8), std::string(who) + ": ap_interp must be non-null and 8-byte aligned");
+    det_ap_interp_kernel<<<dim3((unsigned)(a->C * a->T)), DET_THREADS, 0, (hipStream_t)stream>>>(p, q);
     return cmt_check_launch(who);
 }
 

@@ -5,10 +5,14 @@ evaluator the reference carries in its dataset class (a9coop_dataset.py: accumul
 filter_eval_boxes, _evaluate_a9_nusc).  ``DetectionEvaluator`` collects frames in device buffers without a host
 read; ``compute()`` runs sort -> match -> curves on the device and reads back C x T APs and C x 4 errors, the means
 over them (nine classes, four numbers each) are float64 on the host.
+
+``IouDetectionEvaluator`` is the same collector scored by overlap (``cmt_det_eval_match_iou``: the largest BEV or 3D
+IoU above a threshold, KITTI / VOC style) with the all-point and 40-point APs of ``cmt_det_eval_ap_interp`` next to the
+101-point one.
 """
 import math
 from dataclasses import dataclass
-from typing import Sequence
+from typing import Optional, Sequence
 
 import numpy as np
 import torch
@@ -16,7 +20,8 @@ import torch
 from ... import native_eval as NE
 
 __all__ = ["DetEvalConfig", "tumtraf_eval_config", "nuscenes_eval_config", "DetectionEvaluator", "summarize", "TUMTRAF_CLASSES",
-           "TP_METRICS", "ERR_NAME_MAPPING"]
+           "TP_METRICS", "ERR_NAME_MAPPING", "IouEvalConfig", "tumtraf_iou_config", "IouDetectionEvaluator", "summarize_iou",
+           "NO_RANGE"]
 
 TUMTRAF_CLASSES = ("CAR", "TRAILER", "TRUCK", "VAN", "PEDESTRIAN", "BUS", "MOTORCYCLE", "BICYCLE", "EMERGENCY_VEHICLE")
 _TUMTRAF_RANGE = {"CAR": 50, "TRUCK": 50, "BUS": 50, "TRAILER": 50, "VAN": 50, "EMERGENCY_VEHICLE": 50,
@@ -107,9 +112,11 @@ class DetectionEvaluator:
     ``capacity_frames`` frames of at most ``cfg.max_boxes_per_sample`` predictions fit; the prediction buffers are
     allocated once, ``add`` copies into them on the device and reads nothing back."""
 
-    def __init__(self, cfg: DetEvalConfig, capacity_frames: int, device):
-        if not isinstance(cfg, DetEvalConfig):
-            raise ValueError("cfg must be a DetEvalConfig")
+    config_type = DetEvalConfig
+
+    def __init__(self, cfg, capacity_frames: int, device):
+        if not isinstance(cfg, self.config_type):
+            raise ValueError(f"cfg must be a {self.config_type.__name__}")
         if not 1 <= int(capacity_frames) <= NE.MAX_SAMPLES:
             raise ValueError(f"capacity_frames must be in [1, 2^24], got {capacity_frames}")
         self.cfg = cfg
@@ -212,19 +219,23 @@ class DetectionEvaluator:
 
     def run(self, events=None):
         """sort -> match -> curves on the device -> the dict of device tensors of ``native_eval.det_eval``"""
+        cfg = self.cfg
+        self._result = NE.det_eval(*self._rows_on_device(), num_samples=self._frames, class_range=cfg.class_range,
+                                   yaw_period=cfg.yaw_period, dist_ths=cfg.dist_ths, dist_th_tp=cfg.dist_th_tp,
+                                   min_recall=cfg.min_recall, min_precision=cfg.min_precision, events=events)
+        return self._result
+
+    def _rows_on_device(self):
+        """the eight tensors of ``native_eval.det_eval``: the filled prediction rows and the concatenated ground truth"""
         if self._frames == 0:
             raise ValueError("no frame was added")
-        dev, cfg = self.device, self.cfg
         if self._gt_cat is None:
             self._gt_cat = tuple(torch.cat([g[k] for g in self._gt]).contiguous() for k in range(4))
-        gb, gl, gs, gn = self._gt_cat
-        n = self._n
-        buf = self._buf
-        self._result = NE.det_eval(buf["box"][:n], buf["score"][:n], buf["label"][:n], buf["sample"][:n], gb, gl, gs, gn,
-                                   num_samples=self._frames, class_range=cfg.class_range, yaw_period=cfg.yaw_period,
-                                   dist_ths=cfg.dist_ths, dist_th_tp=cfg.dist_th_tp, min_recall=cfg.min_recall,
-                                   min_precision=cfg.min_precision, events=events)
-        return self._result
+        n, buf = self._n, self._buf
+        return (buf["box"][:n], buf["score"][:n], buf["label"][:n], buf["sample"][:n]) + self._gt_cat
+
+    def _thresholds(self):
+        return self.cfg.dist_ths
 
     def compute(self):
         """The reference's metrics_summary: label_aps, mean_dist_aps, mean_ap, label_tp_errors, tp_errors,
@@ -256,6 +267,116 @@ class DetectionEvaluator:
         md = res["md"].cpu().numpy()
         out = dict()
         for c, name in enumerate(self.cfg.class_names):
-            for k, th in enumerate(self.cfg.dist_ths):
+            for k, th in enumerate(self._thresholds()):
                 out[name + ":" + str(float(th))] = {cn: md[c, k, i].tolist() for i, cn in enumerate(CURVE_NAMES)}
         return out
+
+
+# ---- IoU-matched AP -------------------------------------------------------------------------------------------
+NO_RANGE = 1.0e9   # class_range=None: no range filter (the contract wants a finite range; non-finite centres still drop)
+
+
+@dataclass
+class IouEvalConfig:
+    """The constants of the IoU-matched evaluation (cmt_det_eval_match_iou in include/cmt_hip.h): a prediction
+    matches the unclaimed ground truth of largest BEV or 3D IoU above ``iou_ths[t]``.  ``class_range`` None: no
+    range filter; ``yaw_period`` None: 2 pi for every class."""
+    class_names: Sequence[str]
+    iou_ths: Sequence[float] = (0.1, 0.25, 0.5, 0.7)
+    iou_th_tp: float = 0.5
+    mode: str = "3d"
+    z_origin: float = 0.5
+    class_range: Optional[Sequence[float]] = None
+    yaw_period: Optional[Sequence[float]] = None
+    min_recall: float = 0.1
+    min_precision: float = 0.1
+    max_boxes_per_sample: int = 500
+    gt_velocity_zero: bool = False
+
+    def __post_init__(self):
+        self.class_names = tuple(self.class_names)
+        C = len(self.class_names)
+        self.class_range = [NO_RANGE] * C if self.class_range is None else [float(v) for v in self.class_range]
+        self.yaw_period = [2 * math.pi] * C if self.yaw_period is None else [float(v) for v in self.yaw_period]
+        if len(self.class_range) != C:
+            raise ValueError(f"{C} class names but {len(self.class_range)} class ranges")
+        self.iou_ths = tuple(float(t) for t in self.iou_ths)
+        NE.check_iou_config(self.class_range, self.yaw_period, self.iou_ths, self.iou_th_tp, self.mode, self.z_origin,
+                            self.min_recall, self.min_precision)
+        if not 1 <= int(self.max_boxes_per_sample) <= NE.MAX_PER_SAMPLE:
+            raise ValueError(f"max_boxes_per_sample must be in [1, {NE.MAX_PER_SAMPLE}], got {self.max_boxes_per_sample}")
+
+
+def tumtraf_iou_config(class_names=TUMTRAF_CLASSES, mode="3d"):
+    """Plain defaults for the TUMTraf classes: 3D IoU thresholds 0.1 / 0.25 / 0.5 / 0.7, TP errors and the mean
+    matched IoU at 0.5, boxes with the centre at half height, no range filter, ground-truth velocity zero.  These are
+    settings of this package: they are not taken from, and have not been compared with, the TUMTraf devkit."""
+    return IouEvalConfig(class_names=tuple(class_names), mode=mode, gt_velocity_zero=True)
+
+
+def summarize_iou(cfg, ap, ap_interp, tp_err, mean_iou):
+    """The metrics dictionary from ap [C, T] (the 101-point AP of the reused curves), ap_interp [C, T, 2] (all-point,
+    40-point), tp_err [C, 4] (columns trans, vel, scale, orient; at ``iou_th_tp``) and the mean matched IoU [C] (NaN for
+    a class without a match), in float64 on the host."""
+    ap, ai = np.asarray(ap, dtype=np.float64), np.asarray(ap_interp, dtype=np.float64)
+    tp_err, mean_iou = np.asarray(tp_err, dtype=np.float64), np.asarray(mean_iou, dtype=np.float64)
+    col = {n: i for i, n in enumerate(NE.ERR_NAMES)}
+    label_aps = {n: {t: dict(ap_all=float(ai[c, k, 0]), ap_r40=float(ai[c, k, 1]), ap_101=float(ap[c, k]))
+                     for k, t in enumerate(cfg.iou_ths)} for c, n in enumerate(cfg.class_names)}
+    mean_aps = {n: {m: float(np.mean([d[t][m] for t in cfg.iou_ths])) for m in ("ap_all", "ap_r40", "ap_101")}
+                for n, d in label_aps.items()}
+    label_tp = {n: {m: float(tp_err[c, col[m]]) for m in TP_METRICS} for c, n in enumerate(cfg.class_names)}
+    out = dict(label_aps=label_aps, mean_aps=mean_aps)
+    for m in ("all", "r40", "101"):
+        out["map_" + m] = float(np.mean([mean_aps[n]["ap_" + m] for n in cfg.class_names]))
+    out.update(label_tp_errors=label_tp,
+               tp_errors={m: float(np.nanmean([label_tp[n][m] for n in cfg.class_names])) for m in TP_METRICS},
+               label_mean_iou={n: float(mean_iou[c]) for c, n in enumerate(cfg.class_names)},
+               iou_ths=list(cfg.iou_ths), iou_th_tp=float(cfg.iou_th_tp), mode=cfg.mode)
+    return out
+
+
+class IouDetectionEvaluator(DetectionEvaluator):
+    """``DetectionEvaluator`` (the same ``add`` / ``reset`` and buffers) scored by overlap: per class and IoU threshold
+    the all-point AP, the 40-point AP and the nuScenes-style 101-point AP, their means, the four TP errors and the
+    mean matched IoU at ``cfg.iou_th_tp``."""
+    config_type = IouEvalConfig
+
+    def run(self, events=None):
+        """sort -> IoU match -> curves -> interpolated APs -> the dict of ``native_eval.det_eval_iou``"""
+        cfg = self.cfg
+        self._result = NE.det_eval_iou(*self._rows_on_device(), num_samples=self._frames, class_range=cfg.class_range,
+                                       yaw_period=cfg.yaw_period, iou_ths=cfg.iou_ths, iou_th_tp=cfg.iou_th_tp,
+                                       mode=cfg.mode, z_origin=cfg.z_origin, min_recall=cfg.min_recall,
+                                       min_precision=cfg.min_precision, events=events)
+        return self._result
+
+    def _thresholds(self):
+        return self.cfg.iou_ths
+
+    def _mean_matched_iou(self, res):
+        """per class the mean of match_iou over the matches at iou_th_tp (float64 sums on the device; NaN: none)"""
+        k = self.cfg.iou_ths.index(float(self.cfg.iou_th_tp))
+        v, lab = res["match_iou"][k].double(), self._buf["label"][:self._n]
+        hit = ~torch.isnan(v)
+        sums = [torch.where(hit & (lab == c), v, torch.zeros_like(v)).sum() for c in range(len(self.cfg.class_names))]
+        cnts = [(hit & (lab == c)).sum() for c in range(len(self.cfg.class_names))]
+        s, n = torch.stack(sums).cpu().numpy(), torch.stack(cnts).cpu().numpy()
+        return np.divide(s, n, out=np.full(len(s), np.nan), where=n != 0)
+
+    def compute(self):
+        res = self.run()
+        return summarize_iou(self.cfg, res["ap"].cpu().numpy(), res["ap_interp"].cpu().numpy(),
+                             res["tp_err"].cpu().numpy(), self._mean_matched_iou(res))
+
+    def detail(self):
+        """``object/<class>_<ap kind>_iou_<threshold>`` and the means, values rounded to four decimals"""
+        m = self.compute()
+        detail = dict()
+        for name in self.cfg.class_names:
+            for th, d in m["label_aps"][name].items():
+                for k, v in d.items():
+                    detail["object/{}_{}_iou_{}".format(name, k, th)] = float("{:.4f}".format(v))
+        for k in ("map_all", "map_r40", "map_101"):
+            detail["object/" + k] = m[k]
+        return detail

@@ -408,6 +408,12 @@ class BoxConcatArgs(ctypes.Structure):
                 ("out_boxes", _vp), ("out_scores", _vp), ("out_labels", _vp), ("out_source", _vp), ("out_count", _vp)]
 
 
+class DetIouArgs(ctypes.Structure):
+    """cmt_det_iou_args: the IoU side of the evaluator; the base struct is native_eval.DetEvalArgs"""
+    _fields_ = [("mode", _int), ("reserved", _int), ("z_origin", _flt), ("iou_th", _flt * 8),
+                ("match_iou", _vp), ("ap_interp", _vp)]
+
+
 STRUCTS = {"gemm": GemmArgs, "attn": AttnArgs, "ln": LnArgs, "chain": ChainArgs, "gemm_ex": GemmExArgs,
            "attn_train": AttnTrainArgs, "ln_train": LnTrainArgs, "bn": BnArgs, "det_loss": DetLossArgs,
            "match_cost": MatchCostArgs, "adamw": AdamwArgs, "mlp2": Mlp2Args, "mlp2_affine": Mlp2AffineArgs, "lsap": LsapArgs,
@@ -421,7 +427,7 @@ STRUCTS = {"gemm": GemmArgs, "attn": AttnArgs, "ln": LnArgs, "chain": ChainArgs,
            "points_in_boxes": PointsInBoxesArgs, "pts_augment": PtsAugmentArgs, "boxes_augment": BoxesAugmentArgs,
            "gtdb_extract": GtdbExtractArgs, "gtdb_gather": GtdbGatherArgs, "gtdb_collide": GtdbCollideArgs,
            "track_predict": TrackPredictArgs, "track_update": TrackUpdateArgs,
-           "box_iou": BoxIouArgs, "box_nms": BoxNmsArgs, "box_concat": BoxConcatArgs}
+           "box_iou": BoxIouArgs, "box_nms": BoxNmsArgs, "box_concat": BoxConcatArgs, "det_iou": DetIouArgs}
 
 _LIB = None
 
@@ -586,6 +592,10 @@ def _load():
         "cmt_box_iou": ([P(BoxIouArgs), _vp], _int),
         "cmt_box_nms": ([P(BoxNmsArgs), _vp], _int),
         "cmt_box_concat": ([P(BoxConcatArgs), _vp], _int),
+        "cmt_det_iou_args_size": ([], _i64),
+        # the base struct's mirror lives in native_eval.py, which sets its pointer type
+        "cmt_det_eval_match_iou": ([_vp, P(DetIouArgs), _vp], _int),
+        "cmt_det_eval_ap_interp": ([_vp, P(DetIouArgs), _vp], _int),
         "cmt_adamw_step": ([P(AdamwArgs), _vp], _int),
     }
     for name, (args, res) in sig.items():

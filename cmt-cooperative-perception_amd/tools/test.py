@@ -24,6 +24,12 @@ the same "at least one of --out / --eval / --format-only" check and the same
   mean_ap, tp_errors, nd_score, ...) is printed as one more JSON line after
   the statistics line.  With random weights the score says nothing about a
   model; the path is the one a dataset's ground truth would take;
+* ``--eval iou`` (alone or with ``bbox`` / ``nds``) scores the same boxes
+  against the same ground truth by overlap with ``IouDetectionEvaluator``
+  (``--iou-mode bev|3d``, ``--iou-thr F [F ...]``; the package's own settings,
+  not a devkit's) and prints one more JSON line ``metric="iou_ap"``: ap_all,
+  ap_r40 and ap_101 per class and threshold, map_all, map_r40, the TP errors
+  and the mean matched IoU;
 * ``--launcher pytorch``: frames are sharded over ranks (frame i on rank
   i % world) and rank 0 gathers the results (all_gather_object), as
   multi_gpu_test's result collection.
@@ -90,7 +96,12 @@ def parse_args(argv=None):
     p.add_argument("--openlabel-dir", default="openlabel_out", help="OpenLABEL output folder for --format-only")
     p.add_argument("--eval", type=str, nargs="+",
                    help="evaluation metrics (bbox: detection statistics; nds: nuScenes-style AP / TP errors / NDS "
-                        "against synthetic ground truth, on the device)")
+                        "against synthetic ground truth, on the device; iou: IoU-matched AP against the same ground "
+                        "truth)")
+    p.add_argument("--iou-mode", choices=["bev", "3d"], default="3d", help="overlap of --eval iou (default 3d)")
+    p.add_argument("--iou-thr", type=float, nargs="+", default=None, metavar="F",
+                   help="IoU thresholds of --eval iou (default: the package's 0.1 0.25 0.5 0.7); the TP errors are "
+                        "taken at 0.5 when it is among them, else at the first")
     p.add_argument("--synthetic", action="store_true", help="synthetic frames of the config's shapes (required)")
     p.add_argument("--frames", type=int, default=1, help="synthetic frames")
     p.add_argument("--num-query", type=int, default=None, help="override num_query (config 1: 32)")
@@ -378,6 +389,18 @@ def eval_config(class_names):
     return E.nuscenes_eval_config(class_names)
 
 
+def iou_eval_config(class_names, mode="3d", iou_thr=None):
+    """the package's IoU settings (core/evaluation.tumtraf_iou_config) for any class names; ground-truth velocity zero
+    for TUMTraf names, as eval_config"""
+    from projects.mmdet3d_plugin.core import evaluation as E
+    kw = {}
+    if iou_thr:
+        ths = [float(t) for t in iou_thr]
+        kw = dict(iou_ths=ths, iou_th_tp=0.5 if 0.5 in ths else ths[0])
+    return E.IouEvalConfig(class_names=tuple(class_names), mode=mode,
+                           gt_velocity_zero=all(n in E.TUMTRAF_CLASSES for n in class_names), **kw)
+
+
 def run_frame(head, name, feats, metas):
     if name.startswith("cmtcoop"):
         (xv, iv), (xi_, ii) = feats
@@ -441,12 +464,18 @@ def _run(args, name, device, rank, world, distributed):
                              num_point_features=vcfg["num_point_features"]).eval()
     class_names = list(cfg["tasks"][0]["class_names"])
     want_nds = bool(args.eval) and "nds" in args.eval
-    evaluator = None
+    want_iou = bool(args.eval) and "iou" in args.eval
+    evaluator = iou_evaluator = None
+    if want_nds or want_iou:
+        pcr = meta["point_cloud_range"]
     if want_nds:
         from projects.mmdet3d_plugin.core.evaluation import DetectionEvaluator
-        pcr = meta["point_cloud_range"]
         if rank == 0:
             evaluator = DetectionEvaluator(eval_config(class_names), max(args.frames, 1), device)
+    if want_iou and rank == 0:
+        from projects.mmdet3d_plugin.core.evaluation import IouDetectionEvaluator
+        iou_evaluator = IouDetectionEvaluator(iou_eval_config(class_names, args.iou_mode, args.iou_thr),
+                                              max(args.frames, 1), device)
 
     tracker = None
     if args.track:
@@ -464,6 +493,10 @@ def _run(args, name, device, rank, world, distributed):
     def feed(frame, boxes, scores, labels, points=None):
         gb, gl = frame_ground_truth(frame, args.seed, pcr, len(class_names))
         # the head's boxes are on the device already; the detector's result dict (bbox3d2result) is on the host
+        if iou_evaluator is not None:   # every ground-truth box counts, with or without --count-gt-points
+            iou_evaluator.add(boxes.to(device), scores.to(device), labels.to(device), None, gb.to(device), gl.to(device))
+        if evaluator is None:
+            return
         if points is None:
             evaluator.add(boxes.to(device), scores.to(device), labels.to(device), None, gb.to(device), gl.to(device))
             return
@@ -493,7 +526,7 @@ def _run(args, name, device, rank, world, distributed):
             nms = {}
             if args.nms:
                 boxes, scores, labels, nms["nms_kept"] = nms_frame(boxes, scores, labels, nms_thr, device)
-            if want_nds and not distributed:   # the boxes as tensors: no lists, no JSON
+            if (want_nds or want_iou) and not distributed:   # the boxes as tensors: no lists, no JSON
                 feed(f, boxes.float(), scores.float(), labels, points if args.count_gt_points else None)
             track = {}
             if tracker is not None:
@@ -541,14 +574,19 @@ def _run(args, name, device, rank, world, distributed):
                      seconds=round(elapsed, 4),
                      note="synthetic frames: no annotations offline, so no nuScenes AP")
         print(json.dumps(stats))
-    if want_nds:
+    if want_nds or want_iou:
         if distributed:   # rank 0 evaluates the gathered results
             for r in results:
                 feed(r["frame"], torch.tensor(r["boxes_3d"], dtype=torch.float32, device=device).reshape(-1, 9),
                      torch.tensor(r["scores_3d"], dtype=torch.float32, device=device),
                      torch.tensor(r["labels_3d"], dtype=torch.int64, device=device))
+    if want_nds:
         extra = dict(gt_without_points=int(sum(int(c.item()) for c in empty_gt))) if args.count_gt_points else {}
         print(json.dumps(dict(metric="nds", frames=len(results), gt_per_frame=GT_PER_FRAME, **extra, **evaluator.compute())))
+    if want_iou:
+        m = iou_evaluator.compute()
+        m["label_mean_iou"] = {k: (None if v != v else v) for k, v in m["label_mean_iou"].items()}   # no match: null
+        print(json.dumps(dict(metric="iou_ap", frames=len(results), gt_per_frame=GT_PER_FRAME, **m)))
     return 0
 
 

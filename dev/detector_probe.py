@@ -34,6 +34,11 @@ device events) on 800 frames x 300 predictions, 9 classes, 4 thresholds and 20 g
 ground truth plus false positives) against one run of the contract's numpy restatement (tests/_eval_ref.py, the
 reference's algorithm in its own style of loop) on the host, and checks that both give the same summary.
 
+``--only eval-iou`` (``--eval-iou-out FILE``) times ``IouDetectionEvaluator.run()`` (cmt_det_eval_match_iou and
+cmt_det_eval_ap_interp around the shared keys, sorts and curves) and ``DetectionEvaluator.run()`` on the same rows of the
+``--only eval`` workload, single calls in alternating order, with the stages by device events and the ratio of the two
+match kernels.
+
 ``--only augment`` (``--augment-out FILE``) times ``native_aug.augment_points`` on one training cloud of --points rows
 (F = 5) with 32 paste boxes and 4 000 paste rows, every step on (remove_points_in_boxes, rotation, scale, translation,
 both flips, range filter, shuffle), against the same chain as torch ops on the device (the inside test by
@@ -62,7 +67,7 @@ same draws and collision test followed by torch ops per object and per paste box
 runs VoVNet on the one-pass fp16 kernels; everything else is unchanged.
 
     python dev/detector_probe.py [--img-precision ref|fp16] [--points 300000] [--repeats 20] [--warmup 3]
-                                 [--iters 20] [--seed 0] [--out FILE] [--only resize|points|eval|augment|img-augment|gtdb|track|iou]
+                                 [--iters 20] [--seed 0] [--out FILE] [--only resize|points|eval|eval-iou|augment|img-augment|gtdb|track|iou]
                                  [--gtdb-out FILE] [--track-out FILE] [--iou-out FILE] [--resize-out FILE] [--augment-out FILE] [--img-augment-out FILE]
                                  [--points-out FILE] [--sweep-points 27000] [--sweeps K] [--eval-out FILE]
                                  [--eval-frames 800]
@@ -114,7 +119,7 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--img-precision", choices=("ref", "fp16"), default="ref")
     ap.add_argument("--out", default=None)
-    ap.add_argument("--only", choices=("resize", "points", "eval", "augment", "img-augment", "gtdb", "track", "iou"), default=None,
+    ap.add_argument("--only", choices=("resize", "points", "eval", "eval-iou", "augment", "img-augment", "gtdb", "track", "iou"), default=None,
                     help="run this section alone")
     ap.add_argument("--gtdb-out", default=None, help="write the ground-truth database section to this file")
     ap.add_argument("--track-out", default=None, help="write the tracker section to this file")
@@ -122,6 +127,7 @@ def main():
     ap.add_argument("--img-augment-out", default=None, help="write the cmt_img_augment section to this file")
     ap.add_argument("--augment-out", default=None, help="write the cmt_pts_augment section to this file")
     ap.add_argument("--eval-out", default=None, help="write the detection-evaluation section to this file")
+    ap.add_argument("--eval-iou-out", default=None, help="write the IoU-matched evaluation section to this file")
     ap.add_argument("--eval-frames", type=int, default=800, help="frames of the detection-evaluation section")
     ap.add_argument("--resize-out", default=None, help="write the cmt_img_resize_prepare section to this file")
     ap.add_argument("--points-out", default=None, help="write the cmt_pts_prepare section to this file")
@@ -287,6 +293,9 @@ def main():
     if args.only == "eval":
         eval_section(args, dev, say, lines)
         return
+    if args.only == "eval-iou":
+        eval_iou_section(args, dev, say, lines)
+        return
     if args.only == "augment":
         augment_section(args, dev, say, lines)
         return
@@ -339,16 +348,12 @@ def main():
     points_section(args, dev, say, lines)
 
 
-def eval_section(args, dev, say, lines):
-    """DetectionEvaluator.compute() on the device against the numpy restatement of its contract on the host"""
+def eval_rows(seed, S_, M, G, C, z_follows=False):
+    """the evaluation sections' workload: S_ frames of G ground-truth boxes and M predictions in descending score
+    order (40 % jittered ground truth, the rest false positives).  ``z_follows``: a jittered prediction also takes its
+    ground truth's height (the centre-distance evaluator does not read z, the 3D IoU does)."""
     import numpy as np
-    from projects.mmdet3d_plugin.core.evaluation import DetectionEvaluator, tumtraf_eval_config
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import _eval_ref as R
-    first = len(lines)
-    S_, M, G, cfg = args.eval_frames, 300, 20, tumtraf_eval_config()
-    C, T = len(cfg.class_names), len(cfg.dist_ths)
-    rng = np.random.RandomState(args.seed)
+    rng = np.random.RandomState(seed)
     gb = np.zeros((S_, G, 9), np.float32)
     gb[..., :2] = rng.uniform(-45, 45, (S_, G, 2))
     gb[..., 2] = rng.uniform(-2, 0, (S_, G))
@@ -364,10 +369,25 @@ def eval_section(args, dev, say, lines):
     pb[..., 3:6] = take(gb[..., 3:6], src[..., None], 1) * rng.uniform(0.8, 1.25, (S_, M, 3))
     pb[..., 6] = take(gb[..., 6], src, 1) + rng.normal(0, 0.2, (S_, M))
     pb[..., 7:9] = rng.normal(0, 0.5, (S_, M, 2))
+    if z_follows:
+        pb[..., 2] = take(gb[..., 2], src, 1) + rng.normal(0, 0.1, (S_, M))
     pl = np.where(hit, take(gl, src, 1), rng.randint(0, C, (S_, M))).astype(np.int32)
     ps = np.where(hit, rng.uniform(0.2, 1.0, (S_, M)), rng.uniform(0.0, 0.6, (S_, M))).astype(np.float32)
     order = np.argsort(-ps, 1)                       # box_decode's rows come in descending score order
     pb, pl, ps = take(pb, order[..., None], 1), take(pl, order, 1), take(ps, order, 1)
+    return gb, gl, pb, pl, ps
+
+
+def eval_section(args, dev, say, lines):
+    """DetectionEvaluator.compute() on the device against the numpy restatement of its contract on the host"""
+    import numpy as np
+    from projects.mmdet3d_plugin.core.evaluation import DetectionEvaluator, tumtraf_eval_config
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import _eval_ref as R
+    first = len(lines)
+    S_, M, G, cfg = args.eval_frames, 300, 20, tumtraf_eval_config()
+    C, T = len(cfg.class_names), len(cfg.dist_ths)
+    gb, gl, pb, pl, ps = eval_rows(args.seed, S_, M, G, C)
     count = torch.full((S_,), M, dtype=torch.int32, device=dev)
     ev = DetectionEvaluator(cfg, S_, dev)
     t0 = time.perf_counter()
@@ -411,6 +431,56 @@ def eval_section(args, dev, say, lines):
         f"tp flags equal: {bool(np.array_equal(ev._result['tp'].cpu().numpy(), ref['tp']))}")
     say(f"peak device memory {torch.cuda.max_memory_allocated() / 2 ** 20:.0f} MiB")
     for path, text in ((args.out, lines), (args.eval_out, lines[first:])):
+        if path:
+            os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+            with open(path, "w") as f:
+                f.write("\n".join(text) + "\n")
+
+
+def eval_iou_section(args, dev, say, lines):
+    """IouDetectionEvaluator.run() (cmt_det_eval_match_iou, cmt_det_eval_ap_interp) and DetectionEvaluator.run() on the
+    same rows in the same session, single calls in alternating order"""
+    from projects.mmdet3d_plugin.core.evaluation import (DetectionEvaluator, IouDetectionEvaluator, tumtraf_eval_config,
+                                                         tumtraf_iou_config)
+    first = len(lines)
+    S_, M, G = args.eval_frames, 300, 20
+    cfg_d, cfg_i = tumtraf_eval_config(), tumtraf_iou_config()
+    C, T = len(cfg_i.class_names), len(cfg_i.iou_ths)
+    gb, gl, pb, pl, ps = eval_rows(args.seed, S_, M, G, C, z_follows=True)
+    count = torch.full((S_,), M, dtype=torch.int32, device=dev)
+    evs = dict(iou=IouDetectionEvaluator(cfg_i, S_, dev), dist=DetectionEvaluator(cfg_d, S_, dev))
+    for ev in evs.values():
+        ev.add(torch.from_numpy(pb).to(dev), torch.from_numpy(ps).to(dev), torch.from_numpy(pl).to(dev), count,
+               [torch.from_numpy(gb[s]).to(dev) for s in range(S_)], [torch.from_numpy(gl[s]).to(dev) for s in range(S_)])
+        for _ in range(args.warmup):
+            ev.run()
+    torch.cuda.synchronize()
+    total = {k: [] for k in evs}
+    phases = {k: {} for k in evs}
+    for _ in range(args.repeats):
+        for k, ev in evs.items():
+            events = []
+            total[k].append(event_ms(lambda: ev.run(events=events)))
+            for name, a, b in events:
+                phases[k].setdefault(name, []).append(a.elapsed_time(b))
+    res = evs["iou"]._result
+    tp = res["tp"].cpu().numpy()
+    got = evs["iou"].compute()
+    say(f"--- {torch.cuda.get_device_name(0)}: IoU-matched evaluation (cmt_det_eval_match_iou, mode {cfg_i.mode}) against "
+        f"the centre-distance evaluation on the same rows: {S_} frames x {M} predictions ({S_ * M} rows), {S_ * G} "
+        f"ground-truth boxes, {C} classes, {T} thresholds; run(): median of {args.repeats} single calls in alternating "
+        f"order after {args.warmup} warm-up (min .. max), device events, ms")
+    say(f"{'':>26} {'IoU match':>32}   {'centre distance':>32}")
+    say(f"{'whole run':>26} {fmt(med(total['iou']))}   {fmt(med(total['dist']))}")
+    for name in ("keys", "sort", "match", "curves", "ap_interp"):
+        d = fmt(med(phases["dist"][name])) if name in phases["dist"] else ""
+        say(f"{name:>26} {fmt(med(phases['iou'][name]))}   {d}")
+    r = med(phases["iou"]["match"])[0] / med(phases["dist"]["match"])[0]
+    say(f"match kernel, IoU / centre distance: {r:.2f}")
+    say(f"matches per threshold {tp.sum(1).tolist()} of {S_ * M} rows; map_all {got['map_all']:.6f}, map_r40 "
+        f"{got['map_r40']:.6f}, map_101 {got['map_101']:.6f}")
+    say(f"peak device memory {torch.cuda.max_memory_allocated() / 2 ** 20:.0f} MiB")
+    for path, text in ((args.out, lines), (args.eval_iou_out, lines[first:])):
         if path:
             os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
             with open(path, "w") as f:

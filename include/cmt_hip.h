@@ -1516,6 +1516,44 @@ int cmt_det_eval_keys(const cmt_det_eval_args* args, void* stream);
 int cmt_det_eval_match(const cmt_det_eval_args* args, void* stream);
 int cmt_det_eval_curves(const cmt_det_eval_args* args, void* stream);
 
+/* ---- IoU-matched detection AP (deteval.hip, box_overlap.h; additive to ABI 25) ------------------------
+ * The same evaluation with overlap in place of the centre distance (KITTI / VOC style).  Filters, order,
+ * keys, sorts, output layouts, errors and curves are those above; cmt_det_eval_match_iou stands where
+ * cmt_det_eval_match stands, and cmt_det_eval_ap_interp adds the interpolated APs after (or without)
+ * cmt_det_eval_curves:  keys -> the three sorts -> match_iou -> curves -> ap_interp.
+ * Overlap.  For a visited prediction p and a kept ground truth g of its sample and class, iou(p, g) is
+ * cmt_box_iou's float32 value with THE GROUND TRUTH AS THE FIRST BOX (the pair is clipped in g's frame, so
+ * the value of a ground truth does not depend on which prediction asks): mode 0 its bev, mode 1 its iou3d,
+ * both with z_origin.  A box that is invalid there (a non-finite field among the first seven, or a
+ * non-positive extent) gives 0 on either side; a NaN quotient (0 / 0 of underflowed extents) counts as 0.
+ * Match, per (class c, threshold t): the visited prediction takes, among the not yet taken kept ground truth
+ * of its sample and class, the one with the LARGEST iou; equal iou: the lowest annotation index.  tp = 1 iff
+ * iou > iou_th[t] (strict, in float32: an iou of 0 never matches), and only then is that ground truth taken
+ * (for this t alone) and match_gt = its row; else tp = 0, match_gt = -1.  The four errors of a match are the
+ * ones above, err[0] still the centre distance in float64.  match_iou[T][N] (optional) is the iou of the
+ * match, NaN without one.  dist_th of the base struct is validated but not read.
+ * Every output element has exactly one writer, no atomics, no memset: two runs are bit-equal.
+ * Interpolated APs, per (c, t), with ctp, prec, n, M, npos as above: env[j] = max over k >= j of prec[k],
+ * pos(m) the position of the m-th match (m = 1 .. M):
+ *   ap_interp[c][t][0]  all-point AP = (sum over m of env[pos(m)], a serial sum in m order) / npos;
+ *   ap_interp[c][t][1]  R40 = (sum over k = 1 .. 40, in k order, of env[pos(m_k)]) / 40, m_k the smallest m
+ *                       with m * 40 >= k * npos (integers), the term 0 when m_k > M;
+ *   both 0 when npos == 0 or M == 0.  Float64; a maximum does not round, the sums are serial: bit-equal.
+ * cmt_det_eval_ap_interp reads tp, npos and the sorted class keys and uses the workspace of the base struct.
+ * CMT_EINVAL before any device work: whatever cmt_det_eval_match refuses in the base struct, a mode other
+ * than 0 / 1, a z_origin other than 0 / 0.5, an iou_th outside [0, 1) or non-finite, a misaligned match_iou,
+ * a null or misaligned ap_interp (cmt_det_eval_ap_interp only). */
+typedef struct cmt_det_iou_args {
+    int mode, reserved;                       /* 0 BEV, 1 3D */
+    float z_origin;                           /* 0 or 0.5, as cmt_box_iou */
+    float iou_th[CMT_DET_MAX_THRESHOLDS];     /* T of them, each in [0, 1) */
+    void* match_iou;                          /* fp32 [T][N], or null */
+    void* ap_interp;                          /* float64 [C][T][2], for cmt_det_eval_ap_interp */
+} cmt_det_iou_args;
+int64_t cmt_det_iou_args_size(void);
+int cmt_det_eval_match_iou(const cmt_det_eval_args* args, const cmt_det_iou_args* iou, void* stream);
+int cmt_det_eval_ap_interp(const cmt_det_eval_args* args, const cmt_det_iou_args* iou, void* stream);
+
 /* ---- training-side point and box pipeline (ptsaug.hip; additive to ABI 25) ---------------------------
  * The chain every reference config that trains on points runs between loading and the voxelizer:
  * [Unified]ObjectSample[Coop] (the part after the database sampler has chosen its objects),
