@@ -6,6 +6,9 @@ filter_eval_boxes, _evaluate_a9_nusc).  ``DetectionEvaluator`` collects frames i
 read; ``compute()`` runs sort -> match -> curves on the device and reads back C x T APs and C x 4 errors, the means
 over them (nine classes, four numbers each) are float64 on the host.
 
+``TrackingEvaluator`` scores tracked boxes (``native_track.Tracker``'s ids) against ground truth with instance ids:
+CLEAR MOT counters per recall level and AMOTA / AMOTP (``cmt_mot_eval_*``, csrc/moteval.hip).
+
 ``IouDetectionEvaluator`` is the same collector scored by overlap (``cmt_det_eval_match_iou``: the largest BEV or 3D
 IoU above a threshold, KITTI / VOC style) with the all-point and 40-point APs of ``cmt_det_eval_ap_interp`` next to the
 101-point one.
@@ -21,7 +24,7 @@ from ... import native_eval as NE
 
 __all__ = ["DetEvalConfig", "tumtraf_eval_config", "nuscenes_eval_config", "DetectionEvaluator", "summarize", "TUMTRAF_CLASSES",
            "TP_METRICS", "ERR_NAME_MAPPING", "IouEvalConfig", "tumtraf_iou_config", "IouDetectionEvaluator", "summarize_iou",
-           "NO_RANGE"]
+           "NO_RANGE", "MotEvalConfig", "tumtraf_mot_config", "nuscenes_mot_config", "summarize_mot", "TrackingEvaluator"]
 
 TUMTRAF_CLASSES = ("CAR", "TRAILER", "TRUCK", "VAN", "PEDESTRIAN", "BUS", "MOTORCYCLE", "BICYCLE", "EMERGENCY_VEHICLE")
 _TUMTRAF_RANGE = {"CAR": 50, "TRUCK": 50, "BUS": 50, "TRAILER": 50, "VAN": 50, "EMERGENCY_VEHICLE": 50,
@@ -379,4 +382,217 @@ class IouDetectionEvaluator(DetectionEvaluator):
                     detail["object/{}_{}_iou_{}".format(name, k, th)] = float("{:.4f}".format(v))
         for k in ("map_all", "map_r40", "map_101"):
             detail["object/" + k] = m[k]
+        return detail
+
+
+# ---- tracking evaluation --------------------------------------------------------------------------------------
+
+
+@dataclass
+class MotEvalConfig:
+    """The constants of the tracking evaluation (cmt_mot_eval_* in include/cmt_hip.h).  ``class_range`` and ``dist_th``
+    (metres; one number for all classes or one per class) follow ``class_names``; ``num_thresholds`` recall levels
+    from ``min_recall`` to 1; ``max_gt_tracks`` bounds the instance ids of a scene; at most ``max_boxes_per_frame``
+    prediction rows per frame."""
+    class_names: Sequence[str]
+    class_range: Optional[Sequence[float]] = None
+    dist_th: object = 2.0
+    num_thresholds: int = 40
+    min_recall: float = 0.1
+    max_gt_tracks: int = 1024
+    max_boxes_per_frame: int = 500
+
+    def __post_init__(self):
+        self.class_names = tuple(self.class_names)
+        C = len(self.class_names)
+        self.class_range = [NO_RANGE] * C if self.class_range is None else [float(v) for v in self.class_range]
+        self.dist_th = [float(v) for v in self.dist_th] if isinstance(self.dist_th, (list, tuple)) else [float(self.dist_th)] * C
+        if len(self.class_range) != C:
+            raise ValueError(f"{C} class names but {len(self.class_range)} class ranges")
+        NE.check_mot_config(self.class_range, self.dist_th, self.recall_levels(), self.max_gt_tracks)
+        if int(self.max_boxes_per_frame) < 1:
+            raise ValueError(f"max_boxes_per_frame must be at least 1, got {self.max_boxes_per_frame}")
+
+    def recall_levels(self):
+        return NE.mot_recall_levels(self.num_thresholds, self.min_recall)
+
+
+def tumtraf_mot_config(class_names=TUMTRAF_CLASSES, **overrides):
+    """The TUMTraf classes with the detection evaluator's class ranges (50 / 40 m), a 2 m match distance and 40 recall
+    levels from 0.1.  These are settings of this package: they are not taken from, and have not been compared with,
+    a TUMTraf tracking devkit."""
+    names = tuple(class_names)
+    unknown = [n for n in names if n not in _TUMTRAF_RANGE]
+    if unknown:
+        raise ValueError(f"no TUMTraf class range for {unknown}")
+    return MotEvalConfig(class_names=names, class_range=[float(_TUMTRAF_RANGE[n]) for n in names], **overrides)
+
+
+# nuScenes tracking_nips_2019 (the devkit's public configuration file): seven classes, 2 m, 40 levels from 0.1
+NUSCENES_TRACKING_CLASSES = ("bicycle", "bus", "car", "motorcycle", "pedestrian", "trailer", "truck")
+_NUSCENES_TRACKING_RANGE = {"car": 50, "truck": 50, "bus": 50, "trailer": 50, "pedestrian": 40, "motorcycle": 40,
+                            "bicycle": 40}
+
+
+def nuscenes_mot_config(class_names=NUSCENES_TRACKING_CLASSES, **overrides):
+    """The nuScenes tracking constants: class ranges 50 / 40 m, match distance 2 m, 40 recall levels from 0.1.  The
+    contract's stated deviations from the devkit apply (order-statistic thresholds, no track interpolation)."""
+    names = tuple(class_names)
+    unknown = [n for n in names if n not in _NUSCENES_TRACKING_RANGE]
+    if unknown:
+        raise ValueError(f"no nuScenes tracking class range for {unknown}")
+    return MotEvalConfig(class_names=names, class_range=[float(_NUSCENES_TRACKING_RANGE[n]) for n in names], **overrides)
+
+
+def summarize_mot(cfg, class_sum, npos):
+    """The metrics dictionary from class_sum [C, 12] (native_eval.MOT_CLASS_SUM) and npos [C], in float64 on the
+    host.  A class without ground truth is left out of the means (its entries are NaN), as the devkit does."""
+    cs, npos = np.asarray(class_sum, dtype=np.float64), np.asarray(npos)
+    col = {n: i for i, n in enumerate(NE.MOT_CLASS_SUM)}
+    per_class = dict()
+    for c, name in enumerate(cfg.class_names):
+        d = {k: float(cs[c, col[k]]) for k in ("amota", "amotp", "mota", "motp", "recall")}
+        for k in ("tp", "fp", "fn", "ids", "frag"):
+            v = cs[c, col[k]]
+            d[k] = None if np.isnan(v) else int(v)
+        d["threshold"], d["best_slot"], d["npos"] = float(cs[c, col["thr"]]), int(cs[c, col["best"]]), int(npos[c])
+        per_class[name] = d
+    used = [n for c, n in enumerate(cfg.class_names) if npos[c] > 0]
+
+    def mean(key):
+        vals = [per_class[n][key] for n in used if not math.isnan(per_class[n][key])]
+        return float(np.mean(vals)) if vals else float("nan")
+
+    out = dict(label_metrics=per_class, classes_evaluated=used)
+    out.update({k: mean(k) for k in ("amota", "amotp", "mota", "motp", "recall")})
+    out.update({k: int(sum(per_class[n][k] or 0 for n in used)) for k in ("tp", "fp", "fn", "ids", "frag")})
+    return out
+
+
+class TrackingEvaluator:
+    """Collects tracked boxes and ground truth with instance ids frame by frame on the device and scores them.
+
+    ``capacity_frames`` frames of at most ``cfg.max_boxes_per_frame`` prediction rows fit; the prediction buffers are
+    allocated once.  ``add`` copies on the device and reads nothing back; the (scene, step) table is kept on the host,
+    which knows it without asking the device.  ``compute`` / ``run`` read one pair of counts back (the longest
+    frame) to size the matrices, then the result."""
+
+    def __init__(self, cfg, capacity_frames: int, device):
+        if not isinstance(cfg, MotEvalConfig):
+            raise ValueError("cfg must be a MotEvalConfig")
+        if not 1 <= int(capacity_frames) <= NE.MOT_MAX_SCENE_STEPS:
+            raise ValueError(f"capacity_frames must be in [1, 2^24], got {capacity_frames}")
+        self.cfg = cfg
+        self.capacity_frames = int(capacity_frames)
+        self.device = torch.device(device)
+        self._rows = self.capacity_frames * int(cfg.max_boxes_per_frame)
+        if self._rows >= 2 ** 31:
+            raise ValueError("capacity_frames * max_boxes_per_frame must be below 2^31")
+        self._buf = None
+        self.reset()
+
+    def reset(self):
+        self._n = 0
+        self._table = []       # (scene, step) per frame
+        self._next_step = {}   # scene -> the step of its next frame
+        self._gt = []          # (boxes, labels, frames, ids) per frame
+        self._result = None
+
+    def add(self, boxes, scores, labels, track_ids, count=None, *, gt_boxes, gt_labels, gt_ids, scene, step=None):
+        """One frame.  ``boxes`` fp32 [n, >= 2] (x, y in front, as the decoder's nine columns have them), ``scores``
+        fp32 [n], ``labels`` int [n], ``track_ids`` int32 [n]: ``Tracker.step``'s ``det_track`` as it is (-1: the row
+        belongs to no track), ``count``: None or the device int32 of the valid rows.  ``gt_boxes`` fp32 [g, >= 2],
+        ``gt_labels`` int [g], ``gt_ids`` int [g], the objects' instance ids inside the scene, below
+        ``cfg.max_gt_tracks``.  ``scene``: the frame's scene (an int >= 0); ``step``: its position there (default: one
+        after the scene's latest).  A (scene, step) can be added once."""
+        n = self._check_rows(boxes, "boxes", scores=scores, labels=labels, track_ids=track_ids)
+        g = self._check_rows(gt_boxes, "gt_boxes", gt_labels=gt_labels, gt_ids=gt_ids)
+        if scores.dtype != torch.float32 or track_ids.dtype != torch.int32:
+            raise ValueError("scores must be fp32 and track_ids int32")
+        if n > int(self.cfg.max_boxes_per_frame):
+            raise ValueError(f"only <= {self.cfg.max_boxes_per_frame} boxes per frame allowed, got {n}")
+        if count is not None and (not torch.is_tensor(count) or count.dtype != torch.int32 or count.numel() != 1):
+            raise ValueError("count must be one int32 on the device or None")
+        scene = int(scene)
+        step = self._next_step.get(scene, 0) if step is None else int(step)
+        if scene < 0 or step < 0:
+            raise ValueError(f"scene and step must not be negative, got {scene} and {step}")
+        if (scene, step) in self._table:
+            raise ValueError(f"step {step} of scene {scene} was added before")
+        if len(self._table) >= self.capacity_frames:
+            raise ValueError(f"capacity of {self.capacity_frames} frames exceeded")
+        tensors = [boxes, scores, labels, track_ids, gt_boxes, gt_labels, gt_ids] + ([] if count is None else [count])
+        if any(not t.is_cuda for t in tensors):
+            raise ValueError("the evaluator needs its tensors on a HIP device (no CPU path)")
+        dev, f = self.device, len(self._table)
+        if self._buf is None:
+            r = self._rows
+            self._buf = dict(box=torch.empty((r, 2), dtype=torch.float32, device=dev),
+                             score=torch.empty(r, dtype=torch.float32, device=dev),
+                             label=torch.empty(r, dtype=torch.int32, device=dev),
+                             track=torch.empty(r, dtype=torch.int32, device=dev),
+                             frame=torch.empty(r, dtype=torch.int32, device=dev))
+        lab = labels.to(device=dev, dtype=torch.int32)
+        if count is not None:   # rows at or beyond the count do not exist: label -1
+            live = torch.arange(n, device=dev, dtype=torch.int32) < count.to(dev).reshape(1)
+            lab = torch.where(live, lab, torch.full_like(lab, -1))
+        n0, n1 = self._n, self._n + n
+        self._buf["box"][n0:n1].copy_(boxes[:, :2])
+        self._buf["score"][n0:n1].copy_(scores)
+        self._buf["label"][n0:n1].copy_(lab)
+        self._buf["track"][n0:n1].copy_(track_ids)
+        self._buf["frame"][n0:n1].fill_(f)
+        self._gt.append((gt_boxes[:, :2].to(device=dev, copy=True), gt_labels.to(device=dev, dtype=torch.int32),
+                         torch.full((g,), f, dtype=torch.int32, device=dev), gt_ids.to(device=dev, dtype=torch.int32)))
+        self._table.append((scene, step))
+        self._next_step[scene] = max(self._next_step.get(scene, 0), step + 1)
+        self._n, self._result = n1, None
+
+    @staticmethod
+    def _check_rows(box, name, **cols):
+        if not torch.is_tensor(box) or box.dim() != 2 or box.shape[1] < 2 or box.dtype != torch.float32:
+            raise ValueError(f"{name} must be fp32 [n, >= 2]")
+        n = int(box.shape[0])
+        for k, t in cols.items():
+            if not torch.is_tensor(t) or tuple(t.shape) != (n,):
+                raise ValueError(f"{k} must be a tensor of shape [{n}]")
+            if k in ("labels", "gt_labels", "gt_ids") and t.dtype not in (torch.int32, torch.int64):
+                raise ValueError(f"{k} must be int32 or int64")
+        return n
+
+    def run(self, events=None, workspace_bytes=NE.MOT_WORKSPACE, alloc=None):
+        """the evaluation on the device -> the dict of device tensors of ``native_eval.mot_eval``"""
+        if not self._table:
+            raise ValueError("no frame was added")
+        cfg, buf, n = self.cfg, self._buf, self._n
+        gt = tuple(torch.cat([g[k] for g in self._gt]).contiguous() for k in range(4))
+        table = torch.tensor(self._table, dtype=torch.int32).reshape(-1, 2).to(self.device)
+        self._result = NE.mot_eval(buf["box"][:n], buf["score"][:n], buf["label"][:n], buf["track"][:n], buf["frame"][:n],
+                                   gt[0], gt[1], gt[2], gt[3], table,
+                                   num_scenes=max(s for s, _ in self._table) + 1,
+                                   max_steps=max(t for _, t in self._table) + 1, class_range=cfg.class_range,
+                                   dist_th=cfg.dist_th, recall=cfg.recall_levels(), max_gt_tracks=cfg.max_gt_tracks,
+                                   workspace_bytes=workspace_bytes, alloc=alloc, events=events)
+        return self._result
+
+    def compute(self):
+        """AMOTA / AMOTP and, at the recall level of highest MOTA, MOTA / MOTP / recall / TP / FP / FN / IDS / FRAG per
+        class, with the means over the classes that have ground truth (``summarize_mot``)."""
+        res = self.run()
+        return summarize_mot(self.cfg, res["class_sum"].cpu().numpy(), res["npos"].cpu().numpy())
+
+    def detail(self):
+        """``track/<class>_<metric>`` and the means, floats rounded to four decimals"""
+        res = self.run() if self._result is None else self._result
+        m = summarize_mot(self.cfg, res["class_sum"].cpu().numpy(), res["npos"].cpu().numpy())
+        detail = dict()
+        for name, d in m["label_metrics"].items():
+            for k in ("amota", "amotp", "mota", "motp", "recall"):
+                detail["track/{}_{}".format(name, k)] = float("{:.4f}".format(d[k]))
+            for k in ("ids", "frag", "tp", "fp", "fn"):
+                detail["track/{}_{}".format(name, k)] = d[k]
+        for k in ("amota", "amotp", "mota", "motp", "recall"):
+            detail["track/" + k] = m[k]
+        for k in ("ids", "frag"):
+            detail["track/" + k] = m[k]
         return detail

@@ -266,7 +266,7 @@ def synthetic_vehicle2infrastructure(seed=0):
 
 
 def moving_scene(seed, n_objects=12, frames=30, dt=0.1, grid_cols=4, spacing=10.0, max_speed=1.0, noise=0.2,
-                 p_drop=0.1, max_drop_run=2, n_false=2, false_margin=5.0, num_classes=3, pad_to=None):
+                 p_drop=0.1, max_drop_run=2, n_false=2, false_margin=5.0, num_classes=3, pad_to=None, with_truth=False):
     """A seeded scene of moving boxes for the tracker (native_track.Tracker), as numpy on the host.
 
     ``n_objects`` objects start on a grid of ``grid_cols`` columns ``spacing`` metres apart and move with constant
@@ -277,7 +277,10 @@ def moving_scene(seed, n_objects=12, frames=30, dt=0.1, grid_cols=4, spacing=10.
     [0.5, 0.9], of the false ones in [0.35, 0.5].
     -> a list of dicts: ``boxes`` fp32 [n, 9] (x y z dx dy dz yaw vx vy), ``scores`` fp32 [n], ``labels`` int32 [n],
     ``object`` int32 [n] (the object of a row, -1 for a false box), ``timestamp`` (seconds, float).  With
-    ``pad_to`` every array has ``pad_to`` rows (zeros beyond ``count``, ``object`` -1) and ``count`` is n."""
+    ``pad_to`` every array has ``pad_to`` rows (zeros beyond ``count``, ``object`` -1) and ``count`` is n.  With
+    ``with_truth`` every frame also has the true state of every object, dropped ones included: ``gt_boxes`` fp32
+    [n_objects, 9], ``gt_labels`` int32 and ``gt_ids`` int32 (the object's index); it draws no random number, so the
+    other keys are the same bytes with and without it."""
     rng = np.random.RandomState(seed)
     idx = np.arange(n_objects)
     pos0 = np.stack([(idx % grid_cols) * spacing, (idx // grid_cols) * spacing, np.zeros(n_objects)], 1)
@@ -322,4 +325,8 @@ def moving_scene(seed, n_objects=12, frames=30, dt=0.1, grid_cols=4, spacing=10.
             lab = np.concatenate([lab, np.zeros(pad, np.int32)])
             obj = np.concatenate([obj, np.full(pad, -1, np.int32)])
         out.append(dict(boxes=b, scores=s, labels=lab.astype(np.int32), object=obj, count=n, timestamp=t * dt))
+        if with_truth:
+            g = np.zeros((n_objects, 9))
+            g[:, :3], g[:, 3:6], g[:, 6], g[:, 7:9] = truth, size, np.arctan2(vel[:, 1], vel[:, 0]), vel
+            out[-1].update(gt_boxes=g.astype(np.float32), gt_labels=label.copy(), gt_ids=idx.astype(np.int32))
     return out

@@ -67,6 +67,14 @@ object by its track's uuid from frame to frame and writes the track's positions 
 frames are independent draws, so the ids say nothing about a scene; the path is the one a sequence would take.  Not
 with ``--launcher pytorch`` (the frames are sharded over ranks).
 
+``--eval track`` (alone or beside ``bbox`` / ``nds`` / ``iou``; it needs ``--track`` and exits with status 2 and a
+message otherwise) scores the tracker's ids on the device (``core/evaluation.TrackingEvaluator``, cmt_mot_eval_*).
+Under this flag only, the ground truth of frame f is frame 0's ``synthetic_gt`` moved by its own velocity columns
+over f * 0.1 s, with instance ids equal to the row index.  It prints one JSON line ``metric="mot"`` with ``amota``,
+``amotp`` and, per class at the recall level of highest MOTA, ``mota`` / ``motp`` / ``recall`` / ``ids`` / ``frag`` /
+``fp`` / ``fn`` (null for a class without ground truth).  The detections are still independent draws, so the numbers
+say nothing about tracking quality; the path is the one a sequence would take.
+
 Config 1 of BASELINE.json: ``python cmt-cooperative-perception_amd/tools/test.py
 cmt_lidar_nus --synthetic --num-query 32 --num-layers 1 --points 1000 --eval bbox``.
 The head runs on a HIP device only -- there is no CPU path; without a GPU the
@@ -97,7 +105,8 @@ def parse_args(argv=None):
     p.add_argument("--eval", type=str, nargs="+",
                    help="evaluation metrics (bbox: detection statistics; nds: nuScenes-style AP / TP errors / NDS "
                         "against synthetic ground truth, on the device; iou: IoU-matched AP against the same ground "
-                        "truth)")
+                        "truth; track: MOTA / MOTP / id switches and AMOTA / AMOTP of --track's ids against frame 0's "
+                        "ground truth moved by its own velocity)")
     p.add_argument("--iou-mode", choices=["bev", "3d"], default="3d", help="overlap of --eval iou (default 3d)")
     p.add_argument("--iou-thr", type=float, nargs="+", default=None, metavar="F",
                    help="IoU thresholds of --eval iou (default: the package's 0.1 0.25 0.5 0.7); the TP errors are "
@@ -157,6 +166,8 @@ def parse_args(argv=None):
         p.error("--sweeps K needs --detector and K >= 0")
     if a.count_gt_points and (not a.eval or "nds" not in a.eval or a.launcher != "none"):
         p.error("--count-gt-points needs --eval nds and --launcher none")
+    if a.eval and "track" in a.eval and not a.track:
+        p.error("--eval track scores the tracker's ids: it needs --track")
     if not a.synthetic:
         p.error("dataset loading is out of scope (SURVEY.md 2 rows 18/21): run with --synthetic")
     return a
@@ -345,9 +356,28 @@ def gt_point_counts(gt_boxes, points):
 TRACK_FRAME_SECONDS = 0.1   # --track: the synthetic frames are this far apart
 
 
-def track_frame(tracker, frame, boxes, scores, labels, device, want_history):
+def track_ground_truth(frame, seed, pc_range, num_classes):
+    """--eval track: frame 0's synthetic ground truth moved by its own velocity columns over frame * 0.1 s ->
+    (boxes [20, 9] fp32, labels [20] int64, ids [20] int32 = the row index), on the host"""
+    import torch
+    boxes, labels = frame_ground_truth(0, seed, pc_range, num_classes)
+    boxes = boxes.clone()
+    boxes[:, :2] += boxes[:, 7:9] * (frame * TRACK_FRAME_SECONDS)
+    return boxes, labels, torch.arange(boxes.shape[0], dtype=torch.int32)
+
+
+def mot_eval_config(class_names, max_boxes):
+    """TUMTraf class ranges for TUMTraf class names, the nuScenes detection ranges otherwise; a 2 m match distance and
+    40 recall levels from 0.1 (core/evaluation.MotEvalConfig)"""
+    from projects.mmdet3d_plugin.core import evaluation as E
+    return E.MotEvalConfig(class_names=tuple(class_names), class_range=eval_config(class_names).class_range,
+                           max_boxes_per_frame=max_boxes)
+
+
+def track_frame(tracker, frame, boxes, scores, labels, device, want_history, score=None):
     """One frame's boxes ([n, 9], scores [n], labels [n], on either side) through the tracker -> dict(track_ids [n]
-    as a list, and with ``want_history`` track_history {id: positions, oldest first})."""
+    as a list, and with ``want_history`` track_history {id: positions, oldest first}).  ``score(boxes, scores, labels,
+    det_track, count)`` receives the padded device tensors of the step (--eval track)."""
     import torch
     n, D = int(scores.shape[0]), tracker.max_dets
     if n > D:
@@ -357,7 +387,10 @@ def track_frame(tracker, frame, boxes, scores, labels, device, want_history):
     lab = torch.zeros(D, dtype=torch.int32, device=device)
     b[:n], s[:n], lab[:n] = boxes.float().to(device)[:, :9], scores.float().to(device), labels.to(device).to(torch.int32)
     count = torch.full((1,), n, dtype=torch.int32, device=device)
-    ids = tracker.step(b, s, lab, count, timestamp=frame * TRACK_FRAME_SECONDS)[:n].cpu().tolist()
+    det_track = tracker.step(b, s, lab, count, timestamp=frame * TRACK_FRAME_SECONDS)
+    if score is not None:
+        score(b, s, lab, det_track, count)
+    ids = det_track[:n].cpu().tolist()
     out = dict(track_ids=ids)
     if want_history:
         t = tracker.tracks(confirmed=False)
@@ -484,6 +517,21 @@ def _run(args, name, device, rank, world, distributed):
         from projects.mmdet3d_plugin import native_track as NT
         tracker = NT.Tracker(class_names, device, max_dets=NT.MAX_DETS)
 
+    mot_evaluator = None
+    if args.eval and "track" in args.eval:
+        from projects.mmdet3d_plugin.core.evaluation import TrackingEvaluator
+        mot_evaluator = TrackingEvaluator(mot_eval_config(class_names, tracker.max_dets), max(args.frames, 1), device)
+
+    def feed_track(frame):
+        if mot_evaluator is None:
+            return None
+        gb, gl, gi = track_ground_truth(frame, args.seed, meta["point_cloud_range"], len(class_names))
+
+        def score(b, s, lab, det_track, count):
+            mot_evaluator.add(b, s, lab, det_track, count, gt_boxes=gb.to(device), gt_labels=gl.to(device),
+                              gt_ids=gi.to(device), scene=0, step=frame)
+        return score
+
     nms_thr = None
     if args.nms:
         nms_thr = args.nms_thr if args.nms_thr is not None else float((cfg.get("test_cfg") or {}).get("nms_thr", 0.2))
@@ -530,7 +578,7 @@ def _run(args, name, device, rank, world, distributed):
                 feed(f, boxes.float(), scores.float(), labels, points if args.count_gt_points else None)
             track = {}
             if tracker is not None:
-                track = track_frame(tracker, f, boxes, scores, labels, device, args.format_only)
+                track = track_frame(tracker, f, boxes, scores, labels, device, args.format_only, feed_track(f))
             results.append(dict(frame=f, voxels=vox_stats, **track, **nms,
                                 boxes_3d=boxes.float().cpu().tolist(), scores_3d=scores.float().cpu().tolist(),
                                 labels_3d=labels.cpu().tolist(),
@@ -587,6 +635,16 @@ def _run(args, name, device, rank, world, distributed):
         m = iou_evaluator.compute()
         m["label_mean_iou"] = {k: (None if v != v else v) for k, v in m["label_mean_iou"].items()}   # no match: null
         print(json.dumps(dict(metric="iou_ap", frames=len(results), gt_per_frame=GT_PER_FRAME, **m)))
+    if mot_evaluator is not None:
+        m = mot_evaluator.compute()
+
+        def clean(v):   # a class without ground truth, or without a match: null
+            return None if isinstance(v, float) and v != v else v
+        per_class = {n: {k: clean(d[k]) for k in ("mota", "motp", "recall", "ids", "frag", "fp", "fn", "amota", "amotp")}
+                     for n, d in m["label_metrics"].items()}
+        print(json.dumps(dict(metric="mot", frames=len(results), gt_per_frame=GT_PER_FRAME, amota=clean(m["amota"]),
+                              amotp=clean(m["amotp"]), mota=clean(m["mota"]), motp=clean(m["motp"]),
+                              recall=clean(m["recall"]), ids=m["ids"], frag=m["frag"], label_metrics=per_class)))
     return 0
 
 

@@ -54,6 +54,10 @@ in numpy and uploaded as the reference does), in alternating windows of --iters 
 detection rows against the same algorithm as numpy + scipy on the host (with the copy of the boxes it needs), in
 alternating windows.
 
+``--only mot-eval`` (``--mot-eval-out FILE``) times ``TrackingEvaluator.run()`` (cmt_mot_eval_*: keys, sorts, per step cost,
+cmt_lsap and update for every chain, thresholds, summary) on 150 scenes of 40 frames, 7 classes, 30 objects and about 60
+tracked boxes a frame, 40 recall levels, by device events and split by kernel, against tests/_mot_ref.py on the host.
+
 ``--only iou`` (``--iou-out FILE``) times ``native_iou.box_iou`` at 300 x 300 and 2048 x 2048 boxes and
 ``fuse_detections`` of two and of four agents with 300 rows each against the same algorithm as vectorised numpy on the
 host (with the copies it needs), in alternating windows.
@@ -67,7 +71,7 @@ same draws and collision test followed by torch ops per object and per paste box
 runs VoVNet on the one-pass fp16 kernels; everything else is unchanged.
 
     python dev/detector_probe.py [--img-precision ref|fp16] [--points 300000] [--repeats 20] [--warmup 3]
-                                 [--iters 20] [--seed 0] [--out FILE] [--only resize|points|eval|eval-iou|augment|img-augment|gtdb|track|iou]
+                                 [--iters 20] [--seed 0] [--out FILE] [--only resize|points|eval|eval-iou|augment|img-augment|gtdb|track|iou|mot-eval]
                                  [--gtdb-out FILE] [--track-out FILE] [--iou-out FILE] [--resize-out FILE] [--augment-out FILE] [--img-augment-out FILE]
                                  [--points-out FILE] [--sweep-points 27000] [--sweeps K] [--eval-out FILE]
                                  [--eval-frames 800]
@@ -119,10 +123,11 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--img-precision", choices=("ref", "fp16"), default="ref")
     ap.add_argument("--out", default=None)
-    ap.add_argument("--only", choices=("resize", "points", "eval", "eval-iou", "augment", "img-augment", "gtdb", "track", "iou"), default=None,
+    ap.add_argument("--only", choices=("resize", "points", "eval", "eval-iou", "augment", "img-augment", "gtdb", "track", "iou", "mot-eval"), default=None,
                     help="run this section alone")
     ap.add_argument("--gtdb-out", default=None, help="write the ground-truth database section to this file")
     ap.add_argument("--track-out", default=None, help="write the tracker section to this file")
+    ap.add_argument("--mot-eval-out", default=None, help="write the tracking-evaluation section to this file")
     ap.add_argument("--iou-out", default=None, help="write the rotated-box IoU and late-fusion section to this file")
     ap.add_argument("--img-augment-out", default=None, help="write the cmt_img_augment section to this file")
     ap.add_argument("--augment-out", default=None, help="write the cmt_pts_augment section to this file")
@@ -310,6 +315,9 @@ def main():
         return
     if args.only == "iou":
         iou_section(args, dev, say, lines)
+        return
+    if args.only == "mot-eval":
+        mot_eval_section(args, dev, say, lines)
         return
     frames = frame("cmt_fusion_nus")
     frame("cmtcoop_fusion_tumtraf")
@@ -1191,6 +1199,91 @@ def track_section(args, dev, say, lines):
         say(f"{name:>34} {fmt(med(ts))}   one call between two events, over the {FR} frames (launch overhead included)")
     say(f"peak device memory {torch.cuda.max_memory_allocated() / 2 ** 20:.0f} MiB")
     for path, text in ((args.out, lines), (args.track_out, lines[first:])):
+        if path:
+            os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+            with open(path, "w") as f:
+                f.write("\n".join(text) + "\n")
+
+
+def mot_eval_section(args, dev, say, lines):
+    """TrackingEvaluator.run() against the numpy restatement of its contract (tests/_mot_ref.py) on the host"""
+    import time
+    import numpy as np
+    from projects.mmdet3d_plugin import synthetic as S
+    from projects.mmdet3d_plugin.core import evaluation as E
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import _mot_ref as R
+    first = len(lines)
+    SC, FR, OBJ, FALSE, D, C = 150, 40, 30, 30, 64, 7
+    cfg = E.MotEvalConfig(class_names=[f"c{k}" for k in range(C)], max_gt_tracks=OBJ, max_boxes_per_frame=D)
+    ev = E.TrackingEvaluator(cfg, SC * FR, dev)
+    host = {k: [] for k in ("pred_box", "pred_score", "pred_label", "pred_track", "gt_box", "gt_label", "gt_inst")}
+    live, table, boxes = np.arange(D), [], 0
+    for scene in range(SC):
+        for t, f in enumerate(S.moving_scene(args.seed + scene, n_objects=OBJ, frames=FR, grid_cols=6, n_false=FALSE,
+                                             num_classes=C, pad_to=D, with_truth=True)):
+            track = np.where(f["object"] >= 0, f["object"], 1000 + 64 * t + live).astype(np.int32)
+            track[f["count"]:] = -1
+            ev.add(torch.from_numpy(f["boxes"]).to(dev), torch.from_numpy(f["scores"]).to(dev), torch.from_numpy(f["labels"]).to(dev),
+                   torch.from_numpy(track).to(dev), gt_boxes=torch.from_numpy(f["gt_boxes"]).to(dev),
+                   gt_labels=torch.from_numpy(f["gt_labels"]).to(dev), gt_ids=torch.from_numpy(f["gt_ids"]).to(dev), scene=scene)
+            for k, v in (("pred_box", f["boxes"]), ("pred_score", f["scores"]), ("pred_label", f["labels"]), ("pred_track", track),
+                         ("gt_box", f["gt_boxes"]), ("gt_label", f["gt_labels"]), ("gt_inst", f["gt_ids"])):
+                host[k].append(v)
+            table.append((scene, t))
+            boxes += f["count"]
+    R_ = cfg.num_thresholds
+    say(f"--- {torch.cuda.get_device_name(0)}: tracking evaluation, {SC} scenes x {FR} frames, {C} classes, {OBJ} objects and "
+        f"{boxes / len(table):.1f} tracked boxes a frame, {R_} recall levels: {SC * C} chains in phase 1, {SC * C * R_} in phase 2, "
+        f"{FR} steps each; TrackingEvaluator.run(), median of {args.repeats} (min .. max) after {args.warmup} warm-up runs, "
+        "device events around the whole call (they span its host time, the one host read and the launches), ms")
+    for _ in range(args.warmup):
+        ev.run()
+    torch.cuda.synchronize()
+    total = [event_ms(ev.run) for _ in range(args.repeats)]
+    say(f"{'TrackingEvaluator.run()':>34} {fmt(med(total))}")
+    th = []
+    for _ in range(args.repeats):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ev.run()
+        th.append((time.perf_counter() - t0) * 1e3)
+        torch.cuda.synchronize()
+    say(f"{'host side of the call':>34} {fmt(med(th))}   perf_counter without waiting for the device at the end")
+    parts = {}
+    for _ in range(args.repeats):
+        events = []
+        res = ev.run(events=events)
+        torch.cuda.synchronize()
+        one = {}
+        for name, e0, e1 in events:
+            one[name] = one.get(name, 0.0) + e0.elapsed_time(e1)
+        for name, v in one.items():
+            parts.setdefault(name, []).append(v)
+    whole = sum(med(v)[0] for v in parts.values())
+    launches = {"cost": 2 * FR, "lsap": 2 * FR, "update": 2 * FR, "sort": 2}
+    for name, v in parts.items():
+        say(f"{name:>34} {fmt(med(v))}   {100 * med(v)[0] / whole:4.1f} % of the sum; {launches.get(name, 1)} call(s), each "
+            "between two events (launch overhead and the gaps between calls included)")
+    run_max = res["run_max"].cpu().tolist()
+    say(f"longest (frame, class): {run_max[0]} ground-truth boxes, {run_max[1]} predictions; one block of chains per phase "
+        f"(workspace budget {E.NE.MOT_WORKSPACE >> 20} MiB)")
+    inp = dict({k: np.concatenate(v) for k, v in host.items()},
+               pred_frame=np.repeat(np.arange(len(table)), D).astype(np.int32),
+               gt_frame=np.repeat(np.arange(len(table)), OBJ).astype(np.int32), frame_tab=np.array(table, dtype=np.int32),
+               num_scenes=SC, max_steps=FR, class_range=cfg.class_range, dist_th=cfg.dist_th, recall=cfg.recall_levels(),
+               max_gt_tracks=OBJ)
+    t0 = time.perf_counter()
+    ref = R.evaluate(check_unique=False, **inp)
+    host_ms = (time.perf_counter() - t0) * 1e3
+    same = all(np.array_equal(res[k].cpu().numpy(), ref[k], equal_nan=True) for k in ("counters", "counters1", "npos", "thr", "tp_score"))
+    say(f"{'tests/_mot_ref.py on the host':>34} {host_ms:10.0f} ms   once, perf_counter; numpy loops and one "
+        f"scipy.optimize.linear_sum_assignment per frame of a chain: an interpreter's loop, not a tuned host version; "
+        f"device / host {med(total)[0] / host_ms:.5f}; counters, npos, thresholds and tp_score equal: {same}")
+    m = ev.compute()
+    say(f"AMOTA {m['amota']:.4f} AMOTP {m['amotp']:.4f} MOTA {m['mota']:.4f} recall {m['recall']:.4f} IDS {m['ids']} FRAG {m['frag']}")
+    say(f"peak device memory {torch.cuda.max_memory_allocated() / 2 ** 20:.0f} MiB")
+    for path, text in ((args.out, lines), (args.mot_eval_out, lines[first:])):
         if path:
             os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
             with open(path, "w") as f:

@@ -2073,6 +2073,143 @@ int cmt_box_iou(const cmt_box_iou_args* args, void* stream);
 int cmt_box_nms(const cmt_box_nms_args* args, void* stream);
 int cmt_box_concat(const cmt_box_concat_args* args, void* stream);
 
+/* ---- tracking evaluation (moteval.hip; additive to ABI 25) -------------------------------------------------
+ * CLEAR MOT (MOTA, MOTP, id switches, fragmentations) as the motmetrics package accumulates it, swept over
+ * recall levels as the nuScenes tracking devkit does (AMOTA, AMOTP), for boxes, track ids and ground truth with
+ * instance ids that already live on the device.  THIS TEXT is the contract.  It is written from the public
+ * description of both packages and has NOT been compared with an installed devkit or motmetrics; the stated
+ * deviations are listed at the end.
+ *
+ * Inputs.  Predictions: N rows of box fp32 (row stride ld_pred >= 2 floats; column 0 is the centre's x, column 1
+ * its y, nothing else is read), score fp32, label, track and frame int32.  Ground truth: G rows of box (ld_gt),
+ * label, frame and inst int32, the object's instance id inside its scene.  N and G are capacities: with n_pred /
+ * n_gt non-null only rows below that device word (clamped to [0, capacity]) exist.  frame_tab int32 [F][2] gives
+ * (scene, step) of a frame; two frames must not share a pair (not checked on the device: their rows would form one
+ * frame).  A row is IGNORED when its label is outside [0, C), its frame outside [0, F), the frame's scene outside
+ * [0, S) or step outside [0, Fmax), its x or y is not finite, or it fails the range test
+ * sqrt(x * x + y * y) < range[label] (float64 on the float32 centre, product, sum and root rounded on their own,
+ * strict: the test of cmt_det_eval_*); a prediction also when track < 0 or its score is not finite, a ground-truth
+ * row also when inst is outside [0, max_gt_tracks).  The other rows are KEPT.  Instance ids of the kept ground
+ * truth of one frame and class must be distinct (two rows of one instance in one frame leave the instance's
+ * state, and with it IDS and FRAG, unspecified; every access stays in bounds).
+ * Config: C <= 64 classes with range[c] (float64) and dist_th[c] (float32 metres), R <= 64 recall levels
+ * recall[k] in (0, 1] (the caller computes r_k = min_recall + k (1 - min_recall) / (R - 1) in float64, r_0 = 1 for
+ * R = 1), max_gt_tracks <= 65536.
+ *
+ * A CHAIN is (scene, class) in phase 1 and (scene, class, slot k) in phase 2; its number is scene * C + class,
+ * resp. (scene * C + class) * R + k.  It walks step = 0 .. Fmax - 1 and keeps per instance o: m[o], the track it
+ * was last matched to (-1: never), and lost[o], set when it was matched before and missed at its latest
+ * appearance.  A kept prediction is ACTIVE in a chain iff score >= the chain's threshold (float32, inclusive;
+ * phase 1: every kept prediction is active).  At a step the chain sees the kept ground truth i = 0 .. n_gt - 1 of
+ * its (frame, class) in row order and the active predictions j = 0 .. n_pred - 1 in row order, and does:
+ *  1. d_ij = sqrtf(fl32(fl32(dx * dx) + fl32(dy * dy))), dx, dy the float32 centre differences: every operation is
+ *     an IEEE single operation rounded on its own (the file is built with -ffp-contract=off; hipcc's default
+ *     float32 sqrt is correctly rounded).  A pair is ADMISSIBLE iff d_ij < dist_th[class] (strict; a non-finite d
+ *     fails).
+ *  2. Sticky pass, i ascending: if m[o_i] >= 0 and an active, not yet taken j has track_j == m[o_i] and (i, j) is
+ *     admissible, the lowest such j is matched to i and both are taken.
+ *  3. Assignment: cost[i][j] = d_ij if (i, j) is admissible and neither is taken, else CMT_MOT_BIG; the matrix
+ *     [n_gt][n_pred] (row stride ld) and its descriptor (offset, n_gt, n_pred, ld) go through cmt_lsap (Nq = n_gt,
+ *     ngt = n_pred) unchanged.  A pair counts iff match_g[i] == j, match_q[j] == i and cost[i][j] < CMT_MOT_BIG.
+ *     The optimum minimises the sum of distances over the largest number of admissible pairs; where it is not
+ *     unique cmt_lsap's tie rule (its header text) decides.
+ *  4. Accounting, i ascending.  Matched to a prediction of track h at distance d:  TP += 1; dist_sum += d (a
+ *     float64 sum of the float32 d, in this order); IDS += 1 if m[o] >= 0 and m[o] != h; FRAG += 1 if lost[o]; then
+ *     m[o] = h, lost[o] = 0.  Unmatched: FN += 1; lost[o] = (m[o] >= 0).  FP += n_pred - (matches of the step),
+ *     NPRED += n_pred.  The six counters are int64 in the order TP, FP, FN, IDS, FRAG, NPRED.
+ * Phase 1 also writes tp_score[g] for every ground-truth row g: the score of its matched prediction, a quiet NaN
+ * for an unmatched or ignored row; and tp_key[g] = class << 32 | ~ord(score) (INT64_MAX where tp_score is NaN; ord:
+ * the order-preserving uint32 of a float, -0 as +0), which the caller sorts ascending: per class the true-positive
+ * scores in descending order.
+ * Thresholds.  npos[c] = the kept ground truth of class c.  need_k = max(1, ceil(recall[k] * npos)), the product
+ * in float64.  thr[c][k] = the need_k-th (1-based) of the class's descending true-positive scores; with fewer true
+ * positives, or npos = 0, the slot is NOT ACHIEVED and thr is a quiet NaN.  A chain of a slot not achieved does
+ * nothing: all its counters are 0.
+ * Summary.  Per (class, slot) the chains' counters are added over the scenes in ascending scene order (integers;
+ * dist_sum as a float64 sum in that order) into counters[C][R][6] and dist_sum[C][R]; likewise phase 1 into
+ * counters1[C][6] and dist_sum1[C].  metrics[C][R][4] = recall, MOTA, MOTP, MOTAR in float64, every operation
+ * rounded on its own, with n = npos, e = IDS + FP + FN (int64):
+ *   recall = TP / n;  MOTA = 1 - e / n;  MOTP = dist_sum / TP (dist_th if TP = 0);
+ *   MOTAR = max(0, 1 - (e - (1 - recall) * n) / (recall * n)), 0 if TP = 0.
+ * A slot not achieved has recall = MOTA = MOTAR = 0 and MOTP = dist_th (its counters are 0).  class_sum[C][12]
+ * float64: AMOTA (the mean of MOTAR over all R slots, a serial sum in slot order divided by R), AMOTP (the same
+ * mean of MOTP), best (the achieved slot of highest MOTA, the lowest k on a tie; -1 if none is achieved), then
+ * that slot's MOTA, MOTP, recall, TP, FP, FN, IDS, FRAG and threshold (NaN if best = -1).  A class with npos = 0
+ * has NaN in all of metrics and class_sum but best = -1.
+ *
+ * Calls, all stream-ordered, one args struct:
+ *   cmt_mot_eval_keys        key_pred[N], key_gt[G] int64 = ((scene * Fmax + step) << 6 | class) << 32 | row, INT64_MAX
+ *                            for an ignored row; tp_score / tp_key of the ignored ground-truth rows.
+ *   the caller sorts both key arrays ascending (sk_pred, sk_gt): the kept rows of one (frame, class) become one
+ *   contiguous run in row order, found by binary search.
+ *   cmt_mot_eval_runs        npos[C] and run_max[2][CMT_MOT_RUN_PARTS] int32: the longest run of ground truth ([0][s]) and
+ *                            of predictions ([1][s]) among the runs that end in slice s of the sorted keys (slice s holds
+ *                            the tiles of 256 keys whose number is s modulo CMT_MOT_RUN_PARTS).  The caller reads them
+ *                            once and passes Gmax >= the largest of run_max[0], Hmax >= the largest of run_max[1].
+ *   per phase, per block of chains [chain0, chain0 + nchains), per step 0 .. Fmax - 1 in order:
+ *     cmt_mot_eval_cost      one wave per chain: active predictions compacted in row order into cols[nchains][Hmax]
+ *                            (prediction rows), the sticky pass into smatch[nchains][Gmax] (column or -1), cost
+ *                            [nchains][Gmax][Hmax] and desc[nchains][4] = (chain * Gmax * Hmax, n_gt, n_pred, Hmax);
+ *                            at step 0 also m = -1, lost = 0 for the block's state_m [nchains][max_gt_tracks] int32
+ *                            and state_lost (uint8).  Runs longer than Gmax / Hmax are cut there.
+ *     cmt_lsap               P = nchains, max_nq = max(Gmax, 1), max_ngt = max(Hmax, 1), match_g rows of Gmax,
+ *                            match_q rows of Hmax.
+ *     cmt_mot_eval_update    one wave per chain: the accounting into chain_cnt[chains of the phase][6] int64 and
+ *                            chain_dist (float64) of the chain's own number (step 0 starts from 0, so nothing
+ *                            needs a memset), the state, and in phase 1 tp_score / tp_key.
+ *   The blocks of a phase cover its chains once each; the result does not depend on the split.
+ *   cmt_mot_eval_thresholds  after phase 1 and the caller's ascending sort of tp_key (sk_tp, si_tp): thr[C][R].
+ *   cmt_mot_eval_summary     after phase 2: the outputs of "Summary" from chain_cnt1 / chain_dist1 [S * C] and
+ *                            chain_cnt2 / chain_dist2 [S * C * R].
+ * Every output element has exactly one writer, there are no atomics, two runs are bitwise equal.  Counts and ids
+ * read from device memory (n_pred, n_gt, desc, inst, the match tables, si_tp) are clamped or range-checked before
+ * they index anything.
+ * CMT_EINVAL before any device work: a null struct; N or G outside [0, 2^31); F, S, Fmax, C, R or max_gt_tracks
+ * < 1; S * Fmax > 2^24; ld_pred or ld_gt < 2; a range or dist_th that is not finite and positive; a recall level
+ * outside (0, 1]; phase not 1 or 2; step outside [0, Fmax); chain0 < 0, nchains < 1 or chain0 + nchains above
+ * the phase's chains; Gmax or Hmax < 0; a null or misaligned pointer that the call uses (the row arrays only with
+ * N resp. G > 0).  CMT_ENOTSUP: C > 64; R > 64; max_gt_tracks > 65536; nchains > 65535; Gmax > 512; Hmax > 2048
+ * (the last three are cmt_lsap's own limits).
+ * Deviations from the devkit: the thresholds are order statistics of the true-positive scores (the devkit
+ * interpolates between them with numpy.interp); MOTAR uses the achieved recall; there is no max_switch_time; the
+ * devkit's track interpolation, its TID / LGD / FAF and the per-scene breakdown are not computed. */
+#define CMT_MOT_MAX_CLASSES 64
+#define CMT_MOT_MAX_THRESHOLDS 64
+#define CMT_MOT_MAX_GT_TRACKS 65536
+#define CMT_MOT_MAX_GT 512
+#define CMT_MOT_MAX_PRED 2048
+#define CMT_MOT_MAX_CHAINS 65535
+#define CMT_MOT_RUN_PARTS 64
+#define CMT_MOT_BIG 1.0e6f
+typedef struct cmt_mot_eval_args {
+    int64_t N, G;                                  /* capacities (rows) */
+    int F, S, Fmax, C, R, ld_pred, ld_gt, max_gt_tracks;
+    int phase, step, chain0, nchains, Gmax, Hmax;  /* cost / update only */
+    double range[CMT_MOT_MAX_CLASSES], recall[CMT_MOT_MAX_THRESHOLDS];
+    float dist_th[CMT_MOT_MAX_CLASSES];
+    const void *pred_box, *pred_score, *pred_label, *pred_track, *pred_frame;
+    const void *gt_box, *gt_label, *gt_frame, *gt_inst;
+    const int *n_pred, *n_gt;                      /* device words, or null: all rows */
+    const void* frame_tab;                         /* int32 [F][2] */
+    void *key_pred, *key_gt;                       /* int64 [N], [G]: written by cmt_mot_eval_keys */
+    const void *sk_pred, *sk_gt;                   /* int64: the sorted keys */
+    void *npos, *run_max;                          /* int32 [C], [2][CMT_MOT_RUN_PARTS]: written by cmt_mot_eval_runs */
+    void *tp_score, *tp_key;                       /* fp32 [G], int64 [G] */
+    const void *sk_tp, *si_tp;                     /* int64 [G]: tp_key sorted, and the sort's indices */
+    void* thr;                                     /* fp32 [C][R] */
+    void *chain_cnt1, *chain_dist1, *chain_cnt2, *chain_dist2;
+    void *state_m, *state_lost, *cost, *desc, *cols, *smatch;   /* the block's workspace */
+    const int *match_q, *match_g;                  /* cmt_lsap's tables, rows of Hmax and Gmax */
+    void *counters, *dist_sum, *metrics, *class_sum, *counters1, *dist_sum1;
+} cmt_mot_eval_args;
+int64_t cmt_mot_eval_args_size(void);
+int cmt_mot_eval_keys(const cmt_mot_eval_args* args, void* stream);
+int cmt_mot_eval_runs(const cmt_mot_eval_args* args, void* stream);
+int cmt_mot_eval_cost(const cmt_mot_eval_args* args, void* stream);
+int cmt_mot_eval_update(const cmt_mot_eval_args* args, void* stream);
+int cmt_mot_eval_thresholds(const cmt_mot_eval_args* args, void* stream);
+int cmt_mot_eval_summary(const cmt_mot_eval_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
