@@ -17,7 +17,9 @@ called by hand.  Differences from the reference, all of scope:
 * a cloud may be the padded buffer of ``native_pts.prepare_points`` (kept rows first, NaN rows after them) as it
   is: the voxelizer drops non-finite points and keeps input order, so the result equals the trimmed cloud's bit
   for bit and the count never has to reach the host;
-* ``aug_test`` and ``show_results`` are not built.
+* ``show_results`` writes PNG pictures drawn on the device (core/visualizer: the top view, and camera overlays when
+  the data carries uint8 frames), not mmdet3d's ``.obj`` files, and ``show=True`` raises (there is no display);
+* ``aug_test`` is not built.
 
 State-dict keys are the reference's: ``img_backbone.*``, ``img_neck.*``, ``pts_middle_encoder.*``,
 ``pts_backbone.*``, ``pts_neck.*``, ``pts_bbox_head.*``; the voxel layer, the VFE and the detector add none.
@@ -226,3 +228,8 @@ class CmtDetector(nn.Module):
 
     def check_input_range(self):
         check_children_range(self)
+
+    def show_results(self, data, result, out_dir, show=False, score_thr=None):
+        """the reference's signature (coop_base.py:31); see core/visualizer.show_results for what is written"""
+        from ...core.visualizer import show_results
+        return show_results(self, data, result, out_dir, show=show, score_thr=score_thr)

@@ -5,8 +5,8 @@ and point features, and the CmtHeadCoop decodes both agents' memories and max-fu
 the frame's whole ``img_metas``; the head selects each agent's entries by key prefix (``vehicle_`` /
 ``infrastructure_``).  A missing agent or modality reaches the head as ``[None]`` (cmt_coop.py:552-561).
 State-dict keys: ``vehicle_model.*``, ``infrastructure_model.*`` (each with CmtDetector's keys) and
-``pts_bbox_head.*`` -- what ``merge_coop_checkpoints`` writes.  Training, ``aug_test`` and ``show_results``
-are not built (see cmt.py).
+``pts_bbox_head.*`` -- what ``merge_coop_checkpoints`` writes.  Training and ``aug_test`` are not built (see
+cmt.py); ``show_results`` writes PNG pictures of both agents' clouds (core/visualizer).
 """
 import copy
 
@@ -112,3 +112,8 @@ class CmtCoopDetector(nn.Module):
 
     def check_input_range(self):
         check_children_range(self)
+
+    def show_results(self, data, result, out_dir, show=False, score_thr=None, gt_bboxes=None):
+        """the reference's signature (cmt_coop.py:637); see core/visualizer.show_results for what is written"""
+        from ...core.visualizer import show_results
+        return show_results(self, data, result, out_dir, show=show, score_thr=score_thr, gt_bboxes=gt_bboxes)

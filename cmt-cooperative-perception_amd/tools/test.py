@@ -75,6 +75,14 @@ over f * 0.1 s, with instance ids equal to the row index.  It prints one JSON li
 ``fp`` / ``fn`` (null for a class without ground truth).  The detections are still independent draws, so the numbers
 say nothing about tracking quality; the path is the one a sequence would take.
 
+``--show-dir DIR [--show-score-thr S]`` (the reference's ``--show-dir``; it counts as an operation beside ``--out`` /
+``--eval`` / ``--format-only``) writes one top view per frame, ``DIR/{frame:06d}_bev.png``: every agent's cloud in its
+own colour ramp, the frame's boxes (after ``--nms``) in the class colours, the ground truth when an ``--eval`` built it,
+track ids and trails with ``--track``.  With ``--detector`` on a config with cameras it also writes
+``DIR/{frame:06d}_cam{v}.png``, the loaded frames with the same overlays through the uncropped ``lidar2img``.  The
+pictures are drawn on the device (``core/visualizer``, cmt_render_*); the run prints ``wrote N pictures to DIR``.
+Stated deviation: PNG pictures, not mmdet3d's ``.obj`` files, and ``--show`` alone (a window) exits with status 2.
+
 Config 1 of BASELINE.json: ``python cmt-cooperative-perception_amd/tools/test.py
 cmt_lidar_nus --synthetic --num-query 32 --num-layers 1 --points 1000 --eval bbox``.
 The head runs on a HIP device only -- there is no CPU path; without a GPU the
@@ -148,6 +156,11 @@ def parse_args(argv=None):
                         "written, evaluated, tracked or formatted; the JSON frames gain nms_kept (default: off)")
     p.add_argument("--nms-thr", type=float, default=None,
                    help="IoU threshold of --nms (default: the config's test_cfg nms_thr, else 0.2)")
+    p.add_argument("--show", action="store_true", help="not built (there is no display): use --show-dir")
+    p.add_argument("--show-dir", default=None, metavar="DIR",
+                   help="write every frame's top view (and with --detector the camera overlays) as PNG files into DIR")
+    p.add_argument("--show-score-thr", type=float, default=None, metavar="S",
+                   help="draw only boxes that score above S (default: every box)")
     p.add_argument("--seed", type=int, default=0, help="random seed")
     p.add_argument("--cfg-options", nargs="+", default=None, metavar="KEY=VALUE",
                    help="override head config entries (dotted keys into pts_bbox_head, Python literals)")
@@ -155,7 +168,9 @@ def parse_args(argv=None):
     p.add_argument("--gpu-id", type=int, default=0, help="id of gpu to use (non-distributed)")
     p.add_argument("--local_rank", type=int, default=0)
     a = p.parse_args(argv)
-    if not (a.out or a.eval or a.format_only):
+    if a.show:
+        p.error("--show opens a window and there is no display: write the pictures with --show-dir DIR")
+    if not (a.out or a.eval or a.format_only or a.show_dir):
         p.error('Please specify at least one operation (save/eval/format the results) with the argument '
                 '"--out", "--eval" or "--format-only"')
     if a.eval and a.format_only:
@@ -260,8 +275,9 @@ def build_detector_model(args, name, device):
     return model, cfg
 
 
-def detector_frame_inputs(name, cfg, meta, frame, args, device):
-    """One synthetic frame for the detector -> (forward_test keyword arguments, per-agent point clouds)."""
+def detector_frame_inputs(name, cfg, meta, frame, args, device, show=None):
+    """One synthetic frame for the detector -> (forward_test keyword arguments, per-agent point clouds).  ``show``: a
+    list that receives, per agent with cameras, (the uint8 frames as loaded, their lidar2img without resize or crop)."""
     import numpy as np
     from projects.mmdet3d_plugin import native_img as NI
     from projects.mmdet3d_plugin import native_pts as NP
@@ -317,6 +333,9 @@ def detector_frame_inputs(name, cfg, meta, frame, args, device):
             img = NI.prepare_images(frames, crop=crop)
             metas[prefix + "lidar2img"] = [NI.crop_lidar2img(K, S.camera_lidar2img(y, f=1.0, cx=0.0, cy=0.0), crop)
                                            for y in yaws]
+        if show is not None:
+            full = [NI.crop_lidar2img(K, S.camera_lidar2img(y, f=1.0, cx=0.0, cy=0.0), (0, 0)) for y in yaws]
+            show.append((frames, list(NP.lidar2img_to_infra(np.stack(full), to_infra)) if to_infra is not None else full))
         if to_infra is not None:
             metas[prefix + "lidar2img"] = list(NP.lidar2img_to_infra(np.stack(metas[prefix + "lidar2img"]), to_infra))
         metas[prefix + "pad_shape"] = [tuple(img.shape[2:]) + (3,)] * len(yaws)
@@ -536,6 +555,35 @@ def _run(args, name, device, rank, world, distributed):
     if args.nms:
         nms_thr = args.nms_thr if args.nms_thr is not None else float((cfg.get("test_cfg") or {}).get("nms_thr", 0.2))
 
+    visualizer, pictures = None, 0
+    if args.show_dir and distributed:
+        raise SystemExit("--show-dir draws the frames of one process: run it without a launcher")
+    if args.show_dir:
+        from projects.mmdet3d_plugin.core.visualizer import Visualizer, write_png
+        visualizer = Visualizer(class_names, meta["point_cloud_range"], device=device)
+        os.makedirs(args.show_dir, exist_ok=True)
+
+    def show_frame(frame, points, boxes, scores, labels, track, cams):
+        """--show-dir: the frame's pictures; the boxes carry the bottom z of get_bboxes, the ground truth the centre"""
+        kw = dict(boxes=boxes.float().to(device), scores=scores.float().to(device), labels=labels.to(device),
+                  score_thr=args.show_score_thr, z_origin=0.0, gt_z_origin=0.5)
+        if mot_evaluator is not None:
+            kw["gt_boxes"], kw["gt_labels"] = track_ground_truth(frame, args.seed, meta["point_cloud_range"], len(class_names))[:2]
+        elif want_nds or want_iou:
+            kw["gt_boxes"], kw["gt_labels"] = frame_ground_truth(frame, args.seed, pcr, len(class_names))
+        if tracker is not None:
+            kw["track_ids"] = track["track_ids"]
+            kw["trails"] = tracker.tracks(confirmed=False)["history"]
+        write_png(os.path.join(args.show_dir, f"{frame:06d}_bev.png"), visualizer.bev(points, **kw))
+        n, v0 = 1, 0
+        for frames, l2i in cams:
+            pics = visualizer.cameras(frames, l2i, points=points, **kw).cpu()
+            for v in range(pics.shape[0]):
+                write_png(os.path.join(args.show_dir, f"{frame:06d}_cam{v0 + v}.png"), pics[v])
+            v0 += int(pics.shape[0])
+            n += int(pics.shape[0])
+        return n
+
     empty_gt = []   # per frame, a device count of the ground truth without points (--count-gt-points)
 
     def feed(frame, boxes, scores, labels, points=None):
@@ -558,7 +606,8 @@ def _run(args, name, device, rank, world, distributed):
     with torch.no_grad():
         for f in range(rank, args.frames, world):
             if args.detector:
-                kw, points = detector_frame_inputs(name, dcfg, meta, f, args, device)
+                cams = [] if visualizer is not None else None
+                kw, points = detector_frame_inputs(name, dcfg, meta, f, args, device, show=cams)
             else:
                 feats, metas, points = frame_inputs(name, meta, f, args, device)
             # the voxel layer of the detector (cmt.py:88-113 + HardSimpleVFE), per agent
@@ -579,6 +628,8 @@ def _run(args, name, device, rank, world, distributed):
             track = {}
             if tracker is not None:
                 track = track_frame(tracker, f, boxes, scores, labels, device, args.format_only, feed_track(f))
+            if visualizer is not None:
+                pictures += show_frame(f, points, boxes, scores, labels, track, (cams or []) if args.detector else [])
             results.append(dict(frame=f, voxels=vox_stats, **track, **nms,
                                 boxes_3d=boxes.float().cpu().tolist(), scores_3d=scores.float().cpu().tolist(),
                                 labels_3d=labels.cpu().tolist(),
@@ -613,6 +664,8 @@ def _run(args, name, device, rank, world, distributed):
             detections_to_openlabel(dets, filename=f"frame_{r['frame']:06d}.json",
                                     output_folder_path=args.openlabel_dir, frame_id=r["frame"])
         print(f"wrote {len(results)} OpenLABEL file(s) to {args.openlabel_dir}")
+    if visualizer is not None:
+        print(f"wrote {pictures} pictures to {args.show_dir}")
     if args.eval:
         n = [len(r["scores_3d"]) for r in results]
         s = [x for r in results for x in r["scores_3d"]]

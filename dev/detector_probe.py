@@ -62,6 +62,12 @@ tracked boxes a frame, 40 recall levels, by device events and split by kernel, a
 ``fuse_detections`` of two and of four agents with 300 rows each against the same algorithm as vectorised numpy on the
 host (with the copies it needs), in alternating windows.
 
+``--only render`` (``--render-out FILE``) times the result pictures (core/visualizer, cmt_render_*): ``Visualizer.bev``
+on a cloud of --points rows with 300 box rows and their ids at 800 x 800, and ``Visualizer.cameras`` on six 900 x 1600
+frames.  Every launch is timed alone by device events, the clear of the key plane among them (5 MB for the top view,
+6.9 MB per camera view: both are counted in the whole), and the whole call by the host clock against the same algorithm as
+vectorised numpy (float32) on the host with the copies it needs.
+
 ``--only gtdb`` (``--gtdb-out FILE``) times the ground-truth database (native_gtdb.py) in alternating windows of --iters
 calls: ``GtDatabase.add_frame`` on one cloud of --points rows with 64 boxes against a boolean-mask chain per box and
 ``torch.cat``; and ``UnifiedDataBaseSampler.sample_all`` + ``augment_points`` on a database of 320 objects against the
@@ -71,7 +77,7 @@ same draws and collision test followed by torch ops per object and per paste box
 runs VoVNet on the one-pass fp16 kernels; everything else is unchanged.
 
     python dev/detector_probe.py [--img-precision ref|fp16] [--points 300000] [--repeats 20] [--warmup 3]
-                                 [--iters 20] [--seed 0] [--out FILE] [--only resize|points|eval|eval-iou|augment|img-augment|gtdb|track|iou|mot-eval]
+                                 [--iters 20] [--seed 0] [--out FILE] [--only resize|points|eval|eval-iou|augment|img-augment|gtdb|track|iou|mot-eval|render]
                                  [--gtdb-out FILE] [--track-out FILE] [--iou-out FILE] [--resize-out FILE] [--augment-out FILE] [--img-augment-out FILE]
                                  [--points-out FILE] [--sweep-points 27000] [--sweeps K] [--eval-out FILE]
                                  [--eval-frames 800]
@@ -123,8 +129,9 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--img-precision", choices=("ref", "fp16"), default="ref")
     ap.add_argument("--out", default=None)
-    ap.add_argument("--only", choices=("resize", "points", "eval", "eval-iou", "augment", "img-augment", "gtdb", "track", "iou", "mot-eval"), default=None,
+    ap.add_argument("--only", choices=("resize", "points", "eval", "eval-iou", "augment", "img-augment", "gtdb", "track", "iou", "mot-eval", "render"), default=None,
                     help="run this section alone")
+    ap.add_argument("--render-out", default=None, help="write the result-picture section to this file")
     ap.add_argument("--gtdb-out", default=None, help="write the ground-truth database section to this file")
     ap.add_argument("--track-out", default=None, help="write the tracker section to this file")
     ap.add_argument("--mot-eval-out", default=None, help="write the tracking-evaluation section to this file")
@@ -318,6 +325,9 @@ def main():
         return
     if args.only == "mot-eval":
         mot_eval_section(args, dev, say, lines)
+        return
+    if args.only == "render":
+        render_section(args, dev, say, lines)
         return
     frames = frame("cmt_fusion_nus")
     frame("cmtcoop_fusion_tumtraf")
@@ -1362,6 +1372,201 @@ def host_fuse(results, poses, thr):
             kept.append(r)
             removed[r + 1:] |= sup[r, r + 1:]
     return b[kept], s_[kept], lab[kept]
+
+
+# ---- result pictures ---------------------------------------------------------------------------------------------
+_FONT = ((0x0E, 0x11, 0x13, 0x15, 0x19, 0x11, 0x0E), (0x04, 0x0C, 0x04, 0x04, 0x04, 0x04, 0x0E),
+         (0x0E, 0x11, 0x01, 0x02, 0x04, 0x08, 0x1F), (0x1F, 0x02, 0x04, 0x02, 0x01, 0x11, 0x0E),
+         (0x02, 0x06, 0x0A, 0x12, 0x1F, 0x02, 0x02), (0x1F, 0x10, 0x1E, 0x01, 0x01, 0x11, 0x0E),
+         (0x06, 0x08, 0x10, 0x1E, 0x11, 0x11, 0x0E), (0x1F, 0x01, 0x02, 0x04, 0x08, 0x08, 0x08),
+         (0x0E, 0x11, 0x11, 0x0E, 0x11, 0x11, 0x0E), (0x0E, 0x11, 0x11, 0x0F, 0x01, 0x02, 0x0C))
+
+
+def _host_picture(views, near, H, W, pts, lut, boxes, scores, labels, ids, palette, *, color_col, lo, span, near_wins,
+                  radius, z_origin, src=None):
+    """The picture of Visualizer.bev / .cameras as vectorised numpy float32 on the host (the contract of cmt_hip.h: the
+    key plane, maxima by np.maximum.at): points, box frames, ids, resolve -> uint8 [V, H, W, 3]"""
+    import numpy as np
+    f32, u64 = np.float32, np.uint64
+    V = len(views)
+    plane = np.zeros((V, H * W), dtype=u64)                       # the clear
+
+    def rows(m, x, y, z):
+        return [((f32(m[r, 0]) * x + f32(m[r, 1]) * y) + f32(m[r, 2]) * z) + f32(m[r, 3]) for r in range(4)]
+
+    def put(v, X, Y, key):
+        ok = (X >= 0) & (X < W) & (Y >= 0) & (Y < H)
+        np.maximum.at(plane[v], (Y[ok] * W + X[ok]), key[ok] if isinstance(key, np.ndarray) else key)
+
+    with np.errstate(all="ignore"):
+        x, y, z = pts[:, 0], pts[:, 1], pts[:, 2]
+        fin = np.isfinite(x) & np.isfinite(y) & np.isfinite(z)
+        inv = f32(1.0) / f32(span)
+        for v, m in enumerate(views):
+            r0, r1, d, r3 = rows(m, x, y, z)
+            u, w = r0 / r3, r1 / r3
+            ok = fin & (r3 >= f32(near)) & np.isfinite(d) & (u >= 0) & (u < f32(W)) & (w >= 0) & (w < f32(H))
+            X, Y = np.floor(u[ok]).astype(np.int64), np.floor(w[ok]).astype(np.int64)
+            c = pts[ok, color_col] if color_col >= 0 else d[ok]
+            t = ((c - f32(lo)) * inv) * f32(255.0)
+            idx = np.where(t >= 255, 255, np.where(t >= 0, np.floor(t), 0)).astype(np.int64)
+            b = d[ok].view(np.uint32)
+            o = np.where(b >> 31, ~b, b ^ np.uint32(0x80000000))
+            key = ((~o if near_wins else o).astype(u64) << u64(24)) | (lut[idx].astype(u64) & u64(0xFFFFFF))
+            for j in range(-radius, radius + 1):
+                for i in range(-radius, radius + 1):
+                    put(v, X + i, Y + j, key)
+
+        # boxes: corners, then the thirteen segments of every row through the clip and the walk
+        bx = boxes[:, :7].astype(f32)
+        valid = np.isfinite(bx).all(1) & (bx[:, 3:6] > 0).all(1) & (scores > -np.inf)
+        hx, hy, s, c = bx[:, 3] * f32(0.5), bx[:, 4] * f32(0.5), np.sin(bx[:, 6]), np.cos(bx[:, 6])
+        bot = bx[:, 2] - f32(z_origin) * bx[:, 5]
+        top = bot + bx[:, 5]
+        cor = []
+        for sx, sy in ((-1, -1), (-1, 1), (1, 1), (1, -1)):
+            lx, ly = f32(sx) * hx, f32(sy) * hy
+            cor.append(((lx * c - ly * s) + bx[:, 0], (lx * s + ly * c) + bx[:, 1]))
+        c3 = [(X, Y, bot) for X, Y in cor] + [(X, Y, top) for X, Y in cor]
+        edges = [(c3[k], c3[(k + 1) % 4]) for k in range(4)] + [(c3[k + 4], c3[(k + 1) % 4 + 4]) for k in range(4)] + \
+                [(c3[k], c3[k + 4]) for k in range(4)] + [((bx[:, 0], bx[:, 1], top), (hx * c + bx[:, 0], hx * s + bx[:, 1], top))]
+        bkey = (u64(2) << u64(56)) | ((u64(0xFFFFFFFF) - np.arange(len(bx), dtype=u64)) << u64(24)) | \
+               (palette[np.clip(labels, 0, len(palette) - 1)].astype(u64) & u64(0xFFFFFF))
+        for v, m in enumerate(views):
+            for a, b in edges:
+                A, B = rows(m, *a), rows(m, *b)
+                ok = valid & np.isfinite(np.stack(A + B)).all(0)
+                ina, inb = A[3] >= f32(near), B[3] >= f32(near)
+                ok &= ina | inb
+                t = (f32(near) - A[3]) / (B[3] - A[3])
+                c0, c1 = A[0] + t * (B[0] - A[0]), A[1] + t * (B[1] - A[1])
+                cut_b, cut_a = ina & ~inb, inb & ~ina
+                A0, A1, A3 = np.where(cut_a, c0, A[0]), np.where(cut_a, c1, A[1]), np.where(cut_a, f32(near), A[3])
+                B0, B1, B3 = np.where(cut_b, c0, B[0]), np.where(cut_b, c1, B[1]), np.where(cut_b, f32(near), B[3])
+                ua, va, ub, vb = A0 / A3, A1 / A3, B0 / B3, B1 / B3
+                dx, dy = ub - ua, vb - va
+                ok &= np.isfinite(np.stack([ua, va, ub, vb, dx, dy])).all(0)
+                t0, t1 = np.zeros_like(ua), np.ones_like(ua)
+                for p, q in ((-dx, ua + f32(1.0)), (dx, f32(W + 1) - ua), (-dy, va + f32(1.0)), (dy, f32(H + 1) - va)):
+                    r = q / p
+                    ok &= ~((p == 0) & (q < 0)) & ~((p < 0) & (r > t1)) & ~((p > 0) & (r < t0))
+                    t0 = np.where((p < 0) & (r > t0), r, t0)
+                    t1 = np.where((p > 0) & (r < t1), r, t1)
+                xa, ya = np.where(t0 > 0, ua + t0 * dx, ua), np.where(t0 > 0, va + t0 * dy, va)
+                xb, yb = np.where(t1 < 1, ua + t1 * dx, ub), np.where(t1 < 1, va + t1 * dy, vb)
+                for e in np.nonzero(ok)[0]:
+                    X0, Y0 = int(min(max(np.floor(xa[e]), -2), W + 2)), int(min(max(np.floor(ya[e]), -2), H + 2))
+                    X1, Y1 = int(min(max(np.floor(xb[e]), -2), W + 2)), int(min(max(np.floor(yb[e]), -2), H + 2))
+                    n = max(abs(X1 - X0), abs(Y1 - Y0))
+                    k = np.arange(n + 1, dtype=np.int64)
+                    den = max(2 * n, 1)
+                    put(v, X0 + (2 * (X1 - X0) * k + n) // den, Y0 + (2 * (Y1 - Y0) * k + n) // den, bkey[e])
+            # the ids at the anchors Visualizer uses for gravity-centre rows
+            r0, r1, _, r3 = rows(m, bx[:, 0], bx[:, 1], bx[:, 2] + bx[:, 5] * f32(0.5))
+            u, w = r0 / r3, r1 / r3
+            ok = valid & (ids >= 0) & (r3 >= f32(near)) & (np.abs(u) < 65536) & (np.abs(w) < 65536)
+            for e in np.nonzero(ok)[0]:
+                X0, Y0 = int(np.floor(u[e])), int(np.floor(w[e]))
+                key = (u64(4) << u64(56)) | ((u64(0xFFFFFFFF) - u64(e)) << u64(24)) | u64(0xFFFF00)
+                cells = [(X0 + 6 * j + cx, Y0 + cy) for j, ch in enumerate(str(int(ids[e]))) for cy in range(7)
+                         for cx in range(5) if (_FONT[int(ch)][cy] >> (4 - cx)) & 1]
+                cells = np.array(cells, dtype=np.int64)
+                put(v, cells[:, 0], cells[:, 1], key)
+    rgb = (plane & u64(0xFFFFFF)).astype(np.uint32).reshape(V, H, W)
+    out = np.stack([(rgb >> 16) & 0xFF, (rgb >> 8) & 0xFF, rgb & 0xFF], -1).astype(np.uint8)
+    if src is not None:
+        empty = plane.reshape(V, H, W) == 0
+        out[empty] = src[empty]
+    return out
+
+
+def render_section(args, dev, say, lines):
+    """Visualizer.bev and Visualizer.cameras: every launch alone, and the whole against numpy on the host"""
+    import numpy as np
+    from projects.mmdet3d_plugin import native_render as NR
+    from projects.mmdet3d_plugin import synthetic as S
+    from projects.mmdet3d_plugin.core.visualizer import Visualizer
+    first = len(lines)
+    pcr = [-54.0, -54.0, -5.0, 54.0, 54.0, 3.0]
+    names = ["c%d" % k for k in range(10)]
+    M = 300
+    vis = Visualizer(names, pcr, bev_size=(800, 800), device=dev)
+    pts = S.synthetic_points(args.points, pcr, seed=args.seed, device=dev)
+    gb, gl = S.synthetic_gt(1, pcr, 10, n=M, seed=args.seed + 1, device=dev)
+    boxes, labels = gb[0].contiguous(), gl[0].to(torch.int32)
+    scores = torch.linspace(0.95, 0.05, M, device=dev)
+    ids = torch.arange(M, dtype=torch.int32, device=dev)
+    frames = S.synthetic_frames(6, FRAME[0], FRAME[1], seed=args.seed + 2, device=dev)
+    l2i = [S.camera_lidar2img(y) for y in S.NUS_YAWS]
+    tab = vis._tables()
+    say(f"--- result pictures (cmt_render_*): {args.points} points, {M} box rows with ids; per launch: median of "
+        f"{args.repeats} single calls after {args.warmup} warm-up by device events, ms (min .. max); the whole call by the "
+        "host clock with a synchronisation, against the same algorithm as vectorised numpy float32 on the host (the "
+        "download of the points and boxes it needs included)")
+
+    def stages(tag, V, H, W, views, near, point_kw, src):
+        plane = NR.new_plane(V, H, W, dev)
+        anchors = boxes[:, :3].clone()
+        anchors[:, 2] += boxes[:, 5] * 0.5
+        out = torch.empty((V, H, W, 3), dtype=torch.uint8, device=dev)
+        steps = [(f"clear of the {V * H * W * 8 / 1e6:.1f} MB key plane", lambda: plane.zero_()),
+                 ("cmt_render_points", lambda: NR.render_points(plane, views, pts, near=near, **point_kw)),
+                 ("cmt_render_boxes", lambda: NR.render_boxes(plane, views, boxes, scores=scores, score_thr=float("-inf"),
+                                                              labels=labels, class_rgb=tab["palette"], near=near)),
+                 ("cmt_render_digits", lambda: NR.render_digits(plane, views, ids, anchors, near=near)),
+                 ("cmt_render_resolve", lambda: NR.render_resolve(plane, src=src, out=out))]
+        total = 0.0
+        for name, fn in steps:
+            for _ in range(args.warmup):
+                fn()
+            t = med([event_ms(fn) for _ in range(args.repeats)])
+            total += t[0]
+            say(f"{tag + ' ' + name:>52} {fmt(t)}")
+        say(f"{tag + ' sum of the launches':>52} {total:9.3f}")
+
+    def whole(tag, fn, host_fn, host_repeats):
+        for _ in range(args.warmup):
+            fn()
+        ts = []
+        for _ in range(args.repeats):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            got = fn()
+            torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        hs = []
+        for _ in range(host_repeats):
+            t0 = time.perf_counter()
+            want = host_fn()
+            hs.append((time.perf_counter() - t0) * 1e3)
+        diff = int((got.cpu().numpy().reshape(want.shape) != want).any(-1).sum())
+        say(f"{tag + ' whole call, device':>52} {fmt(med(ts))}")
+        say(f"{tag + ' same picture, numpy on the host':>52} {fmt(med(hs))}   ({host_repeats} calls; {diff} of "
+            f"{want.shape[0] * want.shape[1] * want.shape[2]} pixels differ from the device's: sin / cos of the host)")
+
+    bev_pts = dict(lut=tab["height"][0], color_col=2, lo=pcr[2], span=pcr[5] - pcr[2])
+    stages("bev 800 x 800:", 1, 800, 800, vis.view, 0.5, bev_pts, None)
+    kw = dict(boxes=boxes, scores=scores, labels=labels, track_ids=ids, z_origin=0.5)
+
+    def host(views, near, H, W, src, **pk):
+        return _host_picture(views, near, H, W, pts.cpu().numpy(), pk.pop("lut").cpu().numpy(), boxes.cpu().numpy(),
+                             scores.cpu().numpy(), labels.cpu().numpy(), ids.cpu().numpy(), tab["palette"].cpu().numpy(),
+                             z_origin=0.5, src=None if src is None else src.cpu().numpy(), **pk)
+
+    whole("bev 800 x 800:", lambda: vis.bev(pts, **kw),
+          lambda: host(vis.view, 0.5, 800, 800, None, near_wins=False, radius=0, **bev_pts), 3)
+    views = np.stack([NR.camera_view(m) for m in l2i])
+    cam_pts = dict(lut=tab["depth"], color_col=-1, lo=0.0, span=60.0, near_wins=True, radius=1)
+    stages("cameras 6 x 900 x 1600:", 6, FRAME[0], FRAME[1], views, 0.1, cam_pts, frames)
+    whole("cameras 6 x 900 x 1600:", lambda: vis.cameras(frames, l2i, points=pts, **kw),
+          lambda: host(views, 0.1, FRAME[0], FRAME[1], frames, **cam_pts), 2)
+    say("Both clears are counted in the whole calls: the 5.1 MB plane of the top view and the 11.5 MB plane of each "
+        "camera view (69.1 MB for six).  Nothing is read back but the finished picture.")
+    for path, text in ((args.out, lines), (args.render_out, lines[first:])):
+        if path:
+            os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+            with open(path, "w") as f:
+                f.write("\n".join(text) + "\n")
 
 
 def iou_section(args, dev, say, lines):

@@ -2210,6 +2210,171 @@ int cmt_mot_eval_update(const cmt_mot_eval_args* args, void* stream);
 int cmt_mot_eval_thresholds(const cmt_mot_eval_args* args, void* stream);
 int cmt_mot_eval_summary(const cmt_mot_eval_args* args, void* stream);
 
+/* ---- result pictures: top view and camera overlays (render.hip; additive to ABI 25) --------------------------
+ * Points, line segments, box wire frames and decimal numbers drawn into pictures on the device, from buffers that
+ * already live there.  THIS TEXT is the contract.  Every sum, difference, product and quotient below is an IEEE
+ * single operation rounded on its own (none is fused), in the order the parentheses give.  Caller-owned buffers,
+ * stream-ordered, no allocation, no host read: graph-capturable.  Every CMT_EINVAL below is returned before any
+ * device work.
+ *
+ * THE KEY PLANE.  A picture in progress is a uint64 [V][H][W] plane that the caller clears to 0.  Every drawing
+ * call does nothing but atomic maxima (64-bit vector atomics on global memory) on it with the key
+ *   key = layer << 56 | order << 24 | rgb        layer 8 bits, order 32 bits, rgb 24 bits (r << 16 | g << 8 | b)
+ * Maximum is commutative and idempotent: the finished plane does not depend on the order of the launches, of the
+ * waves or of the writers of a pixel, so it is bitwise repeatable with no ordering machinery.  Key 0 is "empty"; no
+ * call below writes it (every order below is non-zero).  layer is chosen per call, 0..255; a higher layer covers a
+ * lower one, within a layer the higher order wins, then the higher rgb.  Colours are uint32 words of which only the
+ * low 24 bits are used.
+ *   okey(f), the order-preserving map of a float to uint32: bits ^ 0x80000000 with the sign bit clear, ~bits
+ *   otherwise.  okey(-0) + 1 == okey(+0); a finite f gives neither 0 nor 0xFFFFFFFF.
+ *
+ * VIEWS.  view[v], v < V <= CMT_RENDER_MAX_VIEWS, is a HOST row-major 4 x 4 float matrix m.  Row r of a scene
+ * position (x, y, z):  R_r = ((m[r][0] * x + m[r][1] * y) + m[r][2] * z) + m[r][3].  The pixel coordinates are
+ * u = R_0 / R_3, v = R_1 / R_3, the depth is d = R_2.  A camera passes its lidar2img with row 3 set to row 2 (the
+ * depth row, by which lidar2img divides), the top view an orthographic matrix (row 3 = 0 0 0 1, row 2 = 0 0 1 0).
+ * A position is BEHIND the view unless R_3 >= near (near: 0.1 for a camera, anything below 1 for the top view).
+ * Pixel (X, Y) of view v is plane[(v * H + Y) * W + X]; it covers X <= u < X + 1, Y <= v < Y + 1.  Every test on u
+ * and v is made on the floats before a conversion to int: a NaN or an infinity never reaches a cast.
+ *
+ * cmt_render_points.  points fp32 [N][ld], ld >= 3, columns x y z first; n null (N) or a device int32 clamped to
+ *   [0, N].  For a row below n and every view: the row is skipped if x, y or z is not finite (the NaN padding of
+ *   cmt_pts_prepare goes in as it is), if it is behind the view, if d is not finite or unless 0 <= u < W and
+ *   0 <= v < H.  X = floor(u), Y = floor(v).
+ *   c = the row's column color_col (3 <= .. < ld; or 0..2), or d with color_col == -1;
+ *   t = ((c - lo) * inv_span) * 255;  index = 255 if t >= 255, floor(t) if 0 <= t < 255, else 0 (a NaN gives 0);
+ *   rgb = lut[index] (a device uint32 [256]);  order = okey(d), or ~okey(d) with near_wins != 0 (the top view leaves
+ *   it clear: the highest point wins; a camera sets it: the nearest wins).
+ *   The key goes to every pixel (X + i, Y + j), |i|, |j| <= radius (0..2), that lies inside the picture.
+ *   One lane per row, grid-stride, one launch for all V views.
+ *
+ * THE SEGMENT, shared by cmt_render_segments, cmt_render_boxes (one device function).  Ends a and b, a view:
+ *   (1) [not planar]  the segment is dropped if a coordinate is not finite.  A_r, B_r: the rows of a and b, r = 0..3;
+ *       dropped if one of the eight is not finite.  ina = A_3 >= near, inb = B_3 >= near; dropped if neither.  If
+ *       exactly one holds: t = (near - A_3) / (B_3 - A_3), C_r = A_r + t * (B_r - A_r) for r = 0, 1, and the end that
+ *       is behind is replaced by (C_0, C_1, near).  Then ua = A_0 / A_3, va = A_1 / A_3, ub = B_0 / B_3,
+ *       vb = B_1 / B_3.
+ *       [planar]  ua, va, ub, vb are the given coordinates.
+ *       Dropped unless ua, va, ub, vb, dx = ub - ua and dy = vb - va are all finite.
+ *   (2) Liang-Barsky against the picture grown by one pixel, xmin = ymin = -1, xmax = W + 1, ymax = H + 1 (as floats).
+ *       t0 = 0, t1 = 1; for (p, q) in (-dx, ua - xmin), (dx, xmax - ua), (-dy, va - ymin), (dy, ymax - va), in that
+ *       order:  if p == 0: dropped if q < 0, else the next pair;  r = q / p;  if p < 0: dropped if r > t1, and
+ *       t0 = r if r > t0;  if p > 0: dropped if r < t0, and t1 = r if r < t1.
+ *       (xa, ya) = (ua + t0 * dx, va + t0 * dy) if t0 > 0, else (ua, va);
+ *       (xb, yb) = (ua + t1 * dx, va + t1 * dy) if t1 < 1, else (ub, vb).
+ *   (3) X0 = floor(xa) clamped to [-2, W + 2], Y0 = floor(ya) clamped to [-2, H + 2] (the clamps on the floats), X1
+ *       and Y1 likewise from (xb, yb).
+ *   (4) THE INTEGER WALK.  dX = X1 - X0, dY = Y1 - Y0, n = max(|dX|, |dY|).  For k = 0..n the pixel is
+ *       (X0 + floordiv(2 * dX * k + n, 2 * n), Y0 + floordiv(2 * dY * k + n, 2 * n)), floordiv rounding towards minus
+ *       infinity; n == 0 draws the one pixel (X0, Y0).  The walk from b to a visits the same pixels.
+ *       With thickness t in 1..3 every walk pixel (X, Y) stands for the t x t square X + i, Y + j with
+ *       -((t - 1) / 2) <= i, j <= t / 2 (integer divisions).  Pixels outside the picture are not written.
+ *   One wave per (segment, view), the lanes across k.
+ *
+ * cmt_render_segments.  p0, p1 fp32 [S][3] scene positions, or with planar != 0 [S][2] pixel coordinates (no view
+ *   is applied; the segment is drawn into all V pictures); rgb uint32 [S]; rank int32 [S] or null (the segment
+ *   index); n null (S) or a device int32 clamped to [0, S].  order = 0xFFFFFFFF - max(rank, 0): the lower rank
+ *   lies on top.
+ *
+ * cmt_render_boxes.  Rows fp32 [M][ld], ld >= 7, z_origin in {0, 0.5}, validity and derived values hx, hy, s, c,
+ *   bot, top exactly as cmt_box_iou (one sinf / cosf pair per box).  A row draws nothing if it is invalid, at or
+ *   beyond count (null: M; a device int32 clamped to [0, M]), or, with scores given, unless score > score_thr.
+ *   Corners k = 0..3 with (sx, sy) = (-,-), (-,+), (+,+), (+,-), cmt_box_iou's order:
+ *     lx = sx * hx, ly = sy * hy,  X_k = (lx * c - ly * s) + x,  Y_k = (lx * s + ly * c) + y;
+ *   corner k is (X_k, Y_k, bot), corner k + 4 is (X_k, Y_k, top).  Thirteen segments, each from the first corner named
+ *   to the second: (k, (k + 1) mod 4), (k + 4, (k + 1) mod 4 + 4), (k, k + 4) for k = 0..3, and the heading mark from
+ *   (x, y, top) to (hx * c + x, hx * s + y, top).  rgb = class_rgb[label] with labels and class_rgb given and
+ *   0 <= label < ncls, else rgb_default.  order = 0xFFFFFFFF - row index: the better-scoring rows of a decoded frame
+ *   lie on top.  One wave per (box, view).
+ *
+ * cmt_render_digits.  values int32 [M] (a negative value draws nothing), anchors fp32 [M][3] scene positions or,
+ *   with planar != 0, [M][2] pixel coordinates; rgb uint32 [M] or null (rgb_one); rank as for segments; scale 1..4.
+ *   The anchor is projected as a point is; it is dropped if it is behind the view, or unless -65536 <= u < 65536 and
+ *   -65536 <= v < 65536.  X0 = floor(u), Y0 = floor(v) is the top left pixel of the first digit.  The decimal digits,
+ *   most significant first, digit j at cell column 6 * j (one column of space).  Cell (cx, cy), cx = 0..4 from the
+ *   left, cy = 0..6 from the top, of digit g is set iff bit (4 - cx) of font[g][cy] is set; a set cell covers the
+ *   scale x scale pixels (X0 + (6 * j + cx) * scale + i, Y0 + cy * scale + l), 0 <= i, l < scale, inside the picture.
+ *   font[10][7] = {0x0E,0x11,0x13,0x15,0x19,0x11,0x0E}, {0x04,0x0C,0x04,0x04,0x04,0x04,0x0E},
+ *     {0x0E,0x11,0x01,0x02,0x04,0x08,0x1F}, {0x1F,0x02,0x04,0x02,0x01,0x11,0x0E}, {0x02,0x06,0x0A,0x12,0x1F,0x02,0x02},
+ *     {0x1F,0x10,0x1E,0x01,0x01,0x11,0x0E}, {0x06,0x08,0x10,0x1E,0x11,0x11,0x0E}, {0x1F,0x01,0x02,0x04,0x08,0x08,0x08},
+ *     {0x0E,0x11,0x11,0x0E,0x11,0x11,0x0E}, {0x0E,0x11,0x11,0x0F,0x01,0x02,0x0C}.
+ *   One wave per (value, view), the lanes across (digit, cell).
+ *
+ * cmt_render_resolve.  plane -> out uint8 [V][H][W][3] (r, g, b).  A pixel with key 0 takes the pixel of
+ *   src uint8 [V][H][W][3] if src is given, else background; any other pixel takes the key's rgb.  out == src is
+ *   allowed (a thread reads and writes its own pixel only); any other overlap is not.
+ *
+ * Limits and CMT_EINVAL, all calls: a null struct; V outside 1..CMT_RENDER_MAX_VIEWS; H or W outside 1..4096; layer
+ *   outside 0..255; near or a used view entry not finite; a null or misaligned plane (8 bytes); another misaligned
+ *   pointer (4 bytes; the uint8 pictures 1).  points: N outside [0, 2^31); ld < 3; color_col outside -1..ld-1;
+ *   radius outside 0..2; lo or inv_span not finite; with N > 0 a null points or lut.  segments: S outside
+ *   [0, CMT_RENDER_MAX_ITEMS); thickness outside 1..3; with S > 0 a null p0, p1 or rgb.  boxes: M outside
+ *   [0, CMT_RENDER_MAX_ITEMS); ld < 7; z_origin not 0 or 0.5; thickness outside 1..3; score_thr NaN; ncls < 0; with
+ *   M > 0 a null boxes.  digits: M outside [0, CMT_RENDER_MAX_ITEMS); scale outside 1..4; with M > 0 a null values or
+ *   anchors.  resolve: a null out.  A count of 0 is a valid call that launches nothing. */
+#define CMT_RENDER_MAX_VIEWS 8
+#define CMT_RENDER_MAX_SIZE 4096
+#define CMT_RENDER_MAX_ITEMS 1048576
+typedef struct cmt_render_target {
+    int V, H, W, layer;
+    float near, reserved_f;
+    float view[CMT_RENDER_MAX_VIEWS][16];
+    void* plane;                              /* uint64 [V][H][W] */
+} cmt_render_target;
+typedef struct cmt_render_points_args {
+    cmt_render_target t;
+    int N, ld, radius, near_wins, color_col, reserved;
+    float lo, inv_span;
+    const void* points;
+    const int* n;
+    const void* lut;                          /* uint32 [256] */
+} cmt_render_points_args;
+typedef struct cmt_render_segments_args {
+    cmt_render_target t;
+    int S, planar, thickness, reserved;
+    const void* p0;
+    const void* p1;
+    const void* rgb;                          /* uint32 [S] */
+    const int* rank;
+    const int* n;
+} cmt_render_segments_args;
+typedef struct cmt_render_boxes_args {
+    cmt_render_target t;
+    int M, ld, thickness, ncls;
+    float z_origin, score_thr;
+    uint32_t rgb_default, reserved;
+    const void* boxes;
+    const int* count;
+    const int* labels;
+    const void* scores;
+    const void* class_rgb;                    /* uint32 [ncls] */
+} cmt_render_boxes_args;
+typedef struct cmt_render_digits_args {
+    cmt_render_target t;
+    int M, planar, scale, reserved;
+    uint32_t rgb_one, reserved_u;
+    const void* values;                       /* int32 [M] */
+    const void* anchors;
+    const void* rgb;                          /* uint32 [M] or null */
+    const int* rank;
+} cmt_render_digits_args;
+typedef struct cmt_render_resolve_args {
+    int V, H, W, reserved;
+    uint32_t background, reserved_u;
+    const void* plane;
+    const void* src;                          /* uint8 [V][H][W][3] or null */
+    void* out;                                /* uint8 [V][H][W][3] */
+} cmt_render_resolve_args;
+int64_t cmt_render_points_args_size(void);
+int64_t cmt_render_segments_args_size(void);
+int64_t cmt_render_boxes_args_size(void);
+int64_t cmt_render_digits_args_size(void);
+int64_t cmt_render_resolve_args_size(void);
+int cmt_render_points(const cmt_render_points_args* args, void* stream);
+int cmt_render_segments(const cmt_render_segments_args* args, void* stream);
+int cmt_render_boxes(const cmt_render_boxes_args* args, void* stream);
+int cmt_render_digits(const cmt_render_digits_args* args, void* stream);
+int cmt_render_resolve(const cmt_render_resolve_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
